@@ -9,11 +9,14 @@ resident in HBM and the solve is open (sobfu_hip_solver_begin) before the timed 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 8 --steps 20 --warmup 5          # re-executes itself under torch.distributed.run
 
-Timing: W untimed warm-up iterations, then `--repeats` (default 7) timed regions of EXACTLY K iterations each, every region
-bracketed by barrier + synchronize on both sides, MAX over ranks per region; `value` is the MEDIAN region (K iterations /
-seconds), every region's rate is listed in `region_its`.  The per-solve fixed cost (entering / leaving the iteration format,
-reading the max-norm rows) is not an iteration and is reported separately (`per_solve`).  Afterwards, outside the timed
-regions, `--profile-repeats` more regions run with HIP events around every launch for the per-kernel split (`roofline`).
+Timing: W untimed warm-up iterations, then `--profile-repeats` regions of K iterations with HIP events around every launch for
+the per-kernel split (`roofline`), then EXACTLY K timed iterations, cut into `--repeats` (default 1) regions, every region
+bracketed by barrier + synchronize on both sides, MAX over ranks per region; `ms_per_step` is the MEDIAN region's milliseconds
+per iteration and `value` its rate, every region's rate is listed in `region_its`.  The per-solve fixed cost (entering / leaving
+the iteration format, reading the max-norm rows) is not an iteration and is reported separately (`per_solve`).
+
+`--dump-outputs DIR` writes what the timed solve returns after its last step (bench.dump_outputs) as DIR/<name>.npy; the inputs
+are analytic, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0), last on stdout.  `roofline` = the dominant kernel (pass B: Sobolev smoothing + psi update +
 warp + max-norm) incl. `traffic` (fabric bytes per launch from two live rocprofv3 PMC passes, N=1), `cpu_baseline` = the oracle's
@@ -347,17 +350,29 @@ class GpuState:
 GPU_STATE = None
 
 
-def timed_regions(ranks, torch, fn, repeats):
-    """`repeats` regions of one fn() each (fn enqueues exactly K iterations), barrier + synchronize on both sides of every
+def region_steps(K, R):
+    """the K timed steps cut into min(R, K) regions of near-equal size: the regions' sizes add up to exactly K"""
+    R = max(1, min(R, K))
+    return [K // R + (1 if i < K % R else 0) for i in range(R)]
+
+
+def median_step_s(secs, sizes):
+    """median over the regions of (region seconds / region steps): the seconds one timed step took"""
+    s = sorted(t / k for t, k in zip(secs, sizes))
+    return s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
+
+
+def timed_regions(ranks, torch, fn, sizes):
+    """one region per entry of `sizes` (fn(k) enqueues exactly k iterations), barrier + synchronize on both sides of every
     region; returns the per-region seconds after a MAX over ranks.  A rank's clock runs from its exit of the opening barrier to
     the moment its own GPU has drained; the closing barrier follows the stamp, so the region lasts until the SLOWEST rank is
     done (the MAX) without the host round trip of a barrier -- 0.1 ms and more on the nccl backend -- inside it."""
     secs = []
-    for _ in range(repeats):
+    for k in sizes:
         torch.cuda.synchronize()
         ranks.barrier()
         t0 = time.perf_counter()
-        fn()
+        fn(k)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         ranks.barrier()
@@ -365,6 +380,29 @@ def timed_regions(ranks, torch, fn, repeats):
         if GPU_STATE is not None:
             GPU_STATE.mark(t0, t1)
     return ranks.max(secs)
+
+
+DUMP_MAX_VOXELS = 1 << 20  # psi (4 floats) + phi_n o psi (2 floats) + the sample's indices (1 double) per voxel: 32 MB at most
+
+
+def dump_outputs(d, dims, psi, pnp, hist):
+    """--dump-outputs: what the timed solve hands its caller after its last step -- psi, phi_n o psi and the max-norm history --
+    as float32 .npy files.  Grids above DUMP_MAX_VOXELS cells are written as a fixed sample of cells (seed 0, the same for every
+    run of the same --dim), their linear indices z*Y*X + y*X + x in sample_voxels.npy (float64, exact)."""
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    N = dims[0] * dims[1] * dims[2]
+    if N <= DUMP_MAX_VOXELS:
+        out = {"psi": psi.cpu().numpy(), "phi_n_psi": pnp.cpu().numpy()}
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(N, DUMP_MAX_VOXELS, replace=False))
+        it = torch.from_numpy(idx).to(psi.device)
+        out = {"psi": psi.reshape(N, -1)[it].cpu().numpy(), "phi_n_psi": pnp.reshape(N, -1)[it].cpu().numpy(),
+               "sample_voxels": idx.astype(np.float64)}
+    out["max_update_norms"] = np.asarray(hist, np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def bench_single(args, P, ranks, torch):
@@ -379,15 +417,15 @@ def bench_single(args, P, ranks, torch):
     ops.init_sphere(pn, P["vs"], P["trunc"], P["eta"], c1, r)
     psi = ops.new_field(dims)
     ops.init_identity(psi)
-    K, W, R, PR = args.steps, args.warmup, args.repeats, args.profile_repeats
-    total = W + (R + PR) * K
+    K, W, PR = args.steps, args.warmup, args.profile_repeats
+    total = W + (PR + 1) * K
     sv = ops.Solver(dims, max_iter=max(total, 50), alpha=P["alpha"], w_reg=P["w_reg"], s=P["s"], lam=P["lam"],
                     max_update_norm=P["max_update_norm"])
     sv.begin(pg, pn, pnp, psi, total)  # the solve is open and its state resident before anything is timed
     sv.step(W)
-    secs = timed_regions(ranks, torch, lambda: sv.step(K), R)
     # per-kernel split: same loop, HIP events on the solver's stream around EVERY launch (events drain the pipeline between
-    # two kernels, so these regions are not the ones whose wall time is quoted)
+    # two kernels, so these regions are not the ones whose wall time is quoted).  They run before the timed regions, so that
+    # the timed steps are the last ones of the solve and end() returns what they computed.
     ms_a = ms_b = n_prof = 0
     if PR > 0:
         sv.set_profiling(1)
@@ -397,9 +435,13 @@ def bench_single(args, P, ranks, torch):
         torch.cuda.synchronize()
         ms_a, ms_b, n_prof = sv.get_profile()
         sv.set_profiling(0)
+    sizes = region_steps(K, args.repeats)
+    secs = timed_regions(ranks, torch, sv.step, sizes)
     rep, hist = sv.end()
     assert rep.iterations == total, (rep.iterations, total)
     assert np.isfinite(hist).all() and float(hist.max()) > 0
+    if args.dump_outputs and ranks.rank == 0:
+        dump_outputs(args.dump_outputs, dims, psi, pnp, hist)
     # per-solve fixed cost: whole iterate() calls (begin + K iterations + end, host-synchronised) against K timed iterations
     solve = []
     for _ in range(3):
@@ -407,7 +449,7 @@ def bench_single(args, P, ranks, torch):
         t0 = time.perf_counter()
         sv.iterate(pg, pn, pnp, psi, 50)
         solve.append(time.perf_counter() - t0)
-    res = dict(region_seconds=secs, N=N, ms_a=ms_a / max(n_prof, 1), ms_b=ms_b / max(n_prof, 1), n_prof=n_prof, last_norm=float(hist[-1]),
+    res = dict(region_seconds=secs, region_steps=sizes, N=N, ms_a=ms_a / max(n_prof, 1), ms_b=ms_b / max(n_prof, 1), n_prof=n_prof, last_norm=float(hist[-1]),
                workspace=sv.workspace_bytes(), solve50_s=float(np.median(solve)),
                parallelism="single" if ranks.world == 1 else f"{ranks.world} independent {dims[0]}^3 sequences, one per GPU (replicas, no exchange)")
     sv.close()
@@ -509,10 +551,10 @@ def make_line(args, P, res, world, force_tiled, full=True):
     """the JSON line from a result dict.  full=False: the EARLY copy of a tiled run (no live PMC passes, no CPU baseline)"""
     replicas = world > 1 and args.replicas
     K = args.steps
-    secs = sorted(res["region_seconds"])
-    med = secs[len(secs) // 2] if len(secs) % 2 else 0.5 * (secs[len(secs) // 2 - 1] + secs[len(secs) // 2])
+    secs, sizes = res["region_seconds"], res["region_steps"]
+    step_s = median_step_s(secs, sizes)
     mult = world if replicas else 1
-    its = mult * K / med
+    its = mult / step_s
     N = res["N"]
     ms_b, ms_a = res.get("ms_b"), res.get("ms_a")
 
@@ -535,14 +577,15 @@ def make_line(args, P, res, world, force_tiled, full=True):
     out = {
         "metric": f"solver iterations/sec on {args.dim}^3 voxel grid",
         "value": its, "unit": "iterations/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-        "ms_per_step": 1e3 * med / K, "higher_is_better": True,
+        "ms_per_step": 1e3 * step_s, "higher_is_better": True,
         "scaling": ("strong" if not replicas else "weak") if world > 1 else "single", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"{args.dim}^3 TSDF, params_boxing.ini solver values (alpha 0.001, w_reg 0.6, S=7, "
                                f"lambda 0.1, max_update_norm 1e-10), two analytic spheres 1.3 voxels apart; a step = one solver "
                                f"iteration of an open solve",
                    "grid": [args.dim] * 3, "parallelism": res["parallelism"]},
-        "repeats": len(secs), "timing": f"median of {len(secs)} regions of {K} iterations (barrier + synchronize around each, MAX over ranks)",
-        "region_its": [round(mult * K / s, 1) for s in res["region_seconds"]],
+        "repeats": len(secs), "timing": f"{K} timed iterations in {len(secs)} region(s) of {'/'.join(map(str, sizes))} (barrier + synchronize around "
+                                          "each, MAX over ranks); ms_per_step = the median region's time per iteration",
+        "region_its": [round(mult * k / s, 1) for s, k in zip(secs, sizes)],
         # whole-iteration view, per GPU: the 76 B/voxel the compact format must move per iteration against the HBM peak.
         # (SURVEY 8(d) prices an iteration at 112 algorithmic B/voxel; at that price the same run is
         # `iteration_algorithmic_GBps`, which can exceed the peak precisely because the format moves fewer bytes.)
@@ -585,14 +628,14 @@ def make_line(args, P, res, world, force_tiled, full=True):
             "pass_a": {"avg_launch_ms": ms_a, "algorithmic_bytes_per_launch": NL * B_PASS_A, "physical_bytes_per_launch": NL * C_PASS_A,
                        "traffic": traffic["a"]["bytes"] if traffic else None,
                        "physical_GBps": gbps(NL * C_PASS_A, ms_a), "frac_physical": gbps(NL * C_PASS_A, ms_a) / HBM_PEAK_GBPS},
-            "event_sum_vs_step": (ms_a + ms_b + (res.get("ms_exchange") or 0.0)) / (1e3 * med / K),
+            "event_sum_vs_step": (ms_a + ms_b + (res.get("ms_exchange") or 0.0)) / (1e3 * step_s),
         }
         if res.get("ms_exchange") is not None:  # N > 1, serial schedule: what an iteration is made of
             out["tiled_iteration_ms"] = {"pass_a_incl_message_stores" + ("_and_peer_wait" if res.get("transport") == "direct" else ""): ms_a,
                                          "exchange_transfer_and_scatter": res["ms_exchange"], "pass_b": ms_b}
     if res.get("solve50_s"):
         s50 = res["solve50_s"]
-        out["per_solve"] = {"iterations": 50, "ms": 1e3 * s50, "fixed_ms": 1e3 * s50 - 50 * 1e3 * med / K,
+        out["per_solve"] = {"iterations": 50, "ms": 1e3 * s50, "fixed_ms": 1e3 * s50 - 50 * 1e3 * step_s,
                             "iterations_per_s_incl_fixed": 50 / s50,
                             "note": "one whole sobfu_hip_solver_iterate call of 50 iterations (BASELINE config 3's frame): enter the "
                                     "compact format + 50 iterations + max-norm rows to the host + leave, host-synchronised"}
@@ -639,9 +682,13 @@ def make_line(args, P, res, world, force_tiled, full=True):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed iterations (in all, over the --repeats regions)")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=7, help="timed regions of --steps iterations each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="regions the --steps timed iterations are cut into (for their spread); the median is "
+                                                         "reported.  Each region pays one synchronisation: keep them long")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed solve computed (psi, phi_n o psi, max-norm history) as DIR/<name>.npy "
+                         "(single-grid runs: N = 1 or --replicas, rank 0's grid)")
     ap.add_argument("--profile-repeats", type=int, default=2, help="extra regions with HIP events around every launch (kernel split)")
     ap.add_argument("--dim", type=int, default=256, help="grid edge (256 = the BASELINE metric's grid)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -667,6 +714,12 @@ def main():
                          "`skipped` otherwise; a run still busy 25 s past its budget prints the core line it already holds and exits.  "
                          "Default: 300 s at N > 1 (a healthy 8-GPU run takes about two minutes), none at N = 1; 0 = none")
     args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1:
+        ap.error("--steps and --repeats must be at least 1")
+    if args.dump_outputs and args.gpus > 1 and not args.replicas:
+        ap.error("--dump-outputs covers the single-grid path (--gpus 1 or --replicas)")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     os.environ.setdefault("SOBFU_BENCH_T0", repr(time.time()))  # (inherited by the ranks of a self-launched run: one clock for all)
     if args.budget_s < 0:
         args.budget_s = 300.0 if (args.gpus > 1 and not args.replicas) else 0.0

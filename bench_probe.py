@@ -45,12 +45,12 @@ def main() -> int:
 
     a = json.loads(os.environ["SOBFU_PROBE_ARGS"])
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    if os.environ.get("SOBFU_PROBE_TEST_FAIL") == str(rank):  # tests: this rank's child dies abruptly, before it touches the GPU
+        os._exit(1)
     share = os.environ.get("SOBFU_BENCH_SHARE_GPU") == "1"
     torch.cuda.set_device(0 if share else int(os.environ.get("LOCAL_RANK", "0")))
     dist.init_process_group("gloo", init_method=f"tcp://{a['addr']}:{a['port']}", rank=rank, world_size=world,
                             timeout=datetime.timedelta(seconds=int(a.get("timeout", 90))))
-    if os.environ.get("SOBFU_PROBE_TEST_ABORT") == str(rank):  # tests: this rank's child dies the way a GPU fault would kill it
-        os.abort()
     vs = np.array(a["vs"], np.float32)
     P = dict(dims=tuple(a["dims"]), vs=vs, trunc=np.float32(a["trunc"]), eta=np.float32(a["eta"]))
     why = bench_tiled.direct_transport_precheck(P, _Ranks(torch, dist, rank, world), a["kw"], tuple(a["grid"]), iters=int(a.get("iters", 4)))

@@ -439,10 +439,13 @@ def frames_on_tiles(args, ranks, grid, transport, max_frames):
 def run_leg(args, P, ranks, timed_regions, grid, transport_name, kw):
     """One timed run of the tile loop on one transport + the bitwise self-check of the whole run.  Returns a dict; {"failed": reason}
     when the transport broke (collective: every rank returns the same kind)."""
+    import bench
+
     rank, world = ranks.rank, ranks.world
     dims = P["dims"]
-    K, W, R, PR = args.steps, args.warmup, args.repeats, args.profile_repeats
-    total = W + (R + PR) * K
+    K, W, PR = args.steps, args.warmup, args.profile_repeats
+    sizes = bench.region_steps(K, args.repeats)
+    total = W + (1 + PR) * K
     solver, keep, why = None, None, None
     try:
         solver, keep = make_native_solver(dims, grid, ranks, kw, transport_name)
@@ -469,7 +472,7 @@ def run_leg(args, P, ranks, timed_regions, grid, transport_name, kw):
         if transport_name == "direct":
             torch.cuda.synchronize()
             solver.wait_stats(reset=True)
-        secs = timed_regions(ranks, torch, lambda: solver.step(K), R)
+        secs = timed_regions(ranks, torch, solver.step, sizes)
         if transport_name == "direct":
             wait = solver.wait_stats(reset=True)
         if PR > 0:  # the split of an iteration (pass A incl. the message stores / transfer + scatter / pass B), outside the timed regions
@@ -506,9 +509,8 @@ def run_leg(args, P, ranks, timed_regions, grid, transport_name, kw):
             print(f"[rank {rank}] tiled self-check on {transport_name}: {what}", file=sys.stderr, flush=True)
         del psi_f, pnp_f
     own = tuple(L.g1[a] - L.g0[a] for a in range(3))
-    s = sorted(secs)
-    med = s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
-    leg = dict(transport=transport_name, value=K / med, ms_per_step=1e3 * med / K, region_seconds=secs, parity=parity,
+    step_s = bench.median_step_s(secs, sizes)
+    leg = dict(transport=transport_name, value=1.0 / step_s, ms_per_step=1e3 * step_s, region_seconds=secs, region_steps=sizes, parity=parity,
                ms_a=(prof[0] if prof else None), ms_exchange=(prof[1] if prof else None), ms_b=(prof[2] if prof else None),
                n_prof=(prof[3] if prof else None), last_norm=float(norms[-1]), owned=own, slab=L.slab, over_gloo=keep is not None,
                schedule=(f"{solver.SCHEDULES[solver.schedule]} (autotuned)" if tuned else None),
@@ -615,12 +617,12 @@ def bench_tiled(args, P, ranks, timed_regions):
             if "failed" in leg:
                 pub[name] = {"failed": leg["failed"]}
             else:
-                pub[name] = {k: v for k, v in leg.items() if not k.startswith("_") and k not in ("region_seconds", "owned", "slab")}
-                pub[name]["region_its"] = [round(args.steps / s, 1) for s in leg["region_seconds"]]
+                pub[name] = {k: v for k, v in leg.items() if not k.startswith("_") and k not in ("region_seconds", "region_steps", "owned", "slab")}
+                pub[name]["region_its"] = [round(k / s, 1) for s, k in zip(leg["region_seconds"], leg["region_steps"])]
                 pub[name]["tiled_parity_vs_single_gpu"] = "bit-exact" if leg["parity"] else ("MISMATCH" if leg["parity"] is False else None)
         layouts = [TileLayout(dims, grid, q) for q in range(world)]
         return dict(diag_hung=hung, diag_hung_any=hung_any, transport=best, transport_fallback=direct_why, legs=pub,
-                    region_seconds=main["region_seconds"], N=X * Y * Z, ms_a=main["ms_a"], ms_b=main["ms_b"], ms_exchange=main["ms_exchange"],
+                    region_seconds=main["region_seconds"], region_steps=main["region_steps"], N=X * Y * Z, ms_a=main["ms_a"], ms_b=main["ms_b"], ms_exchange=main["ms_exchange"],
                     n_prof=main["n_prof"], last_norm=main["last_norm"], workspace=None, tiled_parity=main["parity"],
                     launch_cells=max((l.g1[0] - l.g0[0]) * (l.g1[1] - l.g0[1]) * (l.g1[2] - l.g0[2]) for l in layouts),
                     tiled_diag={k: v for k, v in extras.items() if k in ("direct_diag", "rccl_diag", "iteration_us_compute_only", "error")} or None,

@@ -10,8 +10,31 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+MAX_PROCS_ON_ONE_GPU = 6  # processes that may hold one GPU open at the same time on a shared machine
+
+
+def ranks_env(args, env):
+    """env of a `--gpus n` run.  With fewer than n GPUs the ranks share cuda:0 (SOBFU_BENCH_SHARE_GPU=1); then this process, the n
+    ranks and -- on tiles -- the n sandboxed-probe children beside them (bench_probe.py) must stay within MAX_PROCS_ON_ONE_GPU: the
+    probe is left out when only it is too many (on one GPU the ranks' own bitwise precheck of the direct transport remains).  The
+    tests keep n <= 5 for that reason: 8 tiles (2 x 2 x 2) are covered in one process by tests/test_gpu_tiled_loopback.py."""
+    n = int(args[args.index("--gpus") + 1])
+    if n == 1 or env.get("SOBFU_BENCH_SHARE_GPU") != "1":
+        return env
+    import torch
+
+    e = dict(env)
+    if torch.cuda.device_count() >= n:
+        del e["SOBFU_BENCH_SHARE_GPU"]
+        return e
+    assert 1 + n <= MAX_PROCS_ON_ONE_GPU, f"{n} ranks on one GPU would be more than {MAX_PROCS_ON_ONE_GPU} processes with it open"
+    if "--replicas" not in args and 1 + 2 * n > MAX_PROCS_ON_ONE_GPU:
+        e["SOBFU_TILED_SANDBOX"] = "0"
+    return e
+
+
 def run_bench(*args, env=None):
-    e = dict(os.environ, **(env or {}))
+    e = dict(os.environ, **ranks_env(args, env or {}))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=900, env=e)
     assert r.returncode == 0, r.stderr[-12000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -48,6 +71,38 @@ def test_single_gpu_line():
         assert rb["value"] > 0 and rb["unit"] == "iterations/s" and rb["this_repo_over_reference_build"] > 2.0 and "shim evidence" in rb["kind"], rb
 
 
+def test_dump_outputs_are_what_the_timed_solve_returns(tmp_path):
+    """--steps sets the timed iterations in all; --dump-outputs writes what the solve returns after its last one: the same arrays,
+    bit for bit, as one untimed sobfu_hip_solver_iterate call of warm-up + profiled + timed iterations on the same inputs."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from sobfu_amd import ops
+
+    d = run_bench("--gpus", "1", "--steps", "7", "--warmup", "3", "--dim", "64", "--repeats", "3", "--profile-repeats", "1", "--no-cpu-baseline",
+                  "--no-traffic", "--frames", "0", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 7 and d["repeats"] == 3 and len(d["region_its"]) == 3 and d["ms_per_step"] > 0
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"psi", "phi_n_psi", "max_update_norms"} and all(a.dtype == np.float32 for a in got.values())
+    P = bench.boxing_params(64)
+    dims = P["dims"]
+    c0, c1, r = bench.sphere_pair(P)
+    pg, pn, pnp = ops.new_volume(dims), ops.new_volume(dims), ops.new_volume(dims)
+    ops.init_sphere(pg, P["vs"], P["trunc"], P["eta"], c0, r)
+    ops.init_sphere(pn, P["vs"], P["trunc"], P["eta"], c1, r)
+    psi = ops.new_field(dims)
+    ops.init_identity(psi)
+    sv = ops.Solver(dims, max_iter=50, alpha=P["alpha"], w_reg=P["w_reg"], s=P["s"], lam=P["lam"], max_update_norm=P["max_update_norm"])
+    rep, hist = sv.iterate(pg, pn, pnp, psi, 3 + 7 + 7)
+    torch.cuda.synchronize()
+    sv.close()
+    assert rep.iterations == 17
+    for name, want in (("psi", psi.cpu().numpy()), ("phi_n_psi", pnp.cpu().numpy()), ("max_update_norms", hist)):
+        assert np.array_equal(got[name].view(np.uint32), want.view(np.uint32)), name
+
+
 def test_gpus_n_self_launches_replicas():
     """plain `python bench.py --gpus 2` (no torchrun): bench.py re-executes itself under torch.distributed.run.  On this 1-GPU box
     both ranks share cuda:0 (gloo process group); --replicas = BASELINE config 5's batched independent sequences."""
@@ -78,10 +133,10 @@ def test_tile_path_line_on_one_gpu():
     assert d["tiled_diag"]["iteration_us_compute_only"] > 0 and d["tiles"]["grid"] == [1, 1, 1]
 
 
-@pytest.mark.parametrize("n,grid,transport", [(8, [2, 2, 2], "direct"), (8, [2, 2, 2], "rccl"), (4, [1, 2, 2], "direct"), (2, [1, 1, 2], "rccl")])
+@pytest.mark.parametrize("n,grid,transport", [(4, [1, 2, 2], "rccl"), (2, [1, 1, 2], "direct"), (4, [1, 2, 2], "direct"), (2, [1, 1, 2], "rccl")])
 def test_gpus_n_strong_scaling_self_launch(n, grid, transport):
-    """plain `python bench.py --gpus 8`: self-launch, the default tile grid (2 x 2 x 2 at N = 8), the native loop on every rank,
-    one REAL process per rank -- on this 1-GPU box the ranks share cuda:0.  direct: the ranks map each other's arrays with hipIpc
+    """plain `python bench.py --gpus 4`: self-launch, the default tile grid (1 x 2 x 2 at N = 4), the native loop on every rank,
+    one REAL process per rank -- on a 1-GPU box the ranks share cuda:0.  direct: the ranks map each other's arrays with hipIpc
     and the halo cells, arrival flags and max-norm rows travel as plain stores between the processes (in-kernel waits live);
     rccl: the packed messages travel over gloo instead of RCCL.  Every rank checks its tile against the single-GPU solve bit for
     bit; the line names the transport."""
@@ -113,22 +168,23 @@ def test_gpus_n_explicit_tiles_and_threshold():
 
 
 def test_direct_transport_probe_child_dies_falls_back():
-    """the direct transport is first exercised in a CHILD of every rank (bench_probe.py): one child dying the way a GPU
-    memory fault would kill it must cost the run nothing but the transport -- every rank agrees on RCCL and the line says why"""
+    """the direct transport is first exercised in a CHILD of every rank (bench_probe.py): one child dying (as abruptly as a GPU
+    memory fault would end it; the test hook exits before the child touches the GPU) must cost the run nothing but the transport
+    -- every rank agrees on RCCL and the line says why"""
     d = run_bench("--gpus", "2", "--steps", "4", "--warmup", "1", "--dim", "64", "--repeats", "2",
-                  env={"SOBFU_BENCH_SHARE_GPU": "1", "SOBFU_TILED_DIAG": "0", "SOBFU_PROBE_TEST_ABORT": "1", "SOBFU_PROBE_TIMEOUT_S": "20"})
+                  env={"SOBFU_BENCH_SHARE_GPU": "1", "SOBFU_TILED_DIAG": "0", "SOBFU_PROBE_TEST_FAIL": "1", "SOBFU_PROBE_TIMEOUT_S": "20"})
     assert d["transport"] == "rccl" and "sandboxed probe" in d["transport_fallback"], d
     assert d["tiled_parity_vs_single_gpu"] == "bit-exact" and "sandboxed probe" in d["legs"]["direct"]["failed"] and d["legs"]["rccl"]["value"] > 0
 
 
-def test_gpus_8_harvests_everything():
-    """ONE `python bench.py --gpus 8` records everything the machine can tell: both transports timed on
-    BASELINE config 4's grid with `value` = the better bit-exact one, every grid of 8 tiles on both transports, the direct
+def test_gpus_4_harvests_everything():
+    """ONE `python bench.py --gpus 4` records everything the machine can tell: both transports timed on
+    the default grid (1 x 2 x 2) with `value` = the better bit-exact one, every grid of 4 tiles on both transports, the direct
     transport's flag round trips / push-box rate / unhidden wait, one exchange and one all-reduce of the RCCL leg, a topology
-    snapshot, frames/s of the whole pipeline ON TILES.  Eight real processes sharing this box's GPU (RCCL leg over gloo)."""
-    d = run_bench("--gpus", "8", "--steps", "6", "--warmup", "2", "--dim", "64", "--repeats", "2", "--frame-iters", "8",
+    snapshot, frames/s of the whole pipeline ON TILES.  Four real processes sharing a 1-GPU box's GPU (RCCL leg over gloo)."""
+    d = run_bench("--gpus", "4", "--steps", "6", "--warmup", "2", "--dim", "64", "--repeats", "2", "--frame-iters", "8",
                   env={"SOBFU_BENCH_SHARE_GPU": "1"})
-    assert d["n_gpus"] == 8 and d["tiles"]["grid"] == [2, 2, 2] and d["tiled_parity_vs_single_gpu"] == "bit-exact"
+    assert d["n_gpus"] == 4 and d["tiles"]["grid"] == [1, 2, 2] and d["tiled_parity_vs_single_gpu"] == "bit-exact"
     legs = d["legs"]
     assert set(legs) == {"direct", "rccl"} and d["transport"] in legs
     for name, leg in legs.items():
@@ -136,21 +192,23 @@ def test_gpus_8_harvests_everything():
         assert leg["ms_a"] > 0 and leg["ms_b"] > 0
     assert d["value"] == max(leg["value"] for leg in legs.values()) and abs(d["value"] - legs[d["transport"]]["value"]) < 1e-9
     assert legs["direct"]["peer_wait_us_per_iteration"] >= 0 and legs["rccl"]["ms_exchange"] > 0
-    bg = d["best_grid"]  # the fastest (grid, transport) of the run is a first-class number beside `value`, which stays on config 4's grid
-    assert bg["value"] >= d["value"] - 1e-9 and bg["transport"] in legs and "x".join(map(str, bg["grid"])) in {"1x1x8", "1x2x4", "2x2x2"} and bg["candidates"] == 6
+    bg = d["best_grid"]  # the fastest (grid, transport) of the run is a first-class number beside `value`, which stays on the default grid
+    # candidates: the two timed legs + the other grid of 4 tiles on both transports
+    assert bg["value"] >= d["value"] - 1e-9 and bg["transport"] in legs and "x".join(map(str, bg["grid"])) in {"1x1x4", "1x2x2"} and bg["candidates"] == 4
     grids = d["tiled_autotune_us"]
-    assert set(grids) == {"direct", "rccl"} and all(set(g) == {"1x1x8", "1x2x4", "2x2x2"} and all(v and v > 0 for v in g.values()) for g in grids.values())
+    assert set(grids) == {"direct", "rccl"} and all(set(g) == {"1x1x4", "1x2x2"} and all(v and v > 0 for v in g.values()) for g in grids.values())
     dd = d["tiled_diag"]["direct_diag"]
-    assert len(dd["flag_round_trip_us"]) == 28 and all(v > 0 for v in dd["flag_round_trip_us"].values())
-    # (eight processes time-sharing ONE GPU make every handshake milliseconds long: only presence and sign are checked here)
+    assert len(dd["flag_round_trip_us"]) == 6 and all(v > 0 for v in dd["flag_round_trip_us"].values())  # every pair of 4 ranks
+    # (processes time-sharing ONE GPU make every handshake milliseconds long: only presence and sign are checked here)
     assert dd["push_boxes_only_us"] > 0 and dd["push_boxes_only_local_stores_us"] > 0 and dd["push_rate_GBps_of_bytes_out"] >= 0 and dd["status_ok"]
-    assert dd["messages"] == 6 and dd["bytes_out_per_iteration"] == 12 * (3 * 4 * 32 * 32 + 3 * 4 * 4 * 32)
+    # rank 0 of 1 x 2 x 2 tiles of 64 x 32 x 32 cells: face neighbours along y and z, edge neighbour yz; 4-cell halos, 12-byte cells
+    assert dd["messages"] == 3 and dd["bytes_out_per_iteration"] == 12 * (2 * 4 * 64 * 32 + 4 * 4 * 64)
     rd = d["tiled_diag"]["rccl_diag"]
     assert rd["exchange_4_cells_us"] > 0 and d["tiled_diag"]["iteration_us_compute_only"] > 0
     topo = d["topology"]
     assert topo["devices_visible"] >= 1 and "pairs" in topo
     f = d["per_frame"]
-    assert f["frames_timed"] == 3 and f["iterations_per_frame"][-1] == 8 and f["frames_per_s"] > 0 and f["tiles"] == "2x2x2"
+    assert f["frames_timed"] == 3 and f["iterations_per_frame"][-1] == 8 and f["frames_per_s"] > 0 and f["tiles"] == "1x2x2"
     # the per-frame tail moves bounded-reach windows, not two all-gathers, and says so; checked against the
     # all-gather tail bit for bit inside the run
     t = f["tail"]

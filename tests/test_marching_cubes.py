@@ -30,14 +30,13 @@ def test_case_table_is_a_valid_marching_cubes_table(oracle):
         assert set(row[:n]) == cut  # the triangles of a case use exactly the edges the surface cuts
         assert all(len(set(row[t:t + 3])) == 3 for t in range(0, n, 3))
     assert table[0] == [15] * 16 and table[255] == [15] * 16 and table[1][:3] == [0, 8, 3]
-    if os.path.exists("/root/reference/src/kfusion/marching_cubes.cpp"):  # dev container only: same constants as the reference
-        import sys
+    # same constants as the reference: its triTable through the hash stored in tests/golden/reference_tables.json
+    import hashlib
+    import json
 
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import pack_mc_table
-
-        ref = pack_mc_table.parse("/root/reference/src/kfusion/marching_cubes.cpp")
-        assert [[15 if v < 0 else v for v in r] for r in ref] == table
+    with open(os.path.join(ROOT, "tests", "golden", "reference_tables.json")) as f:
+        ref_sha = json.load(f)["triTable_sha256"]
+    assert hashlib.sha256(",".join(str(-1 if v == 15 else v) for row in table for v in row).encode()).hexdigest() == ref_sha
 
 
 def sphere_volume(oracle, n=32, centre=(0.25, 0.26, 0.24), r=0.1):
