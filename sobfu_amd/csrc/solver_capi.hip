@@ -344,11 +344,13 @@ int run_verbose(sobfu_hip_solver* s, const float* pg, const float* pn, float* pn
                 sobfu_hip_solver_report* rep, float* per_iter, hipStream_t st) {
     const int X = s->X, Y = s->Y, Z = s->Z;
     const sobfu_hip_solver_params& p = s->p;
-    auto reports = [&](int it) { return p.verbosity == 2 || it == 1 || it % 50 == 0 || it == max_iter; };
+    // solver.cu:132-133,173-174: verbosity 3 and above report nothing (only the `iter. no.` and closing lines)
+    auto reports = [&](int it) { return p.verbosity == 2 || (p.verbosity == 1 && (it == 1 || it % 50 == 0 || it == max_iter)); };
     SOBFU_TRY(ensure_updates(s));
     SOBFU_TRY(session_begin(s, pg, pn, pnp, psi, max_iter, st));
     sobfu_hip_solver::Session& q = s->q;
-    q.inline_log = true;
+    q.upd = s->updates;  // the quiet runs store `updates` too: a break inside one leaves that iteration's (reductor.cpp:26)
+    q.inline_log = p.verbosity <= 2;  // without reporting iterations session_end prints the `iter. no.` lines
     float e_data = NAN, e_reg = NAN, arg = NAN;
     auto fail = [&](int rc) {
         q.active = false;

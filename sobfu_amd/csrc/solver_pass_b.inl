@@ -111,7 +111,9 @@ SOBFU_DEV float pass_b_direct_cell(const PassBArgs& a, int x, int y, int z) {
     if (COMPACT) ((float*) a.pnp)[i] = IDX32 ? interp_tsdf_only32((const float*) a.phi_n, a.pd, p.x, p.y, p.z) : interp_tsdf_only((const float*) a.phi_n, a.pd, p.x, p.y, p.z);
     else ((float2*) a.pnp)[i] = interp_tsdf((const float2*) a.phi_n, a.pd, p.x, p.y, p.z);
     const bool owned = x >= a.own[0] && x < a.own[1] && y >= a.own[2] && y < a.own[3] && z >= a.own[4] && z < a.own[5];
-    return owned ? norm_sq4(uu) : 0.f;
+    // fmaxf(0, .) like the marching paths: a NaN norm never wins the max (reductor.cu's strict '>' from 0); its bit pattern would
+    // beat every finite one in maxnorm_tail's unsigned atomicMax
+    return owned ? fmaxf(0.f, norm_sq4(uu)) : 0.f;
 }
 
 // The SOFTWARE-PIPELINED march of pass B (compact solver format, one row per lane).  In the plain march a plane's dependent
