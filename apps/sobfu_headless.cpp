@@ -4,9 +4,14 @@
 // binary 16-bit PGM or raw little-endian uint16 files of rows*cols pixels (sobfu_amd/depth_io.hpp), or a built-in
 // synthetic translating sphere.  --dump DIR writes psi, psi_inv and the four TSDF volumes as .npy (float32); --mesh DIR
 // writes marching-cubes meshes of the volumes per frame as legacy-ASCII .vtk polydata (the reference: demo.cpp:236-246).
+// --screenshots DIR writes DIR/%06d.png per frame (the reference's --enable-viz, demo.cpp:380-505): raycast + shaded views of the
+// canonical model phi_global (left) and of the canonical model warped to live, phi_global_psi_inv (right; black until a frame has been
+// solved); --screenshots-detailed adds a second row -- phi_n, phi_global_psi_inv / phi_global, phi_n_psi (demo.cpp:445-456).  The
+// views are drawn from the depth camera (the pose and intrinsics the frames are integrated with) with a headlight at its origin, not
+// from the reference viewer's camera at z = max + 3 (demo.cpp:403,467): with the depth camera the live panel lines up with the input.
 //
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR] [--no-stats]
-//                  (--synthetic FRAMES [--shift DX] | frame0.pgm frame1.pgm ...)
+//                  [--screenshots DIR [--screenshots-detailed]] (--synthetic FRAMES [--shift DX] | frame0.pgm frame1.pgm ...)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -38,9 +43,59 @@ static void stats(const char* name, kfusion::cuda::TsdfVolume& v) {
     std::printf("%s: sum_tsdf=%.4f sum_weight=%.0f non_truncated_observed=%ld\n", name, st, sw, nt);
 }
 
+// Screenshot compositor: one device image of 2 x 1 (or 2 x 2) panels of rows x cols, each view raycast into the same point / normal
+// buffers and shaded straight into its panel (pitched output); every buffer is allocated once, on the first frame.
+struct Screenshots {
+    std::string dir;
+    bool detailed = false;
+    int rows = 0, cols = 0;
+    kfusion::cuda::Cloud points;
+    kfusion::cuda::Normals normals;
+    kfusion::cuda::Image image;  // (2 or 1 panel rows) x 2 panels
+    std::vector<kfusion::RGB> bgra;
+    std::vector<uint8_t> rgb;
+
+    void create(int rows_, int cols_) {
+        rows = rows_, cols = cols_;
+        points.create(rows, cols);
+        normals.create(rows, cols);
+        image.create((detailed ? 2 : 1) * rows, 2 * cols);
+        bgra.resize((size_t) image.rows() * image.cols());
+        rgb.resize(bgra.size() * 3);
+    }
+    // shades `v` (or leaves the panel black when v is null) into panel (pr, pc)
+    void panel(kfusion::cuda::TsdfVolume* v, const kfusion::Intr& intr, int pr, int pc) {
+        if (!v) return;
+        v->raycast(cv::Affine3f::Identity(), intr, points, normals);  // the depth camera (SobFusion's camera_pose_)
+        uint8_t* dst = (uint8_t*) image.ptr() + (size_t) pr * rows * image.step() + (size_t) pc * cols * sizeof(kfusion::RGB);
+        sobfuSafeCall(sobfu_hip_render_image((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
+                                             rows, cols, 0.f, 0.f, 0.f, dst, (int) image.step(), nullptr));  // headlight at the camera
+    }
+    bool write(int frame, SobFusion& fusion, bool solved, const kfusion::Intr& intr) {
+        if (points.empty()) create(fusion.getParams().rows, fusion.getParams().cols);
+        sobfuSafeCall(hipMemset2D(image.ptr(), image.step(), 0, (size_t) image.cols() * sizeof(kfusion::RGB), image.rows()));
+        panel(fusion.phi_global.get(), intr, detailed ? 1 : 0, 0);
+        panel(solved ? fusion.phi_global_psi_inv.get() : nullptr, intr, 0, 1);
+        if (detailed) {
+            panel(frame > 0 ? fusion.phi_n.get() : nullptr, intr, 0, 0);
+            panel(solved ? fusion.phi_n_psi.get() : nullptr, intr, 1, 1);
+        }
+        image.download(bgra.data(), (size_t) image.cols() * sizeof(kfusion::RGB));
+        for (size_t i = 0; i < bgra.size(); ++i) {
+            rgb[3 * i] = bgra[i].r;
+            rgb[3 * i + 1] = bgra[i].g;
+            rgb[3 * i + 2] = bgra[i].b;
+        }
+        char name[32];
+        std::snprintf(name, sizeof name, "/%06d.png", frame);  // demo.cpp:409-414
+        return sobfu_amd::write_png_rgb(dir + name, image.rows(), image.cols(), rgb.data());
+    }
+};
+
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR] (--synthetic FRAMES [--shift DX] | depth files...)\n", argv[0]);
+        std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR] [--no-stats] "
+                    "[--screenshots DIR [--screenshots-detailed]] (--synthetic FRAMES [--shift DX] | depth files...)\n", argv[0]);
         return 2;
     }
     Params p;
@@ -52,6 +107,7 @@ int main(int argc, char** argv) {
     int synthetic = 0;
     double shift = 0.005;
     std::string dump, mesh_dir;
+    Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
     std::vector<std::string> files;
     for (int i = 2; i < argc; ++i) {
@@ -65,6 +121,8 @@ int main(int argc, char** argv) {
         else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
         else if (a == "--mesh" && i + 1 < argc) mesh_dir = argv[++i];
         else if (a == "--no-stats") print_stats = false;
+        else if (a == "--screenshots" && i + 1 < argc) shots.dir = argv[++i];
+        else if (a == "--screenshots-detailed") shots.detailed = true;
         else files.push_back(a);
     }
     if (argc > 2) {  // --dims changes the voxel size: re-derive the voxel-unit parameters
@@ -110,6 +168,11 @@ int main(int argc, char** argv) {
                 save_mesh("phi_n_psi", fusion.get_phi_n_psi_mesh());
                 save_mesh("phi_global_psi_inv", fusion.get_phi_global_psi_inv_mesh());
             }
+        }
+        if (!shots.dir.empty()) {
+            const bool solved = n > 0 && n >= p.start_frame;
+            if (shots.write(n, fusion, solved, p.intr)) std::printf("screenshot %s/%06d.png\n", shots.dir.c_str(), n);
+            else std::printf("cannot write screenshot %s/%06d.png\n", shots.dir.c_str(), n);
         }
         if (n > 0 && print_stats) {
             stats("phi_n", *fusion.phi_n);

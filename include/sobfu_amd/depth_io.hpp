@@ -4,6 +4,7 @@
 //   read_depth     16-bit grayscale PNG (zlib inflate + the five PNG row filters; non-interlaced), binary PGM "P5" with
 //                  maxval > 255 (big-endian samples), or raw little-endian uint16 of rows*cols pixels -- sniffed by magic
 //   write_npy      NumPy .npy v1.0, little-endian float32, C order
+//   write_png_rgb  8-bit RGB PNG (colour type 2, filter 0 on every row, zlib-compressed): the headless app's screenshots
 // Link with -lz.
 #pragma once
 #include <zlib.h>
@@ -145,6 +146,42 @@ inline bool write_npy(const std::string& path, const float* data, const std::vec
     const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char) (dict.size() & 255), (unsigned char) (dict.size() >> 8)};
     bool ok = std::fwrite(head, 1, 10, f) == 10 && std::fwrite(dict.data(), 1, dict.size(), f) == dict.size() &&
               std::fwrite(data, sizeof(float), n, f) == n;
+    return std::fclose(f) == 0 && ok;
+}
+
+// rows x cols pixels of 3 bytes (R, G, B), row-major without padding -> `path`.  Returns false if the file cannot be written.
+inline bool write_png_rgb(const std::string& path, int rows, int cols, const uint8_t* rgb) {
+    if (rows < 1 || cols < 1 || !rgb) return false;
+    const size_t stride = (size_t) cols * 3;
+    std::vector<unsigned char> raw((stride + 1) * (size_t) rows);
+    for (int y = 0; y < rows; ++y) {
+        raw[(stride + 1) * y] = 0;  // filter type 0 (None)
+        std::memcpy(&raw[(stride + 1) * y + 1], rgb + stride * y, stride);
+    }
+    uLongf zlen = compressBound((uLong) raw.size());
+    std::vector<unsigned char> z(zlen);
+    if (compress2(z.data(), &zlen, raw.data(), (uLong) raw.size(), 6) != Z_OK) return false;
+    z.resize(zlen);
+    std::vector<unsigned char> out = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    auto put32 = [&](uint32_t v) { for (int k = 3; k >= 0; --k) out.push_back((unsigned char) (v >> (8 * k))); };
+    auto chunk = [&](const char* type, const unsigned char* body, size_t len) {
+        put32((uint32_t) len);
+        const size_t at = out.size();
+        out.insert(out.end(), type, type + 4);
+        out.insert(out.end(), body, body + len);
+        put32((uint32_t) crc32(crc32(0L, Z_NULL, 0), &out[at], (uInt) (len + 4)));
+    };
+    unsigned char ihdr[13] = {0, 0, 0, 0, 0, 0, 0, 0, 8, 2, 0, 0, 0};  // depth 8, colour type 2 (RGB), deflate, filter method 0, no interlace
+    for (int k = 0; k < 4; ++k) {
+        ihdr[k]     = (unsigned char) ((uint32_t) cols >> (24 - 8 * k));
+        ihdr[4 + k] = (unsigned char) ((uint32_t) rows >> (24 - 8 * k));
+    }
+    chunk("IHDR", ihdr, 13);
+    chunk("IDAT", z.data(), z.size());
+    chunk("IEND", nullptr, 0);
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
     return std::fclose(f) == 0 && ok;
 }
 

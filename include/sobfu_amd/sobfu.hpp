@@ -10,6 +10,8 @@
 //   kfusion::cuda::TsdfVolume                include/kfusion/cuda/tsdf_volume.hpp:17-92
 //   kfusion::cuda::{depthBilateralFilter, depthTruncation, computeDists, waitAllDefaultStream}
 //                                            include/kfusion/cuda/imgproc.hpp:11-28
+//   kfusion::{RGB}, kfusion::cuda::{Cloud, Normals, Image, renderImage(Cloud, ...), renderTangentColors}, TsdfVolume::raycast
+//                                            include/kfusion/types.hpp:57-77, imgproc.hpp:30,42-46 (declared there, defined here only)
 //   kfusion::device::{TsdfVolume POD, clear_volume, integrate x2, init_*}  include/kfusion/internal.hpp:59-78,189-198
 //   sobfu::device::{VectorField & typedefs, Jacobian, clear, init_identity, apply, estimate_inverse,
 //                   TsdfDifferentiator, SecondOrderDifferentiator, Differentiator, Reductor, launchers}
@@ -345,6 +347,40 @@ struct Surface {  // include/kfusion/types.hpp:85-88
     DeviceArray<Point> vertices;
     DeviceArray<Normal> normals;
 };
+}  // namespace cuda
+
+// 8-bit BGRA pixel of the rendered images (include/kfusion/types.hpp:57-64): b, g, r and, in the fourth byte, alpha
+struct RGB {
+    union {
+        struct {
+            unsigned char b, g, r;
+        };
+        int bgra;
+    };
+};
+
+namespace cuda {
+// rendered views (include/kfusion/types.hpp:74-77): camera-frame points / normals (w = hit flag) and BGRA images
+typedef DeviceArray2D<Point> Cloud;
+typedef DeviceArray2D<Normal> Normals;
+typedef DeviceArray2D<RGB> Image;
+
+// ---- rendering (include/kfusion/cuda/imgproc.hpp:30,42-46: declared, never defined in the reference) ----------------------------
+// Asynchronous on the null stream like the launchers (the reference has no sync point to reproduce); a download synchronises.
+// renderImage: grey = 0.2 + 0.8 max(0, n . normalize(light_pose - p)), light_pose in the camera frame; misses stay black.  `intr` is
+// unused -- the reference's signature (the points are already in the camera frame).
+inline void renderImage(const Cloud& points, const Normals& normals, const Intr& /*intr*/, const Vec3f& light_pose, Image& image) {
+    image.create(normals.rows(), normals.cols());
+    sobfuSafeCall(sobfu_hip_render_image((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
+                                         normals.rows(), normals.cols(), light_pose[0], light_pose[1], light_pose[2], (uint8_t*) image.ptr(),
+                                         (int) image.step(), nullptr));
+}
+// renderTangentColors: (r, g, b) = (n * 0.5 + 0.5) * 255
+inline void renderTangentColors(const Normals& normals, Image& image) {
+    image.create(normals.rows(), normals.cols());
+    sobfuSafeCall(sobfu_hip_render_normals((const float*) normals.ptr(), (int) normals.step(), normals.rows(), normals.cols(), (uint8_t*) image.ptr(),
+                                           (int) image.step(), nullptr));
+}
 
 // ---- image pre-steps (include/kfusion/cuda/imgproc.hpp:11-28, src/kfusion/imgproc.cpp:3-41) ---------------------
 inline void depthBilateralFilter(const Depth& in, Depth& out, int kernel_size, float sigma_spatial, float sigma_depth) {
@@ -476,6 +512,17 @@ public:
         Affine3f vol2cam = camera_pose.inv() * pose_;  // src/kfusion/tsdf_volume.cpp:96
         device::TsdfVolume v = pod();
         device::integrate(dists, v, device_cast<device::Aff3f>(vol2cam), device::Projector(intr.fx, intr.fy, intr.cx, intr.cy));
+    }
+    // KinFu's raycast (kinfu.hpp's raycast_step_factor, 0.75 voxel when unset): points / normals of the view from camera_pose with
+    // intr, at the size `points` was created with (normals follow it).  Asynchronous on the null stream, like renderImage.
+    virtual void raycast(const Affine3f& camera_pose, const Intr& intr, Cloud& points, Normals& normals) {
+        const Affine3f vol2cam = camera_pose.inv() * pose_;  // as integrate
+        const Vec3f vs = getVoxelSize();
+        normals.create(points.rows(), points.cols());
+        sobfuSafeCall(sobfu_hip_raycast(data_.ptr<float>(), dims_[0], dims_[1], dims_[2], vs[0], vs[1], vs[2], trunc_dist_, vol2cam.R, vol2cam.t,
+                                        intr.fx, intr.fy, intr.cx, intr.cy, points.rows(), points.cols(),
+                                        raycast_step_factor_ > 0.f ? raycast_step_factor_ : 0.75f, (float*) points.ptr(), (int) points.step(),
+                                        (float*) normals.ptr(), (int) normals.step(), nullptr));
     }
     virtual void initBox(const float3& b) { device::TsdfVolume v = pod(); device::init_box(v, b); }
     virtual void initEllipsoid(const float3& r) { device::TsdfVolume v = pod(); device::init_ellipsoid(v, r); }

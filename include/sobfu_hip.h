@@ -300,6 +300,26 @@ int sobfu_hip_mc_generate_triangles(void* stream, const float* d_vol, int X, int
                                     float* d_normals, int max_vertices);
 
 /* ------------------------------------------------------------------------------------------------------
+ * rendering -- kfusion::cuda::renderImage / renderTangentColors (include/kfusion/cuda/imgproc.hpp:30,42-46: declared, never
+ * defined in the reference) and the KinectFusion raycaster the reference's TsdfVolume keeps a step factor for (tsdf_volume.hpp:91)
+ * but does not have.  Points / normals: pitched float4 images (step in bytes, 16-byte aligned); images: pitched 8-bit BGRA
+ * (kfusion::RGB, types.hpp:57-63, 4-byte aligned).  The rules are in sobfu_amd/csrc/render_kernels.hip.
+ * ---------------------------------------------------------------------------------------------------- */
+/* raycast: pixel (u, v) casts ((u - cx) / fx, (v - cy) / fy, 1) from the camera of vol2cam = (R row-major, t) -- the pose argument of
+ * sobfu_hip_integrate_depth -- through the trilinear TSDF; a hit is the first front-face zero crossing between two samples whose 8
+ * corner weights are all > 0.  Hit: point (x, y, z, 0) in the camera frame, normal (nx, ny, nz, 1); miss: both all zero.
+ * step_factor: the fine step in units of the smallest voxel size (KinFu: 0.75); trunc: the truncation distance in metres. */
+int sobfu_hip_raycast(const float* d_vol, int X, int Y, int Z, float vsx, float vsy, float vsz, float trunc, const float R[9],
+                      const float t[3], float fx, float fy, float cx, float cy, int rows, int cols, float step_factor, float* d_points,
+                      int points_step, float* d_normals, int normals_step, void* stream);
+/* renderImage: grey = 0.2 + 0.8 max(0, n . normalize(light - point)), light in the camera frame; misses are (0, 0, 0, 0). */
+int sobfu_hip_render_image(const float* d_points, int points_step, const float* d_normals, int normals_step, int rows, int cols,
+                           float lx, float ly, float lz, uint8_t* d_image, int image_step, void* stream);
+/* renderTangentColors: (r, g, b) = (n * 0.5 + 0.5) * 255; misses are (0, 0, 0, 0). */
+int sobfu_hip_render_normals(const float* d_normals, int normals_step, int rows, int cols, uint8_t* d_image, int image_step,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * native multi-GPU loop: one rank per z-slab, RCCL halo exchange issued from C++ and overlapped with the interior
  * compute (no reference counterpart; schedule documented in sobfu_amd/tiled.py)
  * ---------------------------------------------------------------------------------------------------- */

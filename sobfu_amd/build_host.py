@@ -45,9 +45,23 @@ def build_io_tool(force: bool = False) -> str:
     return IO_TOOL
 
 
+PNG_TOOL = os.path.join(ROOT, "build", "png_write_tool")
+
+
+def build_png_tool(force: bool = False) -> str:
+    """tests/cpp/png_write_tool.cpp: CPU-only driver of the PNG writer (needs zlib only)."""
+    src = os.path.join(ROOT, "tests", "cpp", "png_write_tool.cpp")
+    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp")]
+    if force or not os.path.exists(PNG_TOOL) or any(os.path.getmtime(PNG_TOOL) < os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(PNG_TOOL), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", f"-I{os.path.join(ROOT, 'include')}", src, "-o", PNG_TOOL, "-lz"])
+    return PNG_TOOL
+
+
 def build_host(force: bool = False) -> str:
     build_app(force)
     build_io_tool(force)
+    build_png_tool(force)
     src = os.path.join(ROOT, "tests", "cpp", "host_shell_tests.cpp")
     deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
             os.path.join(HERE, "libsobfu_hip.so")]

@@ -17,9 +17,11 @@ class SobFusion:
         self.frame = 0
         self.phi_global = self.phi_global_psi_inv = self.phi_n = self.phi_n_psi = self.psi = self.psi_inv = self.solver = None
         self.last_report = None
+        self.image_shape = None  # (rows, cols) of the depth frames: the camera render() draws with
 
     def __call__(self, depth_u16):
         ops, P = self.ops, self.P
+        self.image_shape = tuple(depth_u16.shape)
         dims, vs = P["dims"], tuple(float(v) for v in P["vs"])
         ks, ss, sd = P["bilateral"]
         d = ops.bilateral_filter(depth_u16, ks, ss, sd)                                       # sob_fusion.cpp:78
@@ -46,6 +48,18 @@ class SobFusion:
             ops.integrate_fuse(self.phi_global, self.phi_n_psi, P["max_weight"])              # :142
         self.frame += 1
         return self.last_report
+
+    def render(self, which="phi_global", light=(0.0, 0.0, 0.0)):
+        """Raycast + shade one of the volumes ("phi_global", "phi_global_psi_inv", "phi_n", "phi_n_psi") from the sequence's own depth
+        camera (the pose and intrinsics its frames are integrated with) -> (rows, cols, 4) uint8 BGRA image; light in the camera frame."""
+        if which not in ("phi_global", "phi_global_psi_inv", "phi_n", "phi_n_psi"):
+            raise ValueError(f"unknown volume {which!r}")
+        vol = getattr(self, which)
+        if vol is None:
+            raise RuntimeError(f"{which} does not exist before the first frame")
+        P, (rows, cols) = self.P, self.image_shape
+        pts, nrm = self.ops.raycast(vol, P["vs"], P["trunc"], P["R"], P["t"], P["intr"], rows=rows, cols=cols)
+        return self.ops.render_image(pts, nrm, light)
 
     def close(self):
         if self.solver is not None:

@@ -422,3 +422,48 @@ def marching_cubes(vol, volume_size, R=np.eye(3), t=(0, 0, 0), max_voxels=2_000_
     n = torch.zeros_like(v)
     mc_generate_triangles(vol, occ, count, volume_size, R, t, v, n)
     return v[:total], n[:total]
+
+
+# ---- rendering (kfusion::cuda::renderImage / renderTangentColors; KinectFusion raycaster) ---------------------------------------
+def _image_ptr(t, dtype, channels):
+    if not (t.is_cuda and t.dtype == dtype and t.dim() == 3 and t.shape[2] == channels and t.stride(2) == 1 and t.stride(1) == channels):
+        raise ValueError(f"expected a (rows, cols, {channels}) {dtype} image on the GPU with contiguous rows, got {t.dtype} {tuple(t.shape)}")
+    return C.c_void_p(t.data_ptr()), C.c_int(t.stride(0) * t.element_size())
+
+
+def raycast(vol, voxel_size, trunc, R, t, intr, rows=480, cols=640, step_factor=0.75, points=None, normals=None):
+    """Raycasts a TSDF volume (Z, Y, X, 2) from the camera of vol2cam = (R, t) (the pose integrate_depth takes) with intrinsics
+    intr = (fx, fy, cx, cy) -> (points, normals), two (rows, cols, 4) float32 tensors in the camera frame; normals[..., 3] is 1 on a
+    hit and 0 on a miss (where both are all zero).  `points` / `normals` may be given to render into existing buffers."""
+    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
+    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    if points is None:
+        points = torch.empty((rows, cols, 4), dtype=torch.float32, device=vol.device)
+    if normals is None:
+        normals = torch.empty((rows, cols, 4), dtype=torch.float32, device=vol.device)
+    vs = [float(np.float32(v)) for v in voxel_size]
+    check(_lib.lib().sobfu_hip_raycast(_ptr(vol), *_xyz(vol), _f(vs[0]), _f(vs[1]), _f(vs[2]), _f(trunc), Rm, tv, _f(intr[0]), _f(intr[1]),
+                                       _f(intr[2]), _f(intr[3]), C.c_int(int(rows)), C.c_int(int(cols)), _f(step_factor),
+                                       *_image_ptr(points, torch.float32, 4), *_image_ptr(normals, torch.float32, 4), _stream()), "raycast")
+    return points, normals
+
+
+def render_image(points, normals, light=(0.0, 0.0, 0.0), image=None):
+    """renderImage: Lambertian grey from a light at `light` (camera frame) -> (rows, cols, 4) uint8 BGRA; misses are all zero."""
+    rows, cols = normals.shape[:2]
+    if image is None:
+        image = torch.empty((rows, cols, 4), dtype=torch.uint8, device=normals.device)
+    check(_lib.lib().sobfu_hip_render_image(*_image_ptr(points, torch.float32, 4), *_image_ptr(normals, torch.float32, 4), C.c_int(rows),
+                                            C.c_int(cols), _f(light[0]), _f(light[1]), _f(light[2]), *_image_ptr(image, torch.uint8, 4),
+                                            _stream()), "render_image")
+    return image
+
+
+def render_normals(normals, image=None):
+    """renderTangentColors: (r, g, b) = (n * 0.5 + 0.5) * 255 -> (rows, cols, 4) uint8 BGRA; misses are all zero."""
+    rows, cols = normals.shape[:2]
+    if image is None:
+        image = torch.empty((rows, cols, 4), dtype=torch.uint8, device=normals.device)
+    check(_lib.lib().sobfu_hip_render_normals(*_image_ptr(normals, torch.float32, 4), C.c_int(rows), C.c_int(cols),
+                                              *_image_ptr(image, torch.uint8, 4), _stream()), "render_normals")
+    return image
