@@ -193,6 +193,8 @@ int sobfu_hip_tile3_max_displacement(const float* d_psi, int Lx, int Ly, int Lz,
 int sobfu_hip_tile3_integrate_depth(const float* d_dists, int dists_step_bytes, int rows, int cols, float* d_vol_local, int Lx, int Ly,
                                     int Lz, int xb, int yb, int zb, const float voxel_size[3], float trunc_dist, float eta,
                                     const float R[9], const float t[3], float fx, float fy, float cx, float cy, void* stream);
+/* thin != 0 is a diagnostic entry (the native tile loop launches lists its handle owns): every call uploads its box list to a
+ * stream-ordered allocation on `stream`, one small blocking host-to-device copy per call. */
 int sobfu_hip_tile3_potential_gradient(const float* d_phi_n_psi, const float* d_phi_global, const float* d_psi, float* d_nabla_U,
                                        float w_reg, int Lx, int Ly, int Lz, const int box[6], int thin,
                                        const uint32_t* d_prev_slots, float max_update_norm, int compact, void* stream);

@@ -44,10 +44,8 @@ struct TileSync {
     uint32_t* peer_flags[kMaxSync];    // the flags array of sync_rank[i]
     uint32_t* peer_grows[kMaxSync];    // its global rows
 };
-// sync: device pointer to the handle's TileSync (null: no signalling); seq / wait / row / row_index: see TilePassAArgs
-int launch_tile_pass_a(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const TileLaunchBox* boxes,
-                       int n, TileSync* sync, uint32_t seq, int wait, const uint32_t* row, uint32_t row_index, int zc, hipStream_t stream, bool compact);
-// the same launch planned once (compact format): the box list is uploaded to device memory at plan time, a launch passes ~100 bytes
+// Pass A of a tile (compact format), planned once: the box list is uploaded to device memory at plan time, a launch passes ~100
+// bytes.  sync: device pointer to the handle's TileSync (null: no signalling); seq / wait / row / row_index: see TileSignal
 struct TilePassAPlan;
 int tile_pass_a_plan_create(TilePassAPlan** out, const TileLaunchBox* boxes, int n, int X, int Y, int Z);
 void tile_pass_a_plan_destroy(TilePassAPlan* p);

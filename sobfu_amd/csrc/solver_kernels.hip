@@ -13,8 +13,6 @@
 // Arithmetic is op-for-op the reference's (see sobfu_device.hpp): results are bit-identical to the launcher-for-launcher kernels.
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "sobfu_device.hpp"
@@ -168,29 +166,9 @@ static int finish_boxes(BoxList& L, const LaunchBox* boxes, int n, int ty, int c
     return total;
 }
 
-int launch_pass_a_boxes(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const LaunchBox* boxes,
-                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact) {
-    constexpr int TY = kRPT * kWY;
-    bool direct = false;
-    for (int i = 0; i < n; ++i) direct = direct || (boxes[i].direct && box_cells(boxes[i]) > 0);
-    if (direct) {  // thin boxes: the tile kernel (no messages, no signalling)
-        std::vector<TileLaunchBox> tb((size_t) n);
-        for (int i = 0; i < n; ++i) tb[(size_t) i] = TileLaunchBox{boxes[i], nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        return launch_tile_pass_a(pnp, pg, psi, nU, w_reg, X, Y, Z, tb.data(), n, (TileSync*) nullptr, 0, 0, nullptr, 0, zc, stream, compact);
-    }
-    PassAArgs a{{pnp, pg, psi, nU, {X, Y, Z}, w_reg, prev_slots, max_update_norm}, {}};
-    const int groups = finish_boxes(a.boxes, boxes, n, TY, 256 * 4 * 8 / kWY, 2, zc, "SOBFU_ZC_A");  // <= 52 VGPR, 22 KB LDS: 4 workgroups of 8 waves per CU
-    if (groups == 0) return 0;
-    const dim3 grid((unsigned) groups), block(TX, kWY);
-    if (compact && cache_resident(X, Y, Z)) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, 0>), grid, block, 0, stream, a);
-    else if (compact) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, kNT>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, false, 0>), grid, block, 0, stream, a);
-    return (int) hipGetLastError();
-}
-
-// Pass A of a multi-GPU tile (see tile_potential_gradient_kernel): the boxes with a destination (push boxes: direct, their
-// result goes to `dst` only) are numbered first, then the others.  sync / seq / wait / row: the direct transport's signalling.
-// the launch geometry of a tile's pass A: push boxes first; returns the workgroups (< 0: too many boxes)
+// Pass A of a multi-GPU tile (see tile_potential_gradient_kernel): the launch geometry of its box list.  The boxes with a
+// destination (push boxes: direct, their result goes to `dst` only) are numbered first, then the others; returns the workgroups
+// (< 0: too many boxes)
 static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, int X, int Y, int Z, int zc) {
     constexpr int TY = kRPT * kWY;
     L.n = 0;
@@ -209,7 +187,7 @@ static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, in
             const int zc_box = zc > 0 ? zc : ((s.dst != nullptr && !s.box.direct) ? std::min(8, s.box.z1 - s.box.z0) : 0);
             total += finish_box(t.b, s.box, TY, std::max(256 * (cache_resident(X, Y, Z) ? 2 : 4) * 8 / kWY / std::max(live, 1), 1), 2, zc_box,
                                 "SOBFU_ZC_A", false);
-            t.push.base = s.dst;  // (member by member: the list is looked up by its bytes, padding included -- the caller zeroed it)
+            t.push.base = s.dst;
             t.push.ox = s.ox; t.push.oy = s.oy; t.push.oz = s.oz; t.push.px = s.px; t.push.py = s.py;
             t.push.y0 = s.push_y0; t.push.y1 = s.push_y1; t.push.lz0 = s.local_z0; t.push.lz1 = s.local_z1;
             ++L.n;
@@ -220,96 +198,7 @@ static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, in
     return total;
 }
 
-// Device copies of the box lists seen so far.  An entry belongs to the HIP DEVICE it was allocated on (two handles on different GPUs
-// of one process may build byte-identical lists: each gets its own copy), is found by a hash of the list's bytes (then memcmp), and is
-// uploaded with hipMemcpyAsync ON THE LAUNCH STREAM from a pinned staging copy that lives as long as the entry: no blocking
-// null-stream copy inside a launch path, stream order makes the list visible to the launch that follows.  Entries are never freed
-// one by one (a launch in flight may still be reading its list); when a device's entries exceed kMaxCachedLists -- lists are keyed by
-// peer pointers, so a process that keeps creating handles keeps creating lists -- the device is drained and its entries are dropped.
-// Nobody keeps a pointer into this cache beyond the launch it was looked up for (a TilePassAPlan owns its own copy).
-struct CachedBoxes {
-    int device;
-    uint64_t hash;
-    TileBoxList* host;  // pinned
-    TileBoxList* dev;
-    hipEvent_t uploaded;    // completion of the upload: a launch that finds the entry waits for it on its own stream until it is known done
-    bool ready;
-    uint64_t retired;       // generation in which the entry left the look-up (graveyard entries)
-};
-constexpr size_t kMaxCachedLists = 256;
-static std::vector<CachedBoxes> g_box_cache, g_box_graveyard;
-static std::mutex g_box_cache_mutex;
-static uint64_t g_box_generation = 0;  // retirements so far
-static uint64_t bytes_hash(const void* p, size_t n) {  // FNV-1a
-    const unsigned char* b = (const unsigned char*) p;
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
-    return h;
-}
-static int device_boxes(const TileBoxList& L, TileBoxList** out, hipStream_t stream) {
-    int dev = 0;
-    SOBFU_HIP_TRY(hipGetDevice(&dev));
-    const uint64_t h = bytes_hash(&L, sizeof L);
-    std::unique_lock<std::mutex> lock(g_box_cache_mutex);
-    size_t on_dev = 0;
-    for (CachedBoxes& c : g_box_cache) {
-        if (c.device != dev) continue;
-        ++on_dev;
-        if (c.hash == h && std::memcmp(c.host, &L, sizeof L) == 0) {
-            if (!c.ready) {
-                if (hipEventQuery(c.uploaded) == hipSuccess) c.ready = true;
-                else SOBFU_HIP_TRY(hipStreamWaitEvent(stream, c.uploaded, 0));  // (also on the uploading stream: a no-op there, and a recycled stream handle cannot fool it)
-            }
-            *out = c.dev;
-            return 0;
-        }
-    }
-    if (on_dev >= kMaxCachedLists) {  // rare: this device's entries retire.  Two generations: what retired in an EARLIER generation is
-        // freed now, after a device drain; what retires now is only taken out of the look-up -- a thread that has just looked an entry up
-        // and is about to launch with it (the lock is not held across the launch) still finds it alive.  The drain runs WITHOUT the lock:
-        // with in-process ranks on the direct transport a kernel in flight may be waiting for a peer whose host thread needs this cache.
-        const uint64_t gen = g_box_generation;
-        lock.unlock();
-        SOBFU_HIP_TRY(hipDeviceSynchronize());
-        lock.lock();
-        for (size_t k = 0; k < g_box_graveyard.size();) {
-            if (g_box_graveyard[k].device == dev && g_box_graveyard[k].retired <= gen) {  // retired before the drain began
-                (void) hipFree(g_box_graveyard[k].dev);
-                (void) hipHostFree(g_box_graveyard[k].host);
-                (void) hipEventDestroy(g_box_graveyard[k].uploaded);
-                g_box_graveyard.erase(g_box_graveyard.begin() + (long) k);
-            } else ++k;
-        }
-        if (g_box_generation == gen) {  // nobody else retired this device's entries while the lock was open
-            g_box_generation += 1;
-            for (size_t k = 0; k < g_box_cache.size();) {
-                if (g_box_cache[k].device == dev) {
-                    g_box_cache[k].retired = g_box_generation;
-                    g_box_graveyard.push_back(g_box_cache[k]);
-                    g_box_cache.erase(g_box_cache.begin() + (long) k);
-                } else ++k;
-            }
-        }
-    }
-    CachedBoxes c{dev, h, nullptr, nullptr, nullptr, false, 0};
-    hipError_t e = hipHostMalloc((void**) &c.host, sizeof L, hipHostMallocDefault);
-    if (e == hipSuccess) {
-        std::memcpy(c.host, &L, sizeof L);
-        e = hipMalloc((void**) &c.dev, sizeof L);
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c.uploaded, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemcpyAsync(c.dev, c.host, sizeof L, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipEventRecord(c.uploaded, stream);
-    if (e != hipSuccess) {
-        if (c.uploaded) (void) hipEventDestroy(c.uploaded);
-        if (c.dev) (void) hipFree(c.dev);
-        if (c.host) (void) hipHostFree(c.host);
-        return (int) e;
-    }
-    g_box_cache.push_back(c);
-    *out = c.dev;
-    return 0;
-}
+// the launch of a box list in device memory; sync / seq / wait / row: the direct transport's signalling (sync null: none)
 static int launch_tile_boxes(const TileBoxList* d_boxes, int groups, const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X,
                              int Y, int Z, TileSync* sync, uint32_t seq, int wait, const uint32_t* row, uint32_t row_index, hipStream_t stream,
                              bool compact) {
@@ -322,16 +211,33 @@ static int launch_tile_boxes(const TileBoxList* d_boxes, int groups, const float
     return (int) hipGetLastError();
 }
 
-int launch_tile_pass_a(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const TileLaunchBox* boxes,
-                       int n, TileSync* sync, uint32_t seq, int wait, const uint32_t* row, uint32_t row_index, int zc, hipStream_t stream, bool compact) {
-    TileBoxList L;
-    std::memset(&L, 0, sizeof L);  // (padding bytes too: the list is looked up by its bytes)
-    const int total = fill_tile_boxes(L, boxes, n, X, Y, Z, zc);
-    if (total < 0) return SOBFU_E_BADARG;
-    if (total == 0) return 0;
-    TileBoxList* d = nullptr;
-    SOBFU_TRY(device_boxes(L, &d, stream));
-    return launch_tile_boxes(d, total, pnp, pg, psi, nU, w_reg, X, Y, Z, sync, seq, wait, row, row_index, stream, compact);
+int launch_pass_a_boxes(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const LaunchBox* boxes,
+                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact) {
+    constexpr int TY = kRPT * kWY;
+    bool direct = false;
+    for (int i = 0; i < n; ++i) direct = direct || (boxes[i].direct && box_cells(boxes[i]) > 0);
+    if (direct) {  // thin boxes: the tile kernel (no messages, no signalling) with a list of this call's own
+        std::vector<TileLaunchBox> tb((size_t) n);
+        for (int i = 0; i < n; ++i) tb[(size_t) i] = TileLaunchBox{boxes[i], nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        TileBoxList L{};
+        const int total = fill_tile_boxes(L, tb.data(), n, X, Y, Z, zc);
+        if (total <= 0) return total < 0 ? SOBFU_E_BADARG : 0;
+        // a stream-ordered device copy, freed behind the launch (hipMemcpyAsync from pageable memory has read L when it returns)
+        TileBoxList* d = nullptr;
+        SOBFU_HIP_TRY(hipMallocAsync((void**) &d, sizeof L, stream));
+        const hipError_t e = hipMemcpyAsync(d, &L, sizeof L, hipMemcpyHostToDevice, stream);
+        const int rc = e != hipSuccess ? (int) e : launch_tile_boxes(d, total, pnp, pg, psi, nU, w_reg, X, Y, Z, nullptr, 0, 0, nullptr, 0, stream, compact);
+        const hipError_t f = hipFreeAsync(d, stream);
+        return rc != 0 ? rc : (int) f;
+    }
+    PassAArgs a{{pnp, pg, psi, nU, {X, Y, Z}, w_reg, prev_slots, max_update_norm}, {}};
+    const int groups = finish_boxes(a.boxes, boxes, n, TY, 256 * 4 * 8 / kWY, 2, zc, "SOBFU_ZC_A");  // <= 52 VGPR, 22 KB LDS: 4 workgroups of 8 waves per CU
+    if (groups == 0) return 0;
+    const dim3 grid((unsigned) groups), block(TX, kWY);
+    if (compact && cache_resident(X, Y, Z)) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, 0>), grid, block, 0, stream, a);
+    else if (compact) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, kNT>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, false, 0>), grid, block, 0, stream, a);
+    return (int) hipGetLastError();
 }
 
 // A PLANNED launch of the same pass (compact format): the geometry is worked out once per handle and half of the nabla_U ping-pong
@@ -340,14 +246,13 @@ struct TilePassAPlan {
     int groups = 0, X = 0, Y = 0, Z = 0;
 };
 int tile_pass_a_plan_create(TilePassAPlan** out, const TileLaunchBox* boxes, int n, int X, int Y, int Z) {
-    TileBoxList L;
-    std::memset(&L, 0, sizeof L);
+    TileBoxList L{};
     const int total = fill_tile_boxes(L, boxes, n, X, Y, Z, 0);
     if (total < 0) return SOBFU_E_BADARG;
     auto* p = new TilePassAPlan();
     p->groups = total; p->X = X; p->Y = Y; p->Z = Z;
-    // a plan OWNS its device copy (the cache above may drop its entries; a plan lives as long as its handle): plan time is handle
-    // creation, not a launch path, so a blocking copy is fine -- the list is simply there before any stream launches with it
+    // a plan owns its device copy and lives as long as its handle: plan time is handle creation, not a launch path, so a blocking
+    // copy is fine -- the list is simply there before any stream launches with it
     hipError_t e = hipSuccess;
     if (total > 0) {
         e = hipMalloc((void**) &p->d_boxes, sizeof L);

@@ -371,8 +371,8 @@ struct TileSignal {
     const uint32_t* row;  // this rank's max-norm slot row of the PREVIOUS iteration (null: none) ...
     uint32_t row_index;   // ... which is row `row_index` of the global rows
 };
-// The box list of a launch lives in DEVICE memory (a list is fixed for the life of a handle: uploaded once -- launch_tile_pass_a keeps
-// every distinct list it has seen -- and read through the scalar cache), not in the kernel-argument segment: a 1.5 KB argument block
+// The box list of a launch lives in DEVICE memory (a list is fixed for the life of a handle: uploaded once, by the handle's launch
+// plan -- and read through the scalar cache), not in the kernel-argument segment: a 1.5 KB argument block
 // costs a launch 0.6 us (tools/calib/launch_cost.hip: 2.9 -> 3.5 us back to back), and handed on by reference it ended up copied to
 // 1.8 KB of scratch per lane (pass A 17 -> 129 us: found with SOBFU_TILED_DEBUG_SKIP=1)
 struct TilePassAArgsP {

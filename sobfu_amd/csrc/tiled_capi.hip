@@ -280,9 +280,9 @@ struct sobfu_hip_tiled {
     uint32_t *flags = nullptr, *grows = nullptr, *grows_own = nullptr;  // grows_own: a larger private copy once a solve outgrew the arena's
     uint32_t seq_total = 0;                        // sequence numbers used so far (every rank counts the same)
     uint64_t timeout_ticks = 0;                    // deadline of the in-kernel waits (100 MHz ticks; SOBFU_TILED_DEADLINE_S at create)
-    std::vector<sobfu_hip::TileLaunchBox> a_boxes[2];  // pass A's boxes per nabla_U half: one push box per message + the owned block
-    sobfu_hip::TilePassAPlan* a_plan[2] = {nullptr, nullptr};  // ... and their launch plans (box lists in device memory)
-    sobfu_hip::TileLaunchBox a_own{};  // the owned block alone (launches without messages)
+    // pass A's launch plans (box lists in device memory, see build_a_boxes), per nabla_U half: one push box per message + the owned
+    // block, and the push boxes alone (sobfu_hip_tiled_probe_push); the whole owned block alone (launches without messages)
+    sobfu_hip::TilePassAPlan *a_plan[2] = {nullptr, nullptr}, *a_push_plan[2] = {nullptr, nullptr}, *a_own_plan = nullptr;
     int schedule = 0;  // 0 heuristic, 1 overlapped + pass A split, 2 overlapped + pass A whole, 3 serial (sobfu_hip_tiled_set_schedule)
     double last_enqueue_us = 0.0;  // host time per iteration the last iterate() spent issuing the loop (diagnostics)
     // optional timing of the serial schedule's three pieces with HIP events on the loop's stream (sobfu_hip_tiled_set_profiling)
@@ -309,9 +309,9 @@ double deadline_seconds() {
     return v > 0.0 ? v : 30.0;
 }
 
-// (re)builds pass A's box lists: one push box per message, then the owned block.  Destinations: the peers' halo cells when
-// connected (dst[half][i] != null), else the packed send buffer.
-void build_a_boxes(sobfu_hip_tiled* t, float* const* dst0, float* const* dst1, const TileLay* peers) {
+// (re)builds pass A's box lists and their launch plans: one push box per message, then the owned block.  Destinations: the peers'
+// halo cells when connected (dst[half][i] != null), else the packed send buffer.  On failure the handle keeps the plans it had.
+int build_a_boxes(sobfu_hip_tiled* t, float* const* dst0, float* const* dst1, const TileLay* peers) {
     // The y and z FACES are pushed by short marches whose cells the owned block would compute a second time.  Instead such a box
     // stands in for the owned block on its cells (it stores them at home too) and the owned block shrinks: by the 4 rim planes
     // along z, by a whole 8-row tile along y (the face box then marches 8 rows, of which the 4 rim rows travel).  Where face
@@ -327,9 +327,13 @@ void build_a_boxes(sobfu_hip_tiled* t, float* const* dst0, float* const* dst1, c
     const bool y_home = wide && ny_nb > 0 && (t->o1[1] - t->o0[1]) > 8 * ny_nb;
     const int iz0 = t->o0[2] + ((z_home && t->lo[2]) ? kHalo : 0), iz1 = t->o1[2] - ((z_home && t->hi[2]) ? kHalo : 0);  // planes the z boxes leave
     const int iy0 = t->o0[1] + ((y_home && t->lo[1]) ? 8 : 0), iy1 = t->o1[1] - ((y_home && t->hi[1]) ? 8 : 0);
+    sobfu_hip::TilePassAPlan *all[2] = {nullptr, nullptr}, *push[2] = {nullptr, nullptr}, *own_only = nullptr;
+    int rc = 0;
+    auto plan = [&](sobfu_hip::TilePassAPlan** out, const std::vector<sobfu_hip::TileLaunchBox>& v) {
+        if (rc == 0) rc = sobfu_hip::tile_pass_a_plan_create(out, v.data(), (int) v.size(), t->L[0], t->L[1], t->L[2]);
+    };
     for (int h = 0; h < 2; ++h) {
-        std::vector<sobfu_hip::TileLaunchBox>& v = t->a_boxes[h];
-        v.clear();
+        std::vector<sobfu_hip::TileLaunchBox> v;
         for (size_t i = 0; i < t->geom.size(); ++i) {
             const MsgGeom& m = t->geom[i];
             sobfu_hip::TileLaunchBox b{};
@@ -363,16 +367,23 @@ void build_a_boxes(sobfu_hip_tiled* t, float* const* dst0, float* const* dst1, c
             }
             v.push_back(b);
         }
+        plan(&push[h], v);
         sobfu_hip::TileLaunchBox own{};
         own.box = sobfu_hip::LaunchBox{t->o0[0], t->o1[0], iy0, iy1, iz0, iz1, false};
         v.push_back(own);
-        // the same launch without messages (a world of one; timing experiments): the whole owned block
-        t->a_own = sobfu_hip::TileLaunchBox{};
-        t->a_own.box = sobfu_hip::LaunchBox{t->o0[0], t->o1[0], t->o0[1], t->o1[1], t->o0[2], t->o1[2], false};
-        sobfu_hip::tile_pass_a_plan_destroy(t->a_plan[h]);
-        t->a_plan[h] = nullptr;
-        if (sobfu_hip::tile_pass_a_plan_create(&t->a_plan[h], v.data(), (int) v.size(), t->L[0], t->L[1], t->L[2]) != 0) t->a_plan[h] = nullptr;
+        plan(&all[h], v);
     }
+    // the same launch without messages (a world of one; timing experiments): the whole owned block
+    sobfu_hip::TileLaunchBox whole{};
+    whole.box = sobfu_hip::LaunchBox{t->o0[0], t->o1[0], t->o0[1], t->o1[1], t->o0[2], t->o1[2], false};
+    plan(&own_only, {whole});
+    if (rc == 0) {
+        std::swap(all, t->a_plan);
+        std::swap(push, t->a_push_plan);
+        std::swap(own_only, t->a_own_plan);
+    }
+    for (sobfu_hip::TilePassAPlan* p : {all[0], all[1], push[0], push[1], own_only}) sobfu_hip::tile_pass_a_plan_destroy(p);  // the old plans, or the new ones
+    return rc;
 }
 
 void abort_comms(sobfu_hip_tiled* t) {
@@ -435,7 +446,7 @@ int sobfu_hip_tiled_destroy(sobfu_hip_tiled* t) {
     if (t->grows_own) (void) hipFree(t->grows_own);
     if (t->flags) pool_give_back(t->flags);
     if (t->sync_d) (void) hipFree(t->sync_d);
-    for (int h = 0; h < 2; ++h) sobfu_hip::tile_pass_a_plan_destroy(t->a_plan[h]);
+    for (sobfu_hip::TilePassAPlan* p : {t->a_plan[0], t->a_plan[1], t->a_push_plan[0], t->a_push_plan[1], t->a_own_plan}) sobfu_hip::tile_pass_a_plan_destroy(p);
     for (hipEvent_t e : t->prof_ev) (void) hipEventDestroy(e);
     if (t->sendbuf) (void) hipFree(t->sendbuf);
     if (t->recvbuf) (void) hipFree(t->recvbuf);
@@ -564,7 +575,7 @@ int sobfu_hip_tiled_create3(sobfu_hip_tiled** out, int X, int Y, int Z, int Px, 
         sy.my_flags = t->flags; sy.my_grows = t->grows;
         rc = (int) hipMemcpy(t->sync_d, &sy, sizeof sy, hipMemcpyHostToDevice);
     }
-    if (rc == 0) build_a_boxes(t, nullptr, nullptr, nullptr);
+    if (rc == 0) rc = build_a_boxes(t, nullptr, nullptr, nullptr);
     if (rc == 0) rc = (int) hipStreamCreateWithFlags(&t->comm_stream, hipStreamNonBlocking);
     if (rc == 0) rc = (int) hipEventCreateWithFlags(&t->ev_bnd, hipEventDisableTiming);
     if (rc == 0) rc = (int) hipEventCreateWithFlags(&t->ev_xchg, hipEventDisableTiming);
@@ -687,7 +698,7 @@ int sobfu_hip_tiled_connect(sobfu_hip_tiled* t, int n_peers, const int* peer_ran
     }
     SOBFU_HIP_TRY(hipMemcpy(t->sync_d, &sy, sizeof sy, hipMemcpyHostToDevice));
     SOBFU_HIP_TRY(hipDeviceSynchronize());
-    build_a_boxes(t, d0.data(), d1.data(), pl.data());
+    SOBFU_TRY(build_a_boxes(t, d0.data(), d1.data(), pl.data()));
     t->direct = true;
     return 0;
 }
@@ -741,11 +752,10 @@ int sobfu_hip_tiled_probe_push(sobfu_hip_tiled* t, int reps, void* stream) {
     if (t->dead) return SOBFU_E_TIMEOUT;
     for (int r = 0; r < reps; ++r) {
         const uint32_t seq = ++t->seq_total;
-        const std::vector<sobfu_hip::TileLaunchBox>& bx = t->a_boxes[seq & 1u];
-        if (bx.size() < 2) continue;  // no messages
-        // pass A's push boxes alone, on whatever the compact state holds (the halo rims they fill are scratch between solves)
-        SOBFU_TRY(sobfu_hip::launch_tile_pass_a(t->c_f, t->c_g, t->c_psi, t->nUb[seq & 1u], t->p.w_reg, t->L[0], t->L[1], t->L[2], bx.data(),
-                                                (int) bx.size() - 1, t->sync_d, seq, t->wait_enabled, nullptr, 0, 0, (hipStream_t) stream, true));
+        // pass A's push boxes alone, on whatever the compact state holds (the halo rims they fill are scratch between solves); no
+        // messages: no launch
+        SOBFU_TRY(sobfu_hip::launch_tile_pass_a_plan(t->a_push_plan[seq & 1u], t->c_f, t->c_g, t->c_psi, t->nUb[seq & 1u], t->p.w_reg, t->sync_d, seq,
+                                                     t->wait_enabled, nullptr, 0, (hipStream_t) stream));
     }
     return 0;
 }
@@ -1122,18 +1132,12 @@ static int tiled_step_impl(sobfu_hip_tiled* t, int n_steps, hipStream_t st, int 
             // kernel scatters what arrived.  No cross-stream events anywhere.
             if (phases & 1) {
                 if (ev) SOBFU_HIP_TRY(hipEventRecord(e[0], st));
-                const std::vector<sobfu_hip::TileLaunchBox>& bx = t->a_boxes[it & 1];
                 const bool pushes = (multi || sync) && !(dbg & 1);  // a world of one has no messages
                 const uint32_t* row_prev = (sync && it >= 2) ? t->slots + (size_t) (it - 1) * kSlots : nullptr;
-                if (dbg & 4) {
-                } else if (pushes && t->a_plan[it & 1]) {  // the planned launch: box list in device memory
-                    SOBFU_TRY(sobfu_hip::launch_tile_pass_a_plan(t->a_plan[it & 1], f_in, t->c_g, psi_in, nu, p.w_reg, sync ? t->sync_d : nullptr,
-                                                                 q.seq_base + (uint32_t) it, t->wait_enabled, row_prev, (uint32_t) (it - 1), st));
-                } else {
-                    SOBFU_TRY(sobfu_hip::launch_tile_pass_a(f_in, t->c_g, psi_in, nu, p.w_reg, Lx, Ly, Lz, pushes ? bx.data() : &t->a_own,
-                                                            pushes ? (int) bx.size() : 1, sync ? t->sync_d : nullptr, q.seq_base + (uint32_t) it,
-                                                            t->wait_enabled, row_prev, (uint32_t) (it - 1), 0, st, true));
-                }
+                if (!(dbg & 4))
+                    SOBFU_TRY(sobfu_hip::launch_tile_pass_a_plan(pushes ? t->a_plan[it & 1] : t->a_own_plan, f_in, t->c_g, psi_in, nu, p.w_reg,
+                                                                 sync ? t->sync_d : nullptr, q.seq_base + (uint32_t) it, t->wait_enabled, row_prev,
+                                                                 (uint32_t) (it - 1), st));
                 if (ev) SOBFU_HIP_TRY(hipEventRecord(e[1], st));
                 if (multi && !sync) SOBFU_TRY(exchange_packed(t, nu, st));
             }

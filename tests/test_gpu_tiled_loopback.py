@@ -806,11 +806,11 @@ def test_config4_tiles_against_the_emulated_reference_256():
     check(f, "psi", psi4), check(f, "phi_n_psi", pnp_t)
 
 
-def test_box_list_cache_turnover_leaves_live_handles_alone():
-    """A process that keeps creating tile handles keeps creating box lists; the library's cache of their device copies is bounded
-    (256 per device) and retires its entries when full.  A handle that was created BEFORE the turnover -- its planned pass-A launches
-    own their lists -- must compute the same bits after it, and so must handles created during it (found in round 5: the bound first
-    freed lists that live plans still pointed to; the full GPU suite, > 256 handles in one process, caught it once in four runs)."""
+def test_handle_churn_leaves_live_handles_alone():
+    """A process that keeps creating and closing tile handles keeps creating and freeing their pass-A box lists (every handle owns the
+    device copies its launches read).  Handles created BEFORE 300 others came and went must compute the same bits after them, a
+    2 x 2 x 2 tile and a world of one alike (found in round 5, when the lists lived in a bounded process-wide cache: its bound first
+    freed lists that live handles still pointed to; the full GPU suite, > 256 handles in one process, caught it once in four runs)."""
     import torch
 
     from sobfu_amd import ops, tiled
@@ -829,9 +829,9 @@ def test_box_list_cache_turnover_leaves_live_handles_alone():
         return psi_l.clone(), pnp_l.clone()
 
     old = tiled.NativeTiledSolver(dims, alpha=0.05, w_reg=0.4, dry=(8, 7), grid=(2, 2, 2))  # planned launches (push boxes into its send buffer)
-    one = tiled.NativeTiledSolver(dims, alpha=0.05, w_reg=0.4, dry=(1, 0), grid=(1, 1, 1))  # a world of one: the cached (un-planned) path
+    one = tiled.NativeTiledSolver(dims, alpha=0.05, w_reg=0.4, dry=(1, 0), grid=(1, 1, 1))  # a world of one: the owned block alone
     want_old, want_one = run(old), run(one)
-    for i in range(300):  # 300 distinct lists through the cache (a world of one looks its list up at every launch)
+    for i in range(300):  # 300 handles with distinct lists, each created, iterated and closed
         sv = tiled.NativeTiledSolver((8 + i % 150, 8 + i // 150, 8), alpha=0.05, w_reg=0.4, dry=(1, 0), grid=(1, 1, 1))
         L = sv.layout
         sv.iterate(sv.new_local(2), torch.zeros((8, 8 + i // 150, 8 + i % 150, 2), device="cuda"), sv.new_local(2), sv.identity_psi(), 1)
