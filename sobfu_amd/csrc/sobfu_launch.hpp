@@ -26,7 +26,8 @@ struct TileLaunchBox {
 // (X, Y, Z): extents of the field arrays; (pX, pY, pZ): extents of phi_n (the whole volume); own: the cells that enter the
 // max-norm (x0, x1, y0, y1, z0, z1).
 int launch_pass_a_boxes(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const LaunchBox* boxes,
-                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact);
+                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact,
+                        bool warp = false /* pnp is phi_n: pass A samples phi_n at psi itself (see loop_warps_in_pass_a) */);
 // Signalling state of the direct transport (device memory, one per tiled handle; filled by sobfu_hip_tiled_connect and read by
 // the tail of tile_potential_gradient_kernel).
 constexpr int kMaxSync = 64;
@@ -62,17 +63,21 @@ int launch_pass_b_boxes(const float* nU, float* psi, const float* phi_n, float* 
                         float* psi_out = nullptr /* null: update psi in place */, int prev_rows = 1,
                         bool sys_acquire = false /* the launch reads cells other GPUs stored: nabla_U and the max-norm rows are READ AT SYSTEM SCOPE
                                                      (sc0 sc1 loads of the pipelined march / the thin shells / the gate; there is no invalidate -- + 39 us,
-                                                     measured); a launch that cannot take that march is refused with SOBFU_E_UNSUPPORTED */);
+                                                     measured); a launch that cannot take that march is refused with SOBFU_E_UNSUPPORTED */,
+                        bool apply = true /* false: no phi_n o psi (loop_warps_in_pass_a); refused where the launch would not take the plain march */);
 // Pass A / pass B over planes [z_lo, z_hi) (z_hi <= 0: the whole grid) and, optionally, a second range [z_lo2, z_hi2)
 // in the same launch (both boundary regions of a multi-GPU slab).  zc <= 0: z-chunk chosen by the cost model.
 int launch_pass_a(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z,
                   const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, int z_lo = 0, int z_hi = 0,
-                  int z_lo2 = 0, int z_hi2 = 0);
+                  int z_lo2 = 0, int z_hi2 = 0, bool warp = false);
 int launch_pass_b(const float* nU, float* psi, const float* phi_n, float* pnp, float* updates, uint32_t* slots,
                   const float taps[7], float alpha, int X, int Y, int Z, const uint32_t* prev_slots,
                   float max_update_norm, int zc, hipStream_t stream, int phi_Z, int own_lo, int own_hi, bool compact, int z_lo = 0,
                   int z_hi = 0, int z_lo2 = 0, int z_hi2 = 0, float* psi_out = nullptr /* null: update psi in place */,
-                  int prev_rows = 1 /* rows the gate reads, see solver_converged */);
+                  int prev_rows = 1 /* rows the gate reads, see solver_converged */, bool apply = true);
+// Does the compact single-GPU loop of this grid run without the phi_n o psi stream?  Then its pass A takes phi_n for pnp and
+// warp = true, its pass B apply = false (solver_kernels.hip).
+bool loop_warps_in_pass_a(int X, int Y, int Z);
 int launch_pack_vec(const float* src4, float* dst3, size_t N, hipStream_t stream);
 int launch_unpack_vec(const float* src3, float* dst4, size_t N, hipStream_t stream);
 int launch_extract_tsdf(const float* src2, float* dst1, size_t N, hipStream_t stream);

@@ -88,6 +88,7 @@ struct sobfu_hip_solver {
         bool converged = false;
         float last_norm = 0.f;
         bool inline_log = false;  // the verbose loop prints its lines as it goes; session_end then only adds the closing line
+        bool warp = false;  // the loop runs without the phi_n o psi stream (sobfu_hip::loop_warps_in_pass_a)
     } q;
 
     void log(const std::string& line) const {
@@ -200,6 +201,10 @@ int session_begin_impl(sobfu_hip_solver* s, const float* pg, const float* pn, fl
         SOBFU_TRY(ensure_compact(s));
         SOBFU_TRY(sobfu_hip::launch_compact_enter(psi, pg, pn, s->c_psi, s->c_g, s->c_n, s->c_f, X, Y, Z, st));  // incl. solver.cu:106
         q.it_pnp = s->c_f; q.it_pg = s->c_g; q.it_pn = s->c_n; q.it_psi = s->c_psi; q.it_out = s->c_f;
+        // quiet solves of big grids: pass A warps phi_n itself and pass B stores no phi_n o psi (c_f is then not kept current, so
+        // the verbose loop, whose energies read it, and solves that keep `updates` stay on the F stream; session_end rebuilds the
+        // caller's phi_n o psi from psi either way)
+        q.warp = s->p.verbosity == 0 && !q.upd && sobfu_hip::loop_warps_in_pass_a(X, Y, Z);
     }
     if (s->p.max_update_norm >= 0.f) SOBFU_TRY(ensure_poll(s, cap));
     if (s->prof_stride > 0) SOBFU_TRY(ensure_events(s, (size_t) 3 * (cap / s->prof_stride + 1)));
@@ -242,10 +247,11 @@ int session_enqueue(sobfu_hip_solver* s, int n, bool poll, float* per_iter, hipS
         const bool ev = s->prof_stride > 0 && (it % s->prof_stride == 0) && (size_t) 3 * (s->prof_pending + 1) <= s->events.size();
         const int e0  = 3 * s->prof_pending;
         if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0], st));
-        SOBFU_TRY(sobfu_hip::launch_pass_a(q.it_pnp, q.it_pg, q.it_psi, s->nabla_U, p.w_reg, X, Y, Z, prev, p.max_update_norm, 0, st, q.compact));
+        SOBFU_TRY(sobfu_hip::launch_pass_a(q.warp ? q.it_pn : q.it_pnp, q.it_pg, q.it_psi, s->nabla_U, p.w_reg, X, Y, Z, prev, p.max_update_norm, 0,
+                                           st, q.compact, 0, 0, 0, 0, q.warp));
         if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 1], st));
         SOBFU_TRY(sobfu_hip::launch_pass_b(s->nabla_U, q.it_psi, q.it_pn, q.it_out, q.upd, cur, s->taps, p.alpha, X, Y, Z, prev,
-                                           p.max_update_norm, 0, st, 0, 0, 0, q.compact));
+                                           p.max_update_norm, 0, st, 0, 0, 0, q.compact, 0, 0, 0, 0, nullptr, 1, !q.warp));
         if (ev) {
             SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 2], st));
             s->prof_pending += 1;

@@ -211,11 +211,24 @@ static int launch_tile_boxes(const TileBoxList* d_boxes, int groups, const float
     return (int) hipGetLastError();
 }
 
+// The compact single-GPU loop of a grid beyond the Infinity Cache runs without the phi_n o psi stream: pass A warps phi_n itself
+// (pass_a_march, WARP), pass B neither warps nor stores F (APPLY = false) -- 68 instead of 76 B per cell and iteration.  The grids
+// whose pass B takes the plain march with buffer-addressed psi (NTBUF); SOBFU_WARP_A=0 turns the pair off (tuning override).
+bool loop_warps_in_pass_a(int X, int Y, int Z) {
+    const char* e = getenv("SOBFU_WARP_A");
+    if (e && atoi(e) == 0) return false;
+    const char* pipe_e = getenv("SOBFU_PIPE_B");
+    const size_t n = (size_t) X * Y * Z;
+    return !cache_resident(X, Y, Z) && !(pipe_e && atoi(pipe_e) != 0) && n * 12 < ((size_t) 1 << 32) && (size_t) X * Y * 16 < ((size_t) 1 << 32);
+}
+
 int launch_pass_a_boxes(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const LaunchBox* boxes,
-                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact) {
+                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, bool warp) {
     constexpr int TY = kRPT * kWY;
     bool direct = false;
     for (int i = 0; i < n; ++i) direct = direct || (boxes[i].direct && box_cells(boxes[i]) > 0);
+    // warp: pnp is phi_n (tsdf-only, extents X, Y, Z), sampled with 32-bit byte offsets
+    if (warp && (direct || !compact || cache_resident(X, Y, Z) || (size_t) X * Y * Z * 4 >= ((size_t) 1 << 32))) return SOBFU_E_UNSUPPORTED;
     if (direct) {  // thin boxes: the tile kernel (no messages, no signalling) with a list of this call's own
         std::vector<TileLaunchBox> tb((size_t) n);
         for (int i = 0; i < n; ++i) tb[(size_t) i] = TileLaunchBox{boxes[i], nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -231,10 +244,12 @@ int launch_pass_a_boxes(const float* pnp, const float* pg, const float* psi, flo
         return rc != 0 ? rc : (int) f;
     }
     PassAArgs a{{pnp, pg, psi, nU, {X, Y, Z}, w_reg, prev_slots, max_update_norm}, {}};
-    const int groups = finish_boxes(a.boxes, boxes, n, TY, 256 * 4 * 8 / kWY, 2, zc, "SOBFU_ZC_A");  // <= 52 VGPR, 22 KB LDS: 4 workgroups of 8 waves per CU
+    // <= 64 VGPR (the warping march included), 22 KB LDS: 4 workgroups of 8 waves per CU
+    const int groups = finish_boxes(a.boxes, boxes, n, TY, 256 * 4 * 8 / kWY, 2, zc, "SOBFU_ZC_A");
     if (groups == 0) return 0;
     const dim3 grid((unsigned) groups), block(TX, kWY);
-    if (compact && cache_resident(X, Y, Z)) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, 0>), grid, block, 0, stream, a);
+    if (warp) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, kNT, true>), grid, block, 0, stream, a);
+    else if (compact && cache_resident(X, Y, Z)) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, 0>), grid, block, 0, stream, a);
     else if (compact) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, kNT>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, false, 0>), grid, block, 0, stream, a);
     return (int) hipGetLastError();
@@ -289,7 +304,7 @@ int launch_tile_flush(TileSync* sync, uint32_t seq, int wait, const uint32_t* ro
 int launch_pass_b_boxes(const float* nU, float* psi, const float* phi_n, float* pnp, float* updates, uint32_t* slots, const float taps[7],
                         float alpha, int X, int Y, int Z, int pX, int pY, int pZ, const int own[6], const LaunchBox* boxes, int n,
                         const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, float* psi_out, int prev_rows,
-                        bool sys_acquire) {
+                        bool sys_acquire, bool apply) {
     constexpr int TY = kRPT * kWY;
     PassBArgs a{nU, psi, phi_n, pnp, (float4*) updates, slots, {X, Y, Z}, {}, alpha, {}, prev_slots, max_update_norm, {pX, pY, pZ},
                 {own[0], own[1], own[2], own[3], own[4], own[5]}, prev_rows, psi_out ? psi_out : psi, sys_acquire ? 1 : 0};
@@ -317,12 +332,14 @@ int launch_pass_b_boxes(const float* nU, float* psi, const float* phi_n, float* 
         if (a.boxes.b[i].kind == 0) zc_max = std::max(zc_max, a.boxes.b[i].zc + (a.boxes.b[i].rem > 0 ? 1 : 0));  // the first `rem` chunks march one plane more
         if (a.boxes.b[i].kind == 0 && pipe && resident && SOBFU_PAIR_B) a.boxes.b[i].pair = 1;  // neighbouring z-chunks march towards / away from each other
     }
+    const bool ntbuf = (size_t) X * Y * Z * 12 < ((size_t) 1 << 32);  // the plain march's 12-byte psi load / store as buffer instructions (their cache-policy operand carries the streaming hint): arrays below 4 GiB
+    // !apply (loop_warps_in_pass_a): the plain march with buffer-addressed psi only -- any other launch would leave phi_n o psi stale
+    if (!apply && (direct || !compact || !idx32 || updates || resident || pipe || !ntbuf || sys_acquire)) return SOBFU_E_UNSUPPORTED;
     const dim3 grid((unsigned) groups), block(TX, kWY);
 #define SOBFU_LAUNCH_B(UPD, CMP, DIR) \
     hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, UPD, CMP, DIR>), grid, block, 0, stream, a)
 #define SOBFU_LAUNCH_BX(DIR, HLV, NTV, PIP) \
     hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, DIR, true, HLV, NTV, PIP>), grid, block, 0, stream, a)
-    const bool ntbuf = (size_t) X * Y * Z * 12 < ((size_t) 1 << 32);  // the plain march's 12-byte psi load / store as buffer instructions (their cache-policy operand carries the streaming hint): arrays below 4 GiB
     if (direct) {
         if (updates && compact) SOBFU_LAUNCH_B(true, true, true);
         else if (updates) SOBFU_LAUNCH_B(true, false, true);
@@ -342,7 +359,9 @@ int launch_pass_b_boxes(const float* nU, float* psi, const float* phi_n, float* 
             // long marches (big grids): halo requests run SOBFU_HLEAD planes ahead; short ones (small grids, multi-GPU tiles) skip
             // the extra prologue round trip
             const bool lead = SOBFU_HLEAD > 0 && zc_max >= SOBFU_HLEAD_MIN_ZC && !resident && !pipe;
-            if (lead && ntbuf) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, SOBFU_HLEAD, kNT, false, true>), grid, block, 0, stream, a);
+            if (!apply && lead) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, SOBFU_HLEAD, kNT, false, true, false>), grid, block, 0, stream, a);
+            else if (!apply) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, 0, kNT, false, true, false>), grid, block, 0, stream, a);
+            else if (lead && ntbuf) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, SOBFU_HLEAD, kNT, false, true>), grid, block, 0, stream, a);
             else if (lead) SOBFU_LAUNCH_BX(false, SOBFU_HLEAD, kNT, false);
             else if (resident && pipe) SOBFU_LAUNCH_BX(false, 0, 0, true);
             else if (resident) SOBFU_LAUNCH_BX(false, 0, 0, false);
@@ -361,22 +380,22 @@ int launch_pass_b_boxes(const float* nU, float* psi, const float* phi_n, float* 
 // z-range forms (whole x-y planes of the array): the single-GPU solver and the z-slab loop
 int launch_pass_a(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z,
                   const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, int z_lo, int z_hi,
-                  int z_lo2, int z_hi2) {
+                  int z_lo2, int z_hi2, bool warp) {
     if (z_hi <= 0 && z_hi2 <= z_lo2) { z_lo = 0; z_hi = Z; }  // no range given: the whole grid
     const LaunchBox b[2] = {{0, X, 0, Y, z_lo, z_hi, false}, {0, X, 0, Y, z_lo2, z_hi2, false}};
-    return launch_pass_a_boxes(pnp, pg, psi, nU, w_reg, X, Y, Z, b, 2, prev_slots, max_update_norm, zc, stream, compact);
+    return launch_pass_a_boxes(pnp, pg, psi, nU, w_reg, X, Y, Z, b, 2, prev_slots, max_update_norm, zc, stream, compact, warp);
 }
 
 int launch_pass_b(const float* nU, float* psi, const float* phi_n, float* pnp, float* updates, uint32_t* slots,
                   const float taps[7], float alpha, int X, int Y, int Z, const uint32_t* prev_slots,
                   float max_update_norm, int zc, hipStream_t stream, int phi_Z, int own_lo, int own_hi, bool compact, int z_lo,
-                  int z_hi, int z_lo2, int z_hi2, float* psi_out, int prev_rows) {
+                  int z_hi, int z_lo2, int z_hi2, float* psi_out, int prev_rows, bool apply) {
     if (phi_Z <= 0) { phi_Z = Z; own_lo = 0; own_hi = Z; }
     if (z_hi <= 0 && z_hi2 <= z_lo2) { z_lo = 0; z_hi = Z; }  // no range given: the whole grid
     const LaunchBox b[2] = {{0, X, 0, Y, z_lo, z_hi, false}, {0, X, 0, Y, z_lo2, z_hi2, false}};
     const int own[6] = {0, X, 0, Y, own_lo, own_hi};
     return launch_pass_b_boxes(nU, psi, phi_n, pnp, updates, slots, taps, alpha, X, Y, Z, X, Y, phi_Z, own, b, 2, prev_slots, max_update_norm, zc,
-                               stream, compact, psi_out, prev_rows);
+                               stream, compact, psi_out, prev_rows, false, apply);
 }
 
 #define SOBFU_LIN(N) dim3((unsigned) (((N) + 255) / 256)), dim3(256), 0, stream

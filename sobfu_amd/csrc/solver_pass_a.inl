@@ -3,7 +3,7 @@
 
 // --- pass A ----------------------------------------------------------------------------------------------------
 struct PassACore {
-    const void* pnp;  // phi_n o psi
+    const void* pnp;  // phi_n o psi; the WARP march: phi_n itself (tsdf-only, extents d), sampled at psi here
     const void* pg;   // phi_global
     const void* psi;
     void* nU;
@@ -115,8 +115,15 @@ SOBFU_DEV void st3_system(float* p, const float4& v);
 // NTL: streaming (nontemporal) hints, kNT or 0 -- for grids whose state exceeds the 256 MiB Infinity Cache; 0 for cache-resident
 // ones (multi-GPU tiles, small grids), where the hints keep the data the NEXT launch reads out of the cache (2 x 2 x 2 tile of
 // 256^3: 54.4 -> 48.8 us per iteration without them)
-template <int RPT, int WY, bool COMPACT, int NTL, bool PUSHABLE = false>
+// WARP (compact format, one GPU): there is no phi_n o psi stream.  a.pnp is phi_n, and F of every cell -- the lane's rows and the
+// halo cells -- is sampled from that cell's psi, interp_tsdf_only32 op for op: the value pass B used to store, the same bits.  The
+// rows' psi is requested TWO planes ahead, so that the eight corner loads of plane z+1 go out at the top of step z, next to the
+// step's other requests, and are folded into fn behind the barrier.  The halo's corners of plane z+1 are requested behind the
+// step's stores and staged at the next step (carrying them across the barrier too would need more than 64 VGPR).  The prologue
+// samples planes zb-1 and zb (and zb's halo) in place.
+template <int RPT, int WY, bool COMPACT, int NTL, bool PUSHABLE = false, bool WARP = false>
 SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRegs& gate, const PushDst* pd = nullptr) {
+    static_assert(!WARP || (COMPACT && !PUSHABLE), "the warping march exists for the single-GPU compact format");
     constexpr int TY = RPT * WY, LW = TX + 2, LH = TY + 2;
     constexpr int NXH = (2 * TY + TX - 1) / TX;  // row-tasks for the two lane-halo columns
     constexpr int NTASK = 2 + NXH, TPW = (NTASK + WY - 1) / WY;
@@ -161,7 +168,36 @@ SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRe
     float hf[TPW];
     float bg[RPT], bgn[RPT];  // phi_global of plane z, requested one step ahead like everything else (no same-step round trip)
     auto ld_bg = [&](size_t i) { return (NTL >= 3 && COMPACT) ? __builtin_nontemporal_load((const float*) a.pg + i) : ldt<COMPACT>(a.pg, i); };
-    {
+    // WARP: psi of plane z+2 (rows); the corner loads of the rows of plane z+1 in flight across the barrier
+    float4 pnn[WARP ? RPT : 1];
+    Gather8 gr[WARP ? RPT : 1];
+    const float* phi = (const float*) a.pnp;
+    // WARP: buffer addressing (arrays below 4 GiB: checked at launch) -- a 32-bit cell offset per lane and the plane as a scalar byte
+    // offset, instead of 64-bit lane addresses: the registers the gathers in flight need
+    const uint32_t plane4 = (uint32_t) plane * 4u, cells = (uint32_t) plane * (uint32_t) d.z;
+    const __amdgpu_buffer_rsrc_t r_psi = buf_rsrc(a.psi, cells * 12u), r_pg = buf_rsrc(a.pg, cells * 4u), r_nu = buf_rsrc(a.nU, cells * 12u);
+    uint32_t wo[RPT], who[TPW];  // in-plane cell index of the rows / the halo cells
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) wo[r] = (uint32_t) off[r];
+#pragma unroll
+    for (int k = 0; k < TPW; ++k) who[k] = (uint32_t) h_off[k];
+    auto ld_psi_w = [&](uint32_t c, int zz) { return buf_ld3(r_psi, 12u * c, 3u * (uint32_t) zz * plane4); };
+    auto ld_bg_w  = [&](uint32_t c, int zz) {
+        return __uint_as_float(NTL >= 3 ? __builtin_amdgcn_raw_buffer_load_b32(r_pg, (int) (4u * c), (int) ((uint32_t) zz * plane4), 2)
+                                        : __builtin_amdgcn_raw_buffer_load_b32(r_pg, (int) (4u * c), (int) ((uint32_t) zz * plane4), 0));
+    };
+    if constexpr (WARP) {
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            pm[r] = ld_psi_w(wo[r], max(zb - 1, 0));
+            pc[r] = ld_psi_w(wo[r], zb);
+            pn[r] = ld_psi_w(wo[r], min(zb + 1, d.z - 1));
+            bg[r] = ld_bg_w(wo[r], zb);
+        }
+#pragma unroll
+        for (int k = 0; k < TPW; ++k)
+            if (h_on[k]) hp[k] = ld_psi_w(who[k], zb);
+    } else {
         const size_t zm = (size_t) max(zb - 1, 0) * plane, zc0 = (size_t) zb * plane;
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
@@ -179,6 +215,17 @@ SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRe
             }
     }
     if (gate_decide(gate, a.prev_slots, a.max_update_norm)) return;
+    if constexpr (WARP) {  // F of planes zb-1, zb and of zb's halo, sampled in place -- the halo's corners behind the rows' (registers)
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            fm[r] = interp_tsdf_only32(phi, d, pm[r].x, pm[r].y, pm[r].z);
+            fc[r] = interp_tsdf_only32(phi, d, pc[r].x, pc[r].y, pc[r].z);
+            asm volatile("" ::"v"(fm[r]), "v"(fc[r]) : "memory");
+        }
+#pragma unroll
+        for (int k = 0; k < TPW; ++k)
+            if (h_on[k]) hf[k] = interp_tsdf_only32(phi, d, hp[k].x, hp[k].y, hp[k].z);
+    }
 
     const bool ulo = (u == 0), uhi = (u == tg.DU - 1);
     for (int z = zb; z < ze; ++z) {
@@ -193,6 +240,20 @@ SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRe
             if (h_on[k]) t_psi[buf][h_lr[k]][h_lc[k]] = make_float4(hp[k].x, hp[k].y, hp[k].z, hf[k]);
         // prefetch plane z+1 (main) and the halo of plane z+1
         const size_t zn = (size_t) min(z + 1, d.z - 1) * plane, zcur = (size_t) z * plane;
+        if constexpr (WARP) {  // the corners of plane z+1 (its psi is here since the step before), psi of plane z+2, the halo's psi of z+1
+#pragma unroll
+            for (int r = 0; r < RPT; ++r) gr[r] = gather_issue32(phi, d, pn[r].x, pn[r].y, pn[r].z);
+#pragma unroll
+            for (int r = 0; r < RPT; ++r) {
+                pnn[r] = ld_psi_w(wo[r], min(z + 2, d.z - 1));
+                if (z + 1 < ze) bgn[r] = ld_bg_w(wo[r], z + 1);
+            }
+            if (z + 1 < ze) {
+#pragma unroll
+                for (int k = 0; k < TPW; ++k)
+                    if (h_on[k]) hp[k] = ld_psi_w(who[k], z + 1);
+            }
+        } else {
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
             pn[r] = ldv<COMPACT>(a.psi, zn + off[r]);
@@ -207,7 +268,12 @@ SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRe
                     hf[k] = ldt<COMPACT>(a.pnp, zn + h_off[k]);
                 }
         }
+        }
         __syncthreads();
+        if constexpr (WARP) {
+#pragma unroll
+            for (int r = 0; r < RPT; ++r) fn[r] = gather_finish(gr[r]);
+        }
 
         const bool zlo = (z == 0), zhi = (z == d.z - 1);
 #pragma unroll
@@ -233,7 +299,8 @@ SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRe
                         st3_system(pd->base + 3 * j, o);
                     }
                     if (z >= pd->lz0 && z < pd->lz1) stv<COMPACT>(a.nU, i, o);  // ... and where the box stands in for the owned block, home too
-                } else stv<COMPACT>(a.nU, i, o);
+                } else if constexpr (WARP) buf_st3(r_nu, 12u * wo[r], 3u * (uint32_t) z * plane4, o);
+                else stv<COMPACT>(a.nU, i, o);
             }
         }
         // shift the z pipeline
@@ -244,18 +311,25 @@ SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRe
             fm[r] = fc[r];
             fc[r] = fn[r];
             bg[r] = bgn[r];
+            if constexpr (WARP) pn[r] = pnn[r];
+        }
+        if constexpr (WARP) {  // F of the halo of plane z+1, staged at the next step: its corners are requested behind this step's stores
+#pragma unroll
+            for (int k = 0; k < TPW; ++k)
+                if (h_on[k] && z + 1 < ze) hf[k] = interp_tsdf_only32(phi, d, hp[k].x, hp[k].y, hp[k].z);
         }
     }
 }
 
 
-template <int RPT, int WY, bool COMPACT, int NTL>
-__global__ void __launch_bounds__(TX* WY) fused_potential_gradient_kernel(PassAArgs a) {
+// WARP: a.c.pnp is phi_n (see pass_a_march); its register budget is held at 64 VGPR, 8 waves per SIMD: 4 workgroups per CU, like the others
+template <int RPT, int WY, bool COMPACT, int NTL, bool WARP = false>
+__global__ void __launch_bounds__(TX* WY, WARP ? 8 : 1) fused_potential_gradient_kernel(PassAArgs a) {
     const GateRegs gate = gate_load(a.c.prev_slots, 1);
     const unsigned t    = xcd_swizzle(blockIdx.x, (unsigned) a.boxes.first[a.boxes.n]);
     int first;
     const Box b = find_box(a.boxes, t, first);
-    pass_a_march<RPT, WY, COMPACT, NTL>(a.c, geom_in_box(b, t, first, a.c.d, RPT * WY), gate);
+    pass_a_march<RPT, WY, COMPACT, NTL, false, WARP>(a.c, geom_in_box(b, t, first, a.c.d, RPT * WY), gate);
 }
 
 // ---- pass A of a multi-GPU TILE: the halo exchange is part of the launch ---------------------------------------------------

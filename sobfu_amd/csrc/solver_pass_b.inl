@@ -263,12 +263,16 @@ SOBFU_DEV void pass_b_march_pipe(const PassBArgs& a, const TileGeom& tg, const G
 // REAL.  hipcc drops the nontemporal flag of __builtin_nontemporal_load / _store on the 4-byte-aligned 12-byte vector type (found in the
 // ISA in round 5: `global_load_dwordx3 ... off` without `nt`, while the 4-byte phi_n o psi store carries it); the buffer instructions
 // take the hint as an operand.
-template <int RPT, int WY, bool WRITE_UPDATES, bool COMPACT, bool DIRECT_OK, bool IDX32 = false, int HL = 0, int NTL = kNT, bool PIPE = false, bool NTBUF = false>
+// APPLY = false (plain march of the compact single-GPU loop): no phi_n gather and no phi_n o psi store -- the next pass A samples phi_n
+// at psi itself (pass_a_march, WARP).
+template <int RPT, int WY, bool WRITE_UPDATES, bool COMPACT, bool DIRECT_OK, bool IDX32 = false, int HL = 0, int NTL = kNT, bool PIPE = false, bool NTBUF = false,
+          bool APPLY = true>
 // (the API-format instantiations -- 16-byte psi / nabla_U, 8-byte volumes: the launcher-level entry point and set_compact(0) -- get the
 // 128-VGPR budget: at 80 they spilled 12 - 28 B/lane to scratch)
 __global__ void __launch_bounds__(TX* WY, (PIPE || !COMPACT) ? SOBFU_MINW_PIPE : SOBFU_MINW_B) fused_smooth_update_apply_kernel(PassBArgs a) {
     static_assert(!NTBUF || (COMPACT && !PIPE && NTL >= 1), "NTBUF: the plain march of the compact format with streaming hints");
     static_assert(!PIPE || (RPT == 1 && COMPACT && IDX32 && !WRITE_UPDATES && HL == 0), "the pipelined march exists for the compact solver format");
+    static_assert(APPLY || (COMPACT && !DIRECT_OK && !PIPE && !WRITE_UPDATES), "only the plain march of the compact single-GPU loop leaves the warp to pass A");
     constexpr int R = 3, TY = RPT * WY, LW = TX + 2 * R, LH = TY + 2 * R;
     static_assert(HL == 0 || HL >= 2, "the halo-lead FIFO needs a lead of >= 2 planes (a lead of 1 is the register path, HL = 0)");
     constexpr int NXH = (2 * R * TY + TX - 1) / TX;  // row-tasks for the 2R lane-halo columns
@@ -491,14 +495,16 @@ __global__ void __launch_bounds__(TX* WY, (PIPE || !COMPACT) ? SOBFU_MINW_PIPE :
                 else stvb<COMPACT>((char*) a.psi_out + zcur * VB, off[r], p, NTL >= 1);
                 if (WRITE_UPDATES) *(float4*) ((char*) a.updates + zcur * 16 + (size_t) (offT[r] / TB * 16u)) = uu;
                 // apply_kernel (vector_fields.cu:95-98)
-                if (COMPACT) {
-                    const float f = IDX32 ? interp_tsdf_only32((const float*) a.phi_n, a.pd, p.x, p.y, p.z)
-                                          : interp_tsdf_only((const float*) a.phi_n, a.pd, p.x, p.y, p.z);
-                    float* fo = (float*) ((char*) a.pnp + zcur * TB + (size_t) offT[r]);
-                    if (NTL >= 1) __builtin_nontemporal_store(f, fo);
-                    else *fo = f;
+                if constexpr (APPLY) {
+                    if (COMPACT) {
+                        const float f = IDX32 ? interp_tsdf_only32((const float*) a.phi_n, a.pd, p.x, p.y, p.z)
+                                              : interp_tsdf_only((const float*) a.phi_n, a.pd, p.x, p.y, p.z);
+                        float* fo = (float*) ((char*) a.pnp + zcur * TB + (size_t) offT[r]);
+                        if (NTL >= 1) __builtin_nontemporal_store(f, fo);
+                        else *fo = f;
+                    }
+                    else *(float2*) ((char*) a.pnp + zcur * TB + (size_t) offT[r]) = interp_tsdf((const float2*) a.phi_n, a.pd, p.x, p.y, p.z);
                 }
-                else *(float2*) ((char*) a.pnp + zcur * TB + (size_t) offT[r]) = interp_tsdf((const float2*) a.phi_n, a.pd, p.x, p.y, p.z);
             }
         }
 #pragma unroll
