@@ -9,9 +9,20 @@
 // solved); --screenshots-detailed adds a second row -- phi_n, phi_global_psi_inv / phi_global, phi_n_psi (demo.cpp:445-456).  The
 // views are drawn from the depth camera (the pose and intrinsics the frames are integrated with) with a headlight at its origin, not
 // from the reference viewer's camera at z = max + 3 (demo.cpp:403,467): with the depth camera the live panel lines up with the input.
+// Colour (opt-in): --data DIR reads a dataset laid out as the reference app expects (demo.cpp:177-197): sorted DIR/depth/*, DIR/color/*
+// when present (8-bit PNG or binary PPM, registered to depth) and DIR/omask/* when present (a mask zeroes the depth where it is 0,
+// demo.cpp:314-328); --synthetic N --textured gives the sphere a texture that moves with it.  With colour frames the canonical colour is
+// fused through psi: --mesh writes per-vertex colours for phi_global and phi_global_psi_inv, the phi_global / phi_global_psi_inv
+// screenshot panels are coloured (the live panels of --screenshots-detailed stay grey) and --dump adds colour_global.npy (Z, Y, X, 4)
+// uint8 (b, g, r, weight).  Without colour frames every output is the geometry-only one.
 //
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR] [--no-stats]
-//                  [--screenshots DIR [--screenshots-detailed]] (--synthetic FRAMES [--shift DX] | frame0.pgm frame1.pgm ...)
+//                  [--screenshots DIR [--screenshots-detailed]]
+//                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | frame0.pgm frame1.pgm ...)
+#include <dirent.h>
+#include <sys/stat.h>
+
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -33,6 +44,40 @@ static void render_sphere(double cx, double cy, double cz, double r, const kfusi
         }
 }
 
+// BGRA colour frame of the same sphere: a pixel that hits it takes a fixed function of the direction n from the centre to the hit point
+// (the texture moves with the sphere); a miss is black.  Same convention as sobfu_amd/synthetic.py::render_textured_sphere_colour.
+static void render_sphere_colour(double cx, double cy, double cz, double r, const kfusion::Intr& in, int rows, int cols, std::vector<uint8_t>& out) {
+    out.assign((size_t) rows * cols * 4, 0);
+    for (int v = 0; v < rows; ++v)
+        for (int u = 0; u < cols; ++u) {
+            double dx = (u - (double) in.cx) / (double) in.fx, dy = (v - (double) in.cy) / (double) in.fy;
+            double a = dx * dx + dy * dy + 1.0, b = -2.0 * (dx * cx + dy * cy + cz), c = cx * cx + cy * cy + cz * cz - r * r;
+            double disc = b * b - 4.0 * a * c;
+            if (disc < 0) continue;
+            const double z = (-b - std::sqrt(disc)) / (2.0 * a);
+            const double nx = (z * dx - cx) / r, ny = (z * dy - cy) / r;
+            uint8_t* o = &out[((size_t) v * cols + u) * 4];
+            o[2] = (uint8_t) std::nearbyint(127.5 * (1.0 + nx));
+            o[1] = (uint8_t) std::nearbyint(127.5 * (1.0 + ny));
+            o[0] = (uint8_t) std::nearbyint(127.5 * (1.0 + std::sin(12.0 * nx) * std::cos(12.0 * ny)));
+            o[3] = 255;
+        }
+}
+
+// sorted regular files of a directory; false when it does not exist
+static bool list_dir(const std::string& dir, std::vector<std::string>& out) {
+    DIR* d = opendir(dir.c_str());
+    if (!d) return false;
+    while (dirent* e = readdir(d)) {
+        const std::string path = dir + "/" + e->d_name;
+        struct stat st;
+        if (e->d_name[0] != '.' && stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode)) out.push_back(path);
+    }
+    closedir(d);
+    std::sort(out.begin(), out.end());
+    return true;
+}
+
 static void stats(const char* name, kfusion::cuda::TsdfVolume& v) {
     cv::Vec3i d = v.getDims();
     std::vector<float2> h((size_t) d[0] * d[1] * d[2]);
@@ -51,6 +96,7 @@ struct Screenshots {
     int rows = 0, cols = 0;
     kfusion::cuda::Cloud points;
     kfusion::cuda::Normals normals;
+    kfusion::cuda::Image colours;  // sampled colour of a coloured panel
     kfusion::cuda::Image image;  // (2 or 1 panel rows) x 2 panels
     std::vector<kfusion::RGB> bgra;
     std::vector<uint8_t> rgb;
@@ -63,19 +109,26 @@ struct Screenshots {
         bgra.resize((size_t) image.rows() * image.cols());
         rgb.resize(bgra.size() * 3);
     }
-    // shades `v` (or leaves the panel black when v is null) into panel (pr, pc)
-    void panel(kfusion::cuda::TsdfVolume* v, const kfusion::Intr& intr, int pr, int pc) {
+    // shades `v` (or leaves the panel black when v is null) into panel (pr, pc), in colour when `colour` is given
+    void panel(kfusion::cuda::TsdfVolume* v, const kfusion::Intr& intr, int pr, int pc, const kfusion::cuda::ColourVolume* colour = nullptr) {
         if (!v) return;
         v->raycast(cv::Affine3f::Identity(), intr, points, normals);  // the depth camera (SobFusion's camera_pose_)
         uint8_t* dst = (uint8_t*) image.ptr() + (size_t) pr * rows * image.step() + (size_t) pc * cols * sizeof(kfusion::RGB);
+        if (colour) {
+            colour->sample(points, normals, cv::Affine3f::Identity().inv() * v->getPose(), v->getVoxelSize(), colours);
+            sobfuSafeCall(sobfu_hip_render_colour((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
+                                                  (const uint8_t*) colours.ptr(), (int) colours.step(), rows, cols, 0.f, 0.f, 0.f, dst,
+                                                  (int) image.step(), nullptr));
+            return;
+        }
         sobfuSafeCall(sobfu_hip_render_image((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
                                              rows, cols, 0.f, 0.f, 0.f, dst, (int) image.step(), nullptr));  // headlight at the camera
     }
     bool write(int frame, SobFusion& fusion, bool solved, const kfusion::Intr& intr) {
         if (points.empty()) create(fusion.getParams().rows, fusion.getParams().cols);
         sobfuSafeCall(hipMemset2D(image.ptr(), image.step(), 0, (size_t) image.cols() * sizeof(kfusion::RGB), image.rows()));
-        panel(fusion.phi_global.get(), intr, detailed ? 1 : 0, 0);
-        panel(solved ? fusion.phi_global_psi_inv.get() : nullptr, intr, 0, 1);
+        panel(fusion.phi_global.get(), intr, detailed ? 1 : 0, 0, fusion.colour_global.get());
+        panel(solved ? fusion.phi_global_psi_inv.get() : nullptr, intr, 0, 1, solved ? fusion.get_colour_global_psi_inv().get() : nullptr);
         if (detailed) {
             panel(frame > 0 ? fusion.phi_n.get() : nullptr, intr, 0, 0);
             panel(solved ? fusion.phi_n_psi.get() : nullptr, intr, 1, 1);
@@ -95,7 +148,8 @@ struct Screenshots {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] (--synthetic FRAMES [--shift DX] | depth files...)\n", argv[0]);
+                    "[--screenshots DIR [--screenshots-detailed]] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
+                    argv[0]);
         return 2;
     }
     Params p;
@@ -106,7 +160,8 @@ int main(int argc, char** argv) {
     }
     int synthetic = 0;
     double shift = 0.005;
-    std::string dump, mesh_dir;
+    bool textured = false;
+    std::string dump, mesh_dir, data_dir;
     Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
     std::vector<std::string> files;
@@ -118,6 +173,8 @@ int main(int argc, char** argv) {
         else if (a == "--dims" && i + 1 < argc) { int n = std::atoi(argv[++i]); p.volume_dims = cv::Vec3i::all(n); }
         else if (a == "--synthetic" && i + 1 < argc) synthetic = std::atoi(argv[++i]);
         else if (a == "--shift" && i + 1 < argc) shift = std::atof(argv[++i]);
+        else if (a == "--textured") textured = true;
+        else if (a == "--data" && i + 1 < argc) data_dir = argv[++i];
         else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
         else if (a == "--mesh" && i + 1 < argc) mesh_dir = argv[++i];
         else if (a == "--no-stats") print_stats = false;
@@ -133,26 +190,71 @@ int main(int argc, char** argv) {
         p.tsdf_trunc_dist = tv * p.voxel_sizes()[0];
         p.eta = ev * p.voxel_sizes()[0];
     }
+    std::vector<std::string> colour_files, mask_files;
+    if (!data_dir.empty()) {  // demo.cpp:177-197, with a colour-less dataset allowed
+        if (!files.empty() || synthetic > 0) {
+            std::printf("--data excludes --synthetic and depth files\n");
+            return 2;
+        }
+        if (!list_dir(data_dir + "/depth", files) || files.empty()) {
+            std::printf("no depth frames in %s/depth\n", data_dir.c_str());
+            return 2;
+        }
+        if (list_dir(data_dir + "/color", colour_files) && colour_files.size() != files.size()) {
+            std::printf("%s: %zu depth frames but %zu colour frames\n", data_dir.c_str(), files.size(), colour_files.size());
+            return 2;
+        }
+        if (list_dir(data_dir + "/omask", mask_files) && mask_files.size() != files.size()) {
+            std::printf("%s: %zu depth frames but %zu masks\n", data_dir.c_str(), files.size(), mask_files.size());
+            return 2;
+        }
+    }
+    if (textured && synthetic <= 0) {
+        std::printf("--textured needs --synthetic\n");
+        return 2;
+    }
+    const bool coloured = textured || !colour_files.empty();
     kfusion::cuda::setDevice(0);
     kfusion::cuda::printShortCudaDeviceInfo(0);
     SobFusion fusion(p);
     const int nframes = synthetic > 0 ? synthetic : (int) files.size();
-    std::vector<uint16_t> img;
+    std::vector<uint16_t> img, mask;
+    std::vector<uint8_t> bgra;
     kfusion::cuda::Depth depth;
+    kfusion::cuda::Image colour;
     double time_ms = 0.0;
     for (int n = 0; n < nframes; ++n) {
-        if (synthetic > 0) render_sphere(shift * n, 0.0, 0.75, 0.1, p.intr, p.rows, p.cols, img);
-        else {
+        if (synthetic > 0) {
+            render_sphere(shift * n, 0.0, 0.75, 0.1, p.intr, p.rows, p.cols, img);
+            if (textured) render_sphere_colour(shift * n, 0.0, 0.75, 0.1, p.intr, p.rows, p.cols, bgra);
+        } else {
             std::string why;
             if (!sobfu_amd::read_depth(files[n], p.rows, p.cols, img, &why)) {
                 std::printf("cannot read depth frame %s: %s\n", files[n].c_str(), why.c_str());
                 return 2;
             }
+            if (!mask_files.empty()) {  // depth.copyTo(depth_masked, mask) (demo.cpp:314-317): masks are grey PNG / PGM / raw, or colour
+                std::vector<uint8_t> cm;
+                if (sobfu_amd::read_depth(mask_files[n], p.rows, p.cols, mask, &why)) {
+                    for (size_t i = 0; i < img.size(); ++i) if (mask[i] == 0) img[i] = 0;
+                } else if (sobfu_amd::read_colour(mask_files[n], p.rows, p.cols, cm, &why)) {
+                    for (size_t i = 0; i < img.size(); ++i) if ((cm[4 * i] | cm[4 * i + 1] | cm[4 * i + 2]) == 0) img[i] = 0;
+                } else {
+                    std::printf("cannot read mask %s: %s\n", mask_files[n].c_str(), why.c_str());
+                    return 2;
+                }
+            }
+            if (!colour_files.empty() && !sobfu_amd::read_colour(colour_files[n], p.rows, p.cols, bgra, &why)) {
+                std::printf("cannot read colour frame %s: %s\n", colour_files[n].c_str(), why.c_str());
+                return 2;
+            }
         }
         depth.upload(img.data(), (size_t) p.cols * sizeof(uint16_t), p.rows, p.cols);  // demo.cpp:327-329
+        if (coloured) colour.upload(bgra.data(), (size_t) p.cols * 4, p.rows, p.cols);
         {
             kfusion::SampledScopeTime fps(time_ms);  // demo.cpp:331 -- "avg. frame time" every 34 frames
-            fusion(depth);
+            if (coloured) fusion(depth, colour);
+            else fusion(depth);
         }
         if (print_stats) stats("phi_global", *fusion.phi_global);
         auto save_mesh = [&](const char* name, const sobfu_amd::TriangleMesh& m) {  // demo.cpp:236-246 (name_frame.vtk)
@@ -203,6 +305,11 @@ int main(int argc, char** argv) {
         if (fusion.phi_n) volume("phi_n", *fusion.phi_n);
         if (fusion.phi_n_psi) volume("phi_n_psi", *fusion.phi_n_psi);
         if (fusion.phi_global_psi_inv) volume("phi_global_psi_inv", *fusion.phi_global_psi_inv);
+        if (fusion.colour_global) {
+            std::vector<kfusion::RGB> c(n);
+            fusion.colour_global->data().download(c.data());
+            if (!sobfu_amd::write_npy(dump + "/colour_global.npy", (const uint8_t*) c.data(), {Z, Y, X, 4})) std::printf("cannot write colour_global\n");
+        }
     }
     return 0;
 }

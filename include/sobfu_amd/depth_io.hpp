@@ -5,6 +5,9 @@
 //                  maxval > 255 (big-endian samples), or raw little-endian uint16 of rows*cols pixels -- sniffed by magic
 //   write_npy      NumPy .npy v1.0, little-endian float32, C order
 //   write_png_rgb  8-bit RGB PNG (colour type 2, filter 0 on every row, zlib-compressed): the headless app's screenshots
+//   read_colour    colour frames -> BGRA8 (alpha 255): 8-bit PNG of colour type 2 (RGB), 6 (RGBA, alpha dropped) or 0 (grey), or binary
+//                  PPM "P6" with maxval <= 255 (samples unscaled).  Malformed input returns false with the reason, never aborts.
+//   write_npy      (uint8 overload) NumPy .npy v1.0, uint8, C order
 // Link with -lz.
 #pragma once
 #include <zlib.h>
@@ -127,6 +130,148 @@ inline bool read_depth(const std::string& path, int rows, int cols, std::vector<
     out.resize(npix);
     std::memcpy(out.data(), file.data(), 2 * npix);  // little-endian host
     return true;
+}
+
+namespace detail {
+inline bool read_file(const std::string& path, std::vector<unsigned char>& file) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return false;
+    unsigned char buf[1 << 16];
+    size_t n;
+    while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + n);
+    std::fclose(f);
+    return true;
+}
+}  // namespace detail
+
+// 8-bit non-interlaced PNG of colour type 0, 2 or 6 -> rows x cols BGRA (alpha 255)
+inline bool read_colour_png(const std::vector<unsigned char>& file, int rows, int cols, std::vector<uint8_t>& bgra, std::string* why = nullptr) {
+    auto fail = [&](const char* m) { if (why) *why = m; return false; };
+    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (file.size() < 8 + 25 || std::memcmp(file.data(), sig, 8) != 0) return fail("not a PNG file");
+    size_t pos = 8;
+    uint32_t w = 0, h = 0;
+    int depth = 0, color = -1, interlace = 0;
+    bool ihdr = false;
+    std::vector<unsigned char> idat;
+    while (pos < file.size()) {
+        if (file.size() - pos < 12) return fail("truncated chunk");
+        const uint32_t len = detail::be32(&file[pos]);
+        const char* type = (const char*) &file[pos + 4];
+        if ((size_t) len > file.size() - pos - 12) return fail("truncated chunk");
+        const unsigned char* body = &file[pos + 8];
+        if (detail::be32(body + len) != (uint32_t) crc32(crc32(0L, Z_NULL, 0), &file[pos + 4], len + 4)) return fail("chunk CRC mismatch");
+        if (!std::memcmp(type, "IHDR", 4)) {
+            if (len != 13) return fail("bad IHDR chunk");
+            w = detail::be32(body); h = detail::be32(body + 4); depth = body[8]; color = body[9]; interlace = body[12];
+            ihdr = true;
+        } else if (!std::memcmp(type, "IDAT", 4)) {
+            idat.insert(idat.end(), body, body + len);
+        } else if (!std::memcmp(type, "IEND", 4)) {
+            break;
+        }
+        pos += 12 + (size_t) len;
+    }
+    if (!ihdr) return fail("no IHDR chunk");
+    if (depth != 8 || (color != 0 && color != 2 && color != 6)) return fail("only 8-bit grey, RGB or RGBA PNG colour frames are supported");
+    if (interlace != 0) return fail("interlaced PNG is not supported");
+    if ((int64_t) w != cols || (int64_t) h != rows) return fail("image size differs from the configured rows x cols");
+    const size_t bpp = color == 0 ? 1 : color == 2 ? 3 : 4, stride = (size_t) w * bpp;
+    std::vector<unsigned char> raw((stride + 1) * h);
+    uLongf got = (uLongf) raw.size();
+    if (idat.empty() || uncompress(raw.data(), &got, idat.data(), (uLong) idat.size()) != Z_OK || got != raw.size()) return fail("inflate failed");
+    bgra.assign((size_t) rows * cols * 4, 0);
+    std::vector<unsigned char> prev(stride, 0), cur(stride);
+    for (uint32_t y = 0; y < h; ++y) {
+        const unsigned char* line = &raw[(stride + 1) * y];
+        const int filter = line[0];
+        if (filter > 4) return fail("bad row filter");
+        for (size_t i = 0; i < stride; ++i) {
+            const int a = i >= bpp ? cur[i - bpp] : 0, b = prev[i], c = i >= bpp ? prev[i - bpp] : 0, x = line[1 + i];
+            int v = x;
+            if (filter == 1) v = x + a;
+            else if (filter == 2) v = x + b;
+            else if (filter == 3) v = x + ((a + b) >> 1);
+            else if (filter == 4) v = x + detail::paeth(a, b, c);
+            cur[i] = (unsigned char) v;
+        }
+        for (uint32_t x = 0; x < w; ++x) {
+            uint8_t* o = &bgra[((size_t) y * cols + x) * 4];
+            const unsigned char* p = &cur[x * bpp];
+            o[0] = bpp == 1 ? p[0] : p[2], o[1] = bpp == 1 ? p[0] : p[1], o[2] = p[0], o[3] = 255;
+        }
+        prev.swap(cur);
+    }
+    return true;
+}
+
+inline bool read_colour(const std::string& path, int rows, int cols, std::vector<uint8_t>& bgra, std::string* why = nullptr) {
+    auto fail = [&](const char* m) { if (why) *why = m; return false; };
+    std::vector<unsigned char> file;
+    if (!detail::read_file(path, file)) return fail("cannot open file");
+    if (file.size() >= 8 && file[0] == 0x89 && file[1] == 'P' && file[2] == 'N' && file[3] == 'G') return read_colour_png(file, rows, cols, bgra, why);
+    if (file.size() >= 2 && file[0] == 'P' && file[1] == '6') {  // header as read_depth's PGM: "P6" width height maxval, '#' comments
+        size_t pos = 2;
+        int field[3] = {0, 0, 0};
+        for (int k = 0; k < 3; ++k) {
+            for (;;) {
+                while (pos < file.size() && std::isspace(file[pos])) ++pos;
+                if (pos < file.size() && file[pos] == '#') {
+                    while (pos < file.size() && file[pos] != '\n') ++pos;
+                    continue;
+                }
+                break;
+            }
+            size_t digits = 0;
+            long v = 0;
+            while (pos < file.size() && file[pos] >= '0' && file[pos] <= '9' && digits < 9) {
+                v = v * 10 + (file[pos] - '0');
+                ++pos;
+                ++digits;
+            }
+            if (digits == 0 || (pos < file.size() && file[pos] >= '0' && file[pos] <= '9')) return fail("bad PPM header");
+            field[k] = (int) v;
+        }
+        if (pos >= file.size() || !std::isspace(file[pos])) return fail("bad PPM header");
+        const size_t start = pos + 1, npix = (size_t) rows * cols;
+        if (field[0] != cols || field[1] != rows) return fail("image size differs from the configured rows x cols");
+        if (field[2] < 1 || field[2] > 255) return fail("only 8-bit PPM colour frames are supported");
+        if (file.size() - start < 3 * npix) return fail("truncated PPM");
+        bgra.resize(npix * 4);
+        for (size_t i = 0; i < npix; ++i) {
+            const unsigned char* p = &file[start + 3 * i];
+            bgra[4 * i] = p[2], bgra[4 * i + 1] = p[1], bgra[4 * i + 2] = p[0], bgra[4 * i + 3] = 255;
+        }
+        return true;
+    }
+    return fail("not a PNG or binary PPM file");
+}
+
+namespace detail {
+inline std::string npy_header(const char* descr, const std::vector<size_t>& shape, size_t& n) {
+    std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (";
+    n = 1;
+    for (size_t i = 0; i < shape.size(); ++i) {
+        dict += std::to_string(shape[i]) + (shape.size() == 1 || i + 1 < shape.size() ? "," : "");
+        if (i + 1 < shape.size()) dict += " ";
+        n *= shape[i];
+    }
+    dict += "), }";
+    while ((10 + dict.size() + 1) % 64 != 0) dict += ' ';
+    dict += '\n';
+    return dict;
+}
+}  // namespace detail
+
+// uint8 array, C order, shape given outermost first (e.g. {Z, Y, X, 4} for a colour volume).
+inline bool write_npy(const std::string& path, const uint8_t* data, const std::vector<size_t>& shape) {
+    size_t n = 0;
+    const std::string dict = detail::npy_header("|u1", shape, n);
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char) (dict.size() & 255), (unsigned char) (dict.size() >> 8)};
+    bool ok = std::fwrite(head, 1, 10, f) == 10 && std::fwrite(dict.data(), 1, dict.size(), f) == dict.size() && std::fwrite(data, 1, n, f) == n;
+    return std::fclose(f) == 0 && ok;
 }
 
 // float32 array, C order, shape given outermost first (e.g. {Z, Y, X, 4}).

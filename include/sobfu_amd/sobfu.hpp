@@ -541,6 +541,73 @@ private:
     Affine3f pose_;
     float gradient_delta_factor_, raycast_step_factor_;
 };
+
+// ---- ColourVolume: the canonical colour of the model (no reference counterpart: the reference drops its colour frames) -----------
+// One RGB per voxel, (b, g, r, a) with a = the colour weight (0 = no colour), indexed like the TSDF volumes; the rules are in
+// sobfu_amd/csrc/colour_kernels.hip.  Launches are asynchronous on the null stream, like the TSDF volume's.
+inline int colour_weight_cap(float tsdf_max_weight) { return !(tsdf_max_weight >= 1.f) ? 1 : tsdf_max_weight >= 255.f ? 255 : (int) tsdf_max_weight; }
+class ColourVolume {
+public:
+    explicit ColourVolume(const Vec3i& dims) { create(dims); }
+    void create(const Vec3i& dims) {
+        dims_ = dims;
+        data_.create((size_t) dims_[0] * dims_[1] * dims_[2]);
+        clear();
+    }
+    void clear() { sobfuSafeCall(hipMemsetAsync(data_.ptr(), 0, data_.sizeBytes(), nullptr)); }
+    Vec3i getDims() const { return dims_; }
+    DeviceArray<RGB>& data() { return data_; }
+    const DeviceArray<RGB>& data() const { return data_; }
+    // fuses `image` (BGRA, registered to the depth camera at camera_pose with intr) through `tsdf`, the volume about to be fused, and
+    // psi (device float4 field; NULL = identity)
+    void integrate(const Image& image, const TsdfVolume& tsdf, const float* d_psi, const Affine3f& camera_pose, const Intr& intr) {
+        const Affine3f vol2cam = camera_pose.inv() * tsdf.getPose();  // as TsdfVolume::integrate
+        const Vec3f vs = tsdf.getVoxelSize();
+        const float v[3] = {vs[0], vs[1], vs[2]};
+        sobfuSafeCall(sobfu_hip_integrate_colour((const uint8_t*) image.ptr(), (int) image.step(), image.rows(), image.cols(),
+                                                 tsdf.data().ptr<float>(), d_psi, (uint8_t*) data_.ptr(), dims_[0], dims_[1], dims_[2], v,
+                                                 vol2cam.R, vol2cam.t, intr.fx, intr.fy, intr.cx, intr.cy, colour_weight_cap(tsdf.getMaxWeight()),
+                                                 nullptr));
+    }
+    // out(y) = this(psi_inv(y)), psi_inv a device float4 field of the same dims
+    void apply(const float* d_psi_inv, ColourVolume& out) const {
+        out.create(dims_);
+        sobfuSafeCall(sobfu_hip_apply_colour((const uint8_t*) data_.ptr(), (uint8_t*) out.data_.ptr(), d_psi_inv, dims_[0], dims_[1], dims_[2], nullptr));
+    }
+    // colours at a raycast's points (misses: (0, 0, 0, 0)); vol2cam = the raycast's camera_pose.inv() * volume pose
+    void sample(const Cloud& points, const Normals& normals, const Affine3f& vol2cam, const Vec3f& voxel_size, Image& out) const {
+        out.create(points.rows(), points.cols());
+        const float v[3] = {voxel_size[0], voxel_size[1], voxel_size[2]};
+        sobfuSafeCall(sobfu_hip_sample_colour((const uint8_t*) data_.ptr(), dims_[0], dims_[1], dims_[2], v, vol2cam.R, vol2cam.t, 0,
+                                              (const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
+                                              points.rows(), points.cols(), (uint8_t*) out.ptr(), (int) out.step(), nullptr));
+    }
+    // colours of marching-cubes vertices generated with `mc_pose` (the MarchingCubes pose: volume -> world) -> host, one per vertex
+    void sample_vertices(const DeviceArray<Point>& vertices, const Affine3f& mc_pose, const Vec3f& voxel_size, std::vector<RGB>& out) const {
+        out.clear();
+        const size_t n = vertices.size();
+        if (n == 0) return;
+        DeviceArray<RGB> d(n);
+        const float v[3] = {voxel_size[0], voxel_size[1], voxel_size[2]};
+        sobfuSafeCall(sobfu_hip_sample_colour((const uint8_t*) data_.ptr(), dims_[0], dims_[1], dims_[2], v, mc_pose.R, mc_pose.t, 1,
+                                              (const float*) vertices.ptr(), (int) (n * sizeof(Point)), nullptr, 0, 1, (int) n, (uint8_t*) d.ptr(),
+                                              (int) (n * sizeof(RGB)), nullptr));
+        d.download(out);
+    }
+
+private:
+    DeviceArray<RGB> data_;
+    Vec3i dims_;
+};
+
+// the colour counterpart of renderImage: a hit with colour (colours[.].a != 0) is shaded with renderImage's factor, a hit without
+// colour is renderImage's grey, a miss stays black
+inline void renderImage(const Cloud& points, const Normals& normals, const Image& colours, const Vec3f& light_pose, Image& image) {
+    image.create(normals.rows(), normals.cols());
+    sobfuSafeCall(sobfu_hip_render_colour((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
+                                          (const uint8_t*) colours.ptr(), (int) colours.step(), normals.rows(), normals.cols(), light_pose[0],
+                                          light_pose[1], light_pose[2], (uint8_t*) image.ptr(), (int) image.step(), nullptr));
+}
 }  // namespace cuda
 
 namespace device {
@@ -618,6 +685,7 @@ namespace sobfu_amd {
 // Host triangle soup standing in for pcl::PolygonMesh (three consecutive vertices per polygon, sob_fusion.cpp:160-183)
 struct TriangleMesh {
     std::vector<float4> vertices;
+    std::vector<kfusion::RGB> colours;  // one per vertex when the model has colour, else empty
     size_t triangles() const { return vertices.size() / 3; }
     bool empty() const { return vertices.empty(); }
 };
@@ -632,6 +700,13 @@ inline bool write_vtk(const std::string& path, const TriangleMesh& m) {
     for (size_t i = 0; i < n; ++i) std::fprintf(f, "1 %zu\n", i);
     std::fprintf(f, "\nPOLYGONS %zu %zu\n", nt, 4 * nt);
     for (size_t i = 0; i < nt; ++i) std::fprintf(f, "3 %zu %zu %zu\n", 3 * i, 3 * i + 1, 3 * i + 2);
+    if (!m.colours.empty()) {  // per-vertex colour, VTK's COLOR_SCALARS: r g b as floats in [0, 1]
+        std::fprintf(f, "\nPOINT_DATA %zu\nCOLOR_SCALARS rgb 3\n", n);
+        for (size_t i = 0; i < n; ++i) {
+            const kfusion::RGB c = i < m.colours.size() ? m.colours[i] : kfusion::RGB();
+            std::fprintf(f, "%.6g %.6g %.6g\n", c.r / 255.0, c.g / 255.0, c.b / 255.0);
+        }
+    }
     return std::fclose(f) == 0;
 }
 }  // namespace sobfu_amd
@@ -956,7 +1031,13 @@ public:
         mc->setPose(params.volume_pose);
     }
     Params& getParams() { return params; }
-    bool operator()(const kfusion::cuda::Depth& depth) {
+    // `image` (optional, the reference's signature, sob_fusion.hpp:44): a BGRA colour frame registered to the depth frame, of its size.
+    // An empty image is the geometry-only path (no colour allocation, no colour launch); a colour frame is fused into colour_global
+    // through the TSDF that is fused into phi_global in this frame (phi_global itself on frame 0) and psi on solved frames.
+    bool operator()(const kfusion::cuda::Depth& depth, const kfusion::cuda::Image& image = kfusion::cuda::Image()) {
+        const bool coloured = !image.empty();
+        if (coloured && (image.rows() != depth.rows() || image.cols() != depth.cols()))
+            kfusion::cuda::error("colour frame and depth frame differ in size", __FILE__, __LINE__);
         std::printf("--- FRAME NO. %d ---\n", frame_counter_);
         kfusion::cuda::depthBilateralFilter(depth, filtered_, params.bilateral_kernel_size, params.bilateral_sigma_spatial,
                                             params.bilateral_sigma_depth);                              // sob_fusion.cpp:78
@@ -965,6 +1046,7 @@ public:
         if (frame_counter_ == 0) {                                                                     // :93-123
             phi_global = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
             phi_global->integrate(dists_, camera_pose_, params.intr);
+            if (coloured) integrate_colour(image, *phi_global, nullptr);
             phi_global_psi_inv = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
             phi_n              = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
             phi_n_psi          = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
@@ -976,25 +1058,37 @@ public:
         phi_n->clear();                                                                                // :129
         phi_n->integrate(dists_, camera_pose_, params.intr);                                           // :130
         if (frame_counter_ < params.start_frame) {                                                     // :136-139
+            if (coloured) integrate_colour(image, *phi_n, nullptr);
             phi_global->integrate(*phi_n);
             return ++frame_counter_, true;
         }
         solver->estimate_psi(phi_global, phi_global_psi_inv, phi_n, phi_n_psi, psi, psi_inv);          // :141
+        if (coloured) integrate_colour(image, *phi_n_psi, psi->get_data().ptr<float>());
         phi_global->integrate(*phi_n_psi);                                                             // :142
         return ++frame_counter_, true;
     }
+    // the canonical colour warped to live, colour_global o psi_inv: computed on request (not a per-frame cost); null without colour
+    std::shared_ptr<kfusion::cuda::ColourVolume> get_colour_global_psi_inv() {
+        if (!colour_global) return nullptr;
+        if (!colour_global_psi_inv) colour_global_psi_inv = std::make_shared<kfusion::cuda::ColourVolume>(params.volume_dims);
+        colour_global->apply(psi_inv->get_data().ptr<float>(), *colour_global_psi_inv);
+        return colour_global_psi_inv;
+    }
     std::shared_ptr<sobfu::cuda::DeformationField> getDeformationField() { return psi; }
     // meshes of the four volumes (sob_fusion.cpp:147-183); a host triangle soup replaces pcl::PolygonMesh
-    sobfu_amd::TriangleMesh get_phi_global_mesh() { return get_mesh(phi_global); }
-    sobfu_amd::TriangleMesh get_phi_global_psi_inv_mesh() { return get_mesh(phi_global_psi_inv); }
+    // (with colour, the two canonical-model meshes carry per-vertex colours: colour_global and colour_global o psi_inv)
+    sobfu_amd::TriangleMesh get_phi_global_mesh() { return get_mesh(phi_global, colour_global.get()); }
+    sobfu_amd::TriangleMesh get_phi_global_psi_inv_mesh() { return get_mesh(phi_global_psi_inv, get_colour_global_psi_inv().get()); }
     sobfu_amd::TriangleMesh get_phi_n_mesh() { return get_mesh(phi_n); }
     sobfu_amd::TriangleMesh get_phi_n_psi_mesh() { return get_mesh(phi_n_psi); }
-    sobfu_amd::TriangleMesh get_mesh(cv::Ptr<kfusion::cuda::TsdfVolume> vol) {
+    sobfu_amd::TriangleMesh get_mesh(cv::Ptr<kfusion::cuda::TsdfVolume> vol, const kfusion::cuda::ColourVolume* colour = nullptr) {
         kfusion::cuda::DeviceArray<kfusion::cuda::Point> vertices_buffer;
         kfusion::cuda::DeviceArray<kfusion::cuda::Normal> normals_buffer;
         kfusion::cuda::Surface model = mc->run(*vol, vertices_buffer, normals_buffer);
         kfusion::cuda::waitAllDefaultStream();
-        return convert_to_mesh(model.vertices);
+        sobfu_amd::TriangleMesh m = convert_to_mesh(model.vertices);
+        if (colour) colour->sample_vertices(model.vertices, params.volume_pose, vol->getVoxelSize(), m.colours);  // mc's pose
+        return m;
     }
     static sobfu_amd::TriangleMesh convert_to_mesh(const kfusion::cuda::DeviceArray<kfusion::cuda::Point>& triangles) {
         sobfu_amd::TriangleMesh m;
@@ -1006,8 +1100,13 @@ public:
     cv::Ptr<kfusion::cuda::TsdfVolume> phi_global, phi_global_psi_inv, phi_n, phi_n_psi;
     std::shared_ptr<sobfu::cuda::DeformationField> psi, psi_inv;
     std::shared_ptr<sobfu::cuda::Solver> solver;
+    std::shared_ptr<kfusion::cuda::ColourVolume> colour_global, colour_global_psi_inv;  // null until the first colour frame
 
 private:
+    void integrate_colour(const kfusion::cuda::Image& image, const kfusion::cuda::TsdfVolume& tsdf, const float* d_psi) {
+        if (!colour_global) colour_global = std::make_shared<kfusion::cuda::ColourVolume>(params.volume_dims);
+        colour_global->integrate(image, tsdf, d_psi, camera_pose_, params.intr);
+    }
     int frame_counter_;
     Params params;
     cv::Affine3f camera_pose_;  // fixed to identity, sob_fusion.cpp:33

@@ -322,6 +322,34 @@ int sobfu_hip_render_normals(const float* d_normals, int normals_step, int rows,
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * colour -- the reference's SobFusion::operator()(const Depth&, const Image&) (include/sobfu/sob_fusion.hpp:44) takes a colour image
+ * and drops it (src/sobfu/sob_fusion.cpp:71).  Colour volume: one uchar4 (b, g, r, a) per voxel (kfusion::RGB order, a = colour
+ * weight, 0 = no colour), dense, x fastest, like the TSDF volumes; colour frames: pitched 8-bit BGRA registered to the depth camera.
+ * The rules are in sobfu_amd/csrc/colour_kernels.hip.  Every argument is checked before any device call.
+ * ---------------------------------------------------------------------------------------------------- */
+/* integrate_colour: fuses one colour frame into d_colour through the TSDF about to be fused (d_tsdf: phi_n o psi, phi_n, or phi_global
+ * on frame 0) and psi (NULL = identity): a voxel that is observed in d_tsdf with |tsdf| < 1 takes the pixel psi(x) projects to with
+ * vol2cam = (R row-major, t) and the intrinsics of sobfu_hip_integrate_depth.  Running average c' = rint((c a + c_new) / (a + 1)),
+ * a' = min(a + 1, cap); 1 <= cap <= 255 (the frame driver: min(TSDF_MAX_WEIGHT, 255)). */
+int sobfu_hip_integrate_colour(const uint8_t* d_image, int image_step, int rows, int cols, const float* d_tsdf, const float* d_psi,
+                               uint8_t* d_colour, int X, int Y, int Z, const float voxel_size[3], const float R[9], const float t[3],
+                               float fx, float fy, float cx, float cy, int cap, void* stream);
+/* apply_colour: d_colour_warped(y) = sample(d_colour, psi_inv(y)) -- the colour counterpart of sobfu_hip_apply.  The sampler is
+ * trilinear over the corners with a > 0, renormalised; no corner with colour gives (0, 0, 0, 0), any other result has a = 1. */
+int sobfu_hip_apply_colour(const uint8_t* d_colour, uint8_t* d_colour_warped, const float* d_psi_inv, int X, int Y, int Z, void* stream);
+/* sample_colour: rows x cols float4 points (pitched; a flat list is rows = 1) of a frame whose pose from volume metres is (R, t) -- a
+ * raycast's vol2cam, or the marching-cubes pose with mc_vertices = 1, which undoes the vertices' (x, -y, -z) -- sampled from d_colour
+ * into BGRA d_out.  d_normals (optional): a point whose normal.w == 0 (a raycast miss) gives (0, 0, 0, 0). */
+int sobfu_hip_sample_colour(const uint8_t* d_colour, int X, int Y, int Z, const float voxel_size[3], const float R[9], const float t[3],
+                            int mc_vertices, const float* d_points, int points_step, const float* d_normals, int normals_step, int rows,
+                            int cols, uint8_t* d_out, int out_step, void* stream);
+/* render_colour: a hit with colour (d_colour_image alpha != 0) is colour * (0.2 + 0.8 max(0, n . normalize(light - point))), a hit
+ * without colour is sobfu_hip_render_image's grey, a miss is (0, 0, 0, 0). */
+int sobfu_hip_render_colour(const float* d_points, int points_step, const float* d_normals, int normals_step, const uint8_t* d_colour_image,
+                            int colour_step, int rows, int cols, float lx, float ly, float lz, uint8_t* d_image, int image_step,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * native multi-GPU loop: one rank per z-slab, RCCL halo exchange issued from C++ and overlapped with the interior
  * compute (no reference counterpart; schedule documented in sobfu_amd/tiled.py)
  * ---------------------------------------------------------------------------------------------------- */

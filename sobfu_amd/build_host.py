@@ -58,10 +58,25 @@ def build_png_tool(force: bool = False) -> str:
     return PNG_TOOL
 
 
+COLOUR_TOOL = os.path.join(ROOT, "build", "colour_io_tool")
+
+
+def build_colour_tool(force: bool = False) -> str:
+    """tests/cpp/colour_io_tool.cpp: CPU-only driver of read_colour, the uint8 .npy writer and write_vtk (runs without a GPU)."""
+    src = os.path.join(ROOT, "tests", "cpp", "colour_io_tool.cpp")
+    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp"), os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"),
+            os.path.join(ROOT, "include", "sobfu_hip.h"), os.path.join(HERE, "libsobfu_hip.so")]
+    if force or not os.path.exists(COLOUR_TOOL) or any(os.path.getmtime(COLOUR_TOOL) < os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(COLOUR_TOOL), exist_ok=True)
+        _compile(src, COLOUR_TOOL)
+    return COLOUR_TOOL
+
+
 def build_host(force: bool = False) -> str:
     build_app(force)
     build_io_tool(force)
     build_png_tool(force)
+    build_colour_tool(force)
     src = os.path.join(ROOT, "tests", "cpp", "host_shell_tests.cpp")
     deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
             os.path.join(HERE, "libsobfu_hip.so")]

@@ -410,17 +410,24 @@ def mc_generate_triangles(vol, occ, count, volume_size, R, t, vertices, normals)
                                                      _ptr(vertices), _ptr(normals), C.c_int(vertices.shape[0])), "mc_generate_triangles")
 
 
-def marching_cubes(vol, volume_size, R=np.eye(3), t=(0, 0, 0), max_voxels=2_000_000, max_vertices=None, workspace=None):
-    """kfusion::cuda::MarchingCubes::run (src/kfusion/marching_cubes.cpp:23-79) -> (vertices (n, 4), normals (n, 4)) GPU tensors"""
+def marching_cubes(vol, volume_size, R=np.eye(3), t=(0, 0, 0), max_voxels=2_000_000, max_vertices=None, workspace=None, colour=None):
+    """kfusion::cuda::MarchingCubes::run (src/kfusion/marching_cubes.cpp:23-79) -> (vertices (n, 4), normals (n, 4)) GPU tensors; with a
+    colour volume of the same dims, (vertices, normals, colours (n, 4) uint8 BGRA) -- the vertices' colours, sample_colour's rule"""
     max_vertices = max_vertices or 3 * max_voxels
     occ, count = mc_occupied_voxels(vol, max_voxels, workspace)
     if count == 0:
         e = torch.zeros((0, 4), dtype=torch.float32, device=vol.device)
+        if colour is not None:
+            return e, e.clone(), torch.zeros((0, 4), dtype=torch.uint8, device=vol.device)
         return e, e.clone()
     total = min(mc_offsets(occ, count, workspace), max_vertices // 3 * 3)  # whole triangles only
     v = torch.zeros((max_vertices, 4), dtype=torch.float32, device=vol.device)
     n = torch.zeros_like(v)
     mc_generate_triangles(vol, occ, count, volume_size, R, t, v, n)
+    if colour is not None:
+        Z, Y, X = vol.shape[:3]
+        vs = [float(np.float32(volume_size[i]) / np.float32(d)) for i, d in enumerate((X, Y, Z))]  # the cell size of generateTriangles
+        return v[:total], n[:total], sample_colour(colour, vs, R, t, v[:total], mc_vertices=True)
     return v[:total], n[:total]
 
 
@@ -466,4 +473,77 @@ def render_normals(normals, image=None):
         image = torch.empty((rows, cols, 4), dtype=torch.uint8, device=normals.device)
     check(_lib.lib().sobfu_hip_render_normals(*_image_ptr(normals, torch.float32, 4), C.c_int(rows), C.c_int(cols),
                                               *_image_ptr(image, torch.uint8, 4), _stream()), "render_normals")
+    return image
+
+
+# ---- colour (sobfu_amd/csrc/colour_kernels.hip): a (Z, Y, X, 4) uint8 volume of (b, g, r, weight); BGRA frames ---------------------
+def new_colour_volume(dims, device="cuda"):
+    X, Y, Z = dims
+    return torch.zeros((Z, Y, X, 4), dtype=torch.uint8, device=device)
+
+
+def colour_weight_cap(max_weight):
+    """cap of the colour weight: min((int) TSDF_MAX_WEIGHT, 255), at least 1 (kfusion::cuda::colour_weight_cap)"""
+    w = float(max_weight)
+    return 1 if not w >= 1.0 else 255 if w >= 255.0 else int(w)
+
+
+def _colour_ptr(t):
+    if not (t.dim() == 4 and t.shape[3] == 4):
+        raise ValueError(f"expected a (Z, Y, X, 4) uint8 colour volume, got {tuple(t.shape)}")
+    return _ptr(t, torch.uint8)
+
+
+def integrate_colour(image, tsdf, psi, colour, voxel_size, R, t, intr, cap):
+    """Fuses a (rows, cols, 4) uint8 BGRA frame, registered to the depth camera of vol2cam = (R, t) with intr = (fx, fy, cx, cy), into
+    `colour` through `tsdf` (the volume about to be fused) and `psi` (None = identity)."""
+    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
+    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    if tuple(colour.shape[:3]) != tuple(tsdf.shape[:3]) or (psi is not None and tuple(psi.shape[:3]) != tuple(tsdf.shape[:3])):
+        raise ValueError("colour, tsdf and psi must have the same dims")
+    check(_lib.lib().sobfu_hip_integrate_colour(*_image_ptr(image, torch.uint8, 4), C.c_int(image.shape[0]), C.c_int(image.shape[1]), _ptr(tsdf),
+                                                None if psi is None else _ptr(psi), _colour_ptr(colour), *_xyz(colour),
+                                                _F3(*[float(v) for v in voxel_size]), Rm, tv, _f(intr[0]), _f(intr[1]), _f(intr[2]), _f(intr[3]),
+                                                C.c_int(int(cap)), _stream()), "integrate_colour")
+
+
+def apply_colour(colour, colour_warped, psi_inv):
+    """colour_warped(y) = colour(psi_inv(y)), the renormalised trilinear colour sampler"""
+    if tuple(colour.shape) != tuple(colour_warped.shape) or tuple(psi_inv.shape[:3]) != tuple(colour.shape[:3]):
+        raise ValueError("colour, colour_warped and psi_inv must have the same dims")
+    check(_lib.lib().sobfu_hip_apply_colour(_colour_ptr(colour), _colour_ptr(colour_warped), _ptr(psi_inv), *_xyz(colour), _stream()),
+          "apply_colour")
+    return colour_warped
+
+
+def sample_colour(colour, voxel_size, R, t, points, normals=None, mc_vertices=False, out=None):
+    """Samples `colour` at float4 points of a frame whose pose from volume metres is (R, t): a (rows, cols, 4) raycast image (with its
+    normals: misses give zeros) or an (n, 4) list (marching-cubes vertices with mc_vertices=True and the marching-cubes pose) -> uint8
+    BGRA of the same leading shape; a point with no colour gives (0, 0, 0, 0)."""
+    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
+    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    flat = points.dim() == 2
+    p3 = points.unsqueeze(0) if flat else points
+    if out is None:
+        out = torch.empty(points.shape[:-1] + (4,), dtype=torch.uint8, device=points.device)
+    o3 = out.unsqueeze(0) if out.dim() == 2 else out
+    rows, cols = p3.shape[:2]
+    if rows * cols == 0:
+        return out
+    nrm = (None, C.c_int(0)) if normals is None else _image_ptr(normals.unsqueeze(0) if normals.dim() == 2 else normals, torch.float32, 4)
+    check(_lib.lib().sobfu_hip_sample_colour(_colour_ptr(colour), *_xyz(colour), _F3(*[float(v) for v in voxel_size]), Rm, tv,
+                                             C.c_int(1 if mc_vertices else 0), *_image_ptr(p3, torch.float32, 4), *nrm, C.c_int(rows),
+                                             C.c_int(cols), *_image_ptr(o3, torch.uint8, 4), _stream()), "sample_colour")
+    return out
+
+
+def render_colour(points, normals, colours, light=(0.0, 0.0, 0.0), image=None):
+    """render_image with colour: a hit with colour (colours[..., 3] != 0) -> colour * (0.2 + 0.8 max(0, n . l)), a hit without colour ->
+    render_image's grey, a miss -> zeros; (rows, cols, 4) uint8 BGRA."""
+    rows, cols = normals.shape[:2]
+    if image is None:
+        image = torch.empty((rows, cols, 4), dtype=torch.uint8, device=normals.device)
+    check(_lib.lib().sobfu_hip_render_colour(*_image_ptr(points, torch.float32, 4), *_image_ptr(normals, torch.float32, 4),
+                                             *_image_ptr(colours, torch.uint8, 4), C.c_int(rows), C.c_int(cols), _f(light[0]), _f(light[1]),
+                                             _f(light[2]), *_image_ptr(image, torch.uint8, 4), _stream()), "render_colour")
     return image

@@ -53,3 +53,33 @@ def hash_field(shape, seed=1, scale=1.0):
         h ^= h >> np.uint64(32)
     x = (h & np.uint64(0xFFFFFFFF)).astype(np.float64) / 4294967296.0
     return ((x * 2.0 - 1.0) * scale).astype(np.float32).reshape(shape)
+
+
+def render_textured_sphere_colour(centre, radius, intr, rows=480, cols=640):
+    """(rows, cols, 4) uint8 BGRA colour frame of the sphere of render_sphere_depth: a pixel that hits it takes a fixed function of the
+    direction n from the centre to the hit point, so the texture moves with the sphere -- r = 127.5 (1 + n_x), g = 127.5 (1 + n_y),
+    b = 127.5 (1 + sin(12 n_x) cos(12 n_y)), alpha 255, rounded half to even; a miss is (0, 0, 0, 0).  Float64, the twin of
+    render_sphere_colour in apps/sobfu_headless.cpp."""
+    fx, fy, cx, cy = (np.float64(v) for v in intr)
+    u, v = np.meshgrid(np.arange(cols, dtype=np.float64), np.arange(rows, dtype=np.float64))
+    dx, dy = (u - cx) / fx, (v - cy) / fy
+    c = np.asarray(centre, np.float64)
+    a = dx * dx + dy * dy + 1.0
+    b = -2.0 * (dx * c[0] + dy * c[1] + c[2])
+    cc = float((c * c).sum()) - float(radius) ** 2
+    disc = b * b - 4.0 * a * cc
+    hit = disc >= 0
+    z = (-b - np.sqrt(np.maximum(disc, 0.0))) / (2.0 * a)
+    return np.where(hit[..., None], texture_bgra(*sphere_directions(z * dx, z * dy, c, radius)), 0).astype(np.uint8)
+
+
+def sphere_directions(x, y, centre, radius):
+    """(n_x, n_y) of points (x, y, .) on the sphere, camera frame"""
+    return (x - centre[0]) / radius, (y - centre[1]) / radius
+
+
+def texture_bgra(nx, ny):
+    """the textured sphere's colour at direction (n_x, n_y, .) -> (..., 4) uint8 BGRA"""
+    nx, ny = np.asarray(nx, np.float64), np.asarray(ny, np.float64)
+    ch = [127.5 * (1.0 + np.sin(12.0 * nx) * np.cos(12.0 * ny)), 127.5 * (1.0 + ny), 127.5 * (1.0 + nx), np.full(nx.shape, 255.0)]
+    return np.clip(np.rint(np.stack(ch, -1)), 0, 255).astype(np.uint8)
