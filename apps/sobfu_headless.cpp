@@ -3,7 +3,8 @@
 // dump the fields.  No OpenCV / PCL / VTK: depth frames are 16-bit grayscale PNG (what the reference's datasets ship),
 // binary 16-bit PGM or raw little-endian uint16 files of rows*cols pixels (sobfu_amd/depth_io.hpp), or a built-in
 // synthetic translating sphere.  --dump DIR writes psi, psi_inv and the four TSDF volumes as .npy (float32); --mesh DIR
-// writes marching-cubes meshes of the volumes per frame as legacy-ASCII .vtk polydata (the reference: demo.cpp:236-246).
+// writes marching-cubes meshes of the volumes per frame as legacy-ASCII .vtk polydata (the reference: demo.cpp:236-246); with
+// --mesh-format ply they are indexed meshes instead -- shared vertices with TSDF normals, binary little-endian .ply.
 // --screenshots DIR writes DIR/%06d.png per frame (the reference's --enable-viz, demo.cpp:380-505): raycast + shaded views of the
 // canonical model phi_global (left) and of the canonical model warped to live, phi_global_psi_inv (right; black until a frame has been
 // solved); --screenshots-detailed adds a second row -- phi_n, phi_global_psi_inv / phi_global, phi_n_psi (demo.cpp:445-456).  The
@@ -16,7 +17,7 @@
 // screenshot panels are coloured (the live panels of --screenshots-detailed stay grey) and --dump adds colour_global.npy (Z, Y, X, 4)
 // uint8 (b, g, r, weight).  Without colour frames every output is the geometry-only one.
 //
-//   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR] [--no-stats]
+//   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]]
 //                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | frame0.pgm frame1.pgm ...)
 #include <dirent.h>
@@ -147,7 +148,7 @@ struct Screenshots {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR] [--no-stats] "
+        std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
                     "[--screenshots DIR [--screenshots-detailed]] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
                     argv[0]);
         return 2;
@@ -161,7 +162,7 @@ int main(int argc, char** argv) {
     int synthetic = 0;
     double shift = 0.005;
     bool textured = false;
-    std::string dump, mesh_dir, data_dir;
+    std::string dump, mesh_dir, data_dir, mesh_format = "vtk";
     Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
     std::vector<std::string> files;
@@ -177,10 +178,15 @@ int main(int argc, char** argv) {
         else if (a == "--data" && i + 1 < argc) data_dir = argv[++i];
         else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
         else if (a == "--mesh" && i + 1 < argc) mesh_dir = argv[++i];
+        else if (a == "--mesh-format" && i + 1 < argc) mesh_format = argv[++i];
         else if (a == "--no-stats") print_stats = false;
         else if (a == "--screenshots" && i + 1 < argc) shots.dir = argv[++i];
         else if (a == "--screenshots-detailed") shots.detailed = true;
         else files.push_back(a);
+    }
+    if (mesh_format != "vtk" && mesh_format != "ply") {
+        std::printf("--mesh-format is vtk or ply, not %s\n", mesh_format.c_str());
+        return 2;
     }
     if (argc > 2) {  // --dims changes the voxel size: re-derive the voxel-unit parameters
         std::map<std::string, std::string> kv;
@@ -263,7 +269,20 @@ int main(int argc, char** argv) {
             if (sobfu_amd::write_vtk(path, m)) std::printf("mesh %s: %zu triangles\n", name, m.triangles());
             else std::printf("cannot write %s\n", path.c_str());
         };
-        if (!mesh_dir.empty()) {
+        auto save_ply = [&](const char* name, const sobfu_amd::IndexedMesh& m) {  // name_frame.ply
+            if (m.empty()) return;
+            const std::string path = mesh_dir + "/" + name + "_" + std::to_string(n) + ".ply";
+            if (sobfu_amd::write_ply(path, m)) std::printf("mesh %s: %zu triangles, %zu vertices\n", name, m.triangles(), m.vertices.size());
+            else std::printf("cannot write %s\n", path.c_str());
+        };
+        if (!mesh_dir.empty() && mesh_format == "ply") {
+            save_ply("phi_global", fusion.get_phi_global_indexed_mesh());
+            if (n > 0) save_ply("phi_n", fusion.get_phi_n_indexed_mesh());
+            if (n > 0 && n >= p.start_frame) {
+                save_ply("phi_n_psi", fusion.get_phi_n_psi_indexed_mesh());
+                save_ply("phi_global_psi_inv", fusion.get_phi_global_psi_inv_indexed_mesh());
+            }
+        } else if (!mesh_dir.empty()) {
             save_mesh("phi_global", fusion.get_phi_global_mesh());
             if (n > 0) save_mesh("phi_n", fusion.get_phi_n_mesh());
             if (n > 0 && n >= p.start_frame) {

@@ -646,6 +646,21 @@ inline void generateTriangles(const TsdfVolume& v, const cuda::DeviceArray2D<int
 }
 }  // namespace device
 
+}  // namespace kfusion
+
+namespace sobfu_amd {
+// Indexed triangle mesh (MarchingCubes::run_indexed): shared vertices with per-vertex normals, both float4 (x, -y, -z, 1) like the soup's;
+// faces: three vertex indices per triangle, counter-clockwise seen from outside (the normals' side)
+struct IndexedMesh {
+    std::vector<float4> vertices, normals;
+    std::vector<int> faces;             // 3 per triangle
+    std::vector<kfusion::RGB> colours;  // one per vertex when the model has colour, else empty
+    size_t triangles() const { return faces.size() / 3; }
+    bool empty() const { return faces.empty(); }
+};
+}  // namespace sobfu_amd
+
+namespace kfusion {
 namespace cuda {
 // ---- MarchingCubes (include/kfusion/cuda/marching_cubes.hpp:17-61, src/kfusion/marching_cubes.cpp:14-79) ------------
 class MarchingCubes {
@@ -673,9 +688,40 @@ public:
         return s;
     }
 
+    // indexed (welded) mesh of the volume (sobfu_hip_mc_indexed_*): one vertex per cut edge, per-vertex TSDF normals, faces as int32 x 3;
+    // nothing is truncated.  The device vertices stay in last_indexed_vertices() until the next call (per-vertex colour samples them).
+    sobfu_amd::IndexedMesh run_indexed(const TsdfVolume& volume) {
+        const Vec3i d = volume.getDims();
+        const size_t ws = sobfu_hip_mc_indexed_workspace_bytes(d[0], d[1], d[2]);
+        if (indexed_scratch_.size() < ws) indexed_scratch_.create(ws);
+        const float* vol = volume.data().ptr<float>();
+        int active = 0, nv = 0, nt = 0;
+        sobfuSafeCall(sobfu_hip_mc_indexed_count(nullptr, vol, d[0], d[1], d[2], indexed_scratch_.ptr(), indexed_scratch_.size(), &active, &nv, &nt));
+        std::cout << "no. of active voxels: " << active << std::endl;
+        sobfu_amd::IndexedMesh m;
+        indexed_vertices_.release();
+        if (nt == 0) return m;
+        indexed_vertices_.create(nv);
+        indexed_normals_.create(nv);
+        indexed_faces_.create(3 * (size_t) nt);
+        const Vec3f sz = volume.getSize();
+        sobfuSafeCall(sobfu_hip_mc_indexed_generate(nullptr, vol, d[0], d[1], d[2], sz[0], sz[1], sz[2], pose.R, pose.t, indexed_scratch_.ptr(),
+                                                    indexed_scratch_.size(), (float*) indexed_vertices_.ptr(), (float*) indexed_normals_.ptr(), nv,
+                                                    indexed_faces_.ptr(), nt));
+        indexed_vertices_.download(m.vertices);
+        indexed_normals_.download(m.normals);
+        indexed_faces_.download(m.faces);
+        return m;
+    }
+    const DeviceArray<Point>& last_indexed_vertices() const { return indexed_vertices_; }
+
 private:
     DeviceArray2D<int> occupied_voxels_buffer_;
     DeviceArray<unsigned char> scan_scratch_;  // kept between frames: the scan steps allocate nothing per call
+    DeviceArray<unsigned char> indexed_scratch_;  // run_indexed's workspace, kept between calls like scan_scratch_
+    DeviceArray<Point> indexed_vertices_;
+    DeviceArray<Normal> indexed_normals_;
+    DeviceArray<int> indexed_faces_;
     Affine3f pose;
 };
 }  // namespace cuda
@@ -708,6 +754,36 @@ inline bool write_vtk(const std::string& path, const TriangleMesh& m) {
         }
     }
     return std::fclose(f) == 0;
+}
+// Binary little-endian PLY 1.0 of an indexed mesh: vertex (float x y z nx ny nz [uchar red green blue]), face (list uchar int
+// vertex_indices).  Colours are written when the mesh has one per vertex.  sobfu_amd/mesh_io.py writes the same bytes.
+inline bool write_ply(const std::string& path, const IndexedMesh& m) {
+    const size_t n = m.vertices.size(), nt = m.triangles();
+    const bool coloured = !m.colours.empty() && m.colours.size() == n;
+    std::string h = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) +
+                    "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n";
+    if (coloured) h += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+    h += "element face " + std::to_string(nt) + "\nproperty list uchar int vertex_indices\nend_header\n";
+    const size_t vrec = 24 + (coloured ? 3 : 0), frec = 13;
+    std::vector<unsigned char> buf(h.size() + n * vrec + nt * frec);
+    std::memcpy(buf.data(), h.data(), h.size());
+    unsigned char* o = buf.data() + h.size();
+    static_assert(sizeof(float) == 4 && sizeof(int) == 4, "PLY float / int are 4 bytes");
+    for (size_t i = 0; i < n; ++i, o += vrec) {  // x86-64 and aarch64 hosts are little-endian: the bytes go out as they are
+        const float4 v = m.vertices[i];
+        float r[6] = {v.x, v.y, v.z, 0.f, 0.f, 0.f};
+        if (i < m.normals.size()) r[3] = m.normals[i].x, r[4] = m.normals[i].y, r[5] = m.normals[i].z;
+        std::memcpy(o, r, sizeof r);
+        if (coloured) o[24] = m.colours[i].r, o[25] = m.colours[i].g, o[26] = m.colours[i].b;
+    }
+    for (size_t k = 0; k < nt; ++k, o += frec) {
+        o[0] = 3;
+        std::memcpy(o + 1, &m.faces[3 * k], 12);
+    }
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    return (std::fclose(f) == 0) && ok;
 }
 }  // namespace sobfu_amd
 
@@ -1088,6 +1164,16 @@ public:
         kfusion::cuda::waitAllDefaultStream();
         sobfu_amd::TriangleMesh m = convert_to_mesh(model.vertices);
         if (colour) colour->sample_vertices(model.vertices, params.volume_pose, vol->getVoxelSize(), m.colours);  // mc's pose
+        return m;
+    }
+    // indexed (welded) meshes of the same four volumes, with the same colours as the soup getters
+    sobfu_amd::IndexedMesh get_phi_global_indexed_mesh() { return get_indexed_mesh(phi_global, colour_global.get()); }
+    sobfu_amd::IndexedMesh get_phi_global_psi_inv_indexed_mesh() { return get_indexed_mesh(phi_global_psi_inv, get_colour_global_psi_inv().get()); }
+    sobfu_amd::IndexedMesh get_phi_n_indexed_mesh() { return get_indexed_mesh(phi_n); }
+    sobfu_amd::IndexedMesh get_phi_n_psi_indexed_mesh() { return get_indexed_mesh(phi_n_psi); }
+    sobfu_amd::IndexedMesh get_indexed_mesh(cv::Ptr<kfusion::cuda::TsdfVolume> vol, const kfusion::cuda::ColourVolume* colour = nullptr) {
+        sobfu_amd::IndexedMesh m = mc->run_indexed(*vol);
+        if (colour && !m.empty()) colour->sample_vertices(mc->last_indexed_vertices(), params.volume_pose, vol->getVoxelSize(), m.colours);
         return m;
     }
     static sobfu_amd::TriangleMesh convert_to_mesh(const kfusion::cuda::DeviceArray<kfusion::cuda::Point>& triangles) {

@@ -300,6 +300,25 @@ int sobfu_hip_mc_offsets(void* stream, int* d_occupied, int stride, int count, i
 int sobfu_hip_mc_generate_triangles(void* stream, const float* d_vol, int X, int Y, int Z, const int* d_occupied, int stride, int count,
                                     float size_x, float size_y, float size_z, const float R[9], const float t[3], float* d_vertices,
                                     float* d_normals, int max_vertices);
+/* Indexed (welded) meshes: one vertex per cut grid edge that some active cell uses, shared by all its triangles.  Voxel v owns the edges
+ * leaving it in +x, +y, +z; vertices come in ascending owner index, then axis x < y < z.  A vertex is the soup's interpolation along its
+ * edge from the lower corner up, posed and stored like the soup's ((x, -y, -z, 1)); its normal is the TSDF gradient (central differences,
+ * one-sided on a volume face, interpolated along the edge like the vertex), normalised, rotated by R and stored as (nx, -ny, -nz, 1) --
+ * pointing toward positive TSDF; a zero gradient gives (0, 0, 0, 1).  Face k (int32 x 3) is soup triangle k with corners 1 and 2 swapped:
+ * counter-clockwise seen from outside.  The rules are in sobfu_amd/csrc/mc_kernels.hip.
+ * d_workspace (required): >= sobfu_hip_mc_indexed_workspace_bytes(X, Y, Z) bytes (6 per voxel + per-2048-voxel sums); X*Y*Z > INT32_MAX:
+ * SOBFU_E_UNSUPPORTED. */
+size_t sobfu_hip_mc_indexed_workspace_bytes(int X, int Y, int Z);
+/* Counts of the whole mesh: active cells, vertices, triangles.  Leaves the per-voxel state in d_workspace for
+ * sobfu_hip_mc_indexed_generate.  Synchronises. */
+int sobfu_hip_mc_indexed_count(void* stream, const float* d_vol, int X, int Y, int Z, void* d_workspace, size_t workspace_bytes,
+                               int* h_active_cells, int* h_vertices, int* h_triangles);
+/* Same d_vol and workspace as the preceding count call; pose = volume -> world (R row-major, t).  Vertices / normals: float4, faces:
+ * int32 x 3.  Never truncates: max_vertices or max_triangles below the count call's totals is SOBFU_E_BADARG before any kernel is
+ * launched (reads the totals back: synchronises). */
+int sobfu_hip_mc_indexed_generate(void* stream, const float* d_vol, int X, int Y, int Z, float size_x, float size_y, float size_z,
+                                  const float R[9], const float t[3], void* d_workspace, size_t workspace_bytes, float* d_vertices,
+                                  float* d_normals, int max_vertices, int* d_faces, int max_triangles);
 
 /* ------------------------------------------------------------------------------------------------------
  * rendering -- kfusion::cuda::renderImage / renderTangentColors (include/kfusion/cuda/imgproc.hpp:30,42-46: declared, never

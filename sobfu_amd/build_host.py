@@ -72,11 +72,26 @@ def build_colour_tool(force: bool = False) -> str:
     return COLOUR_TOOL
 
 
+PLY_TOOL = os.path.join(ROOT, "build", "ply_write_tool")
+
+
+def build_ply_tool(force: bool = False) -> str:
+    """tests/cpp/ply_write_tool.cpp: CPU-only driver of sobfu_amd::write_ply (runs without a GPU)."""
+    src = os.path.join(ROOT, "tests", "cpp", "ply_write_tool.cpp")
+    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
+            os.path.join(HERE, "libsobfu_hip.so")]
+    if force or not os.path.exists(PLY_TOOL) or any(os.path.getmtime(PLY_TOOL) < os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(PLY_TOOL), exist_ok=True)
+        _compile(src, PLY_TOOL)
+    return PLY_TOOL
+
+
 def build_host(force: bool = False) -> str:
     build_app(force)
     build_io_tool(force)
     build_png_tool(force)
     build_colour_tool(force)
+    build_ply_tool(force)
     src = os.path.join(ROOT, "tests", "cpp", "host_shell_tests.cpp")
     deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
             os.path.join(HERE, "libsobfu_hip.so")]

@@ -431,6 +431,39 @@ def marching_cubes(vol, volume_size, R=np.eye(3), t=(0, 0, 0), max_voxels=2_000_
     return v[:total], n[:total]
 
 
+def mc_indexed_workspace(vol):
+    """workspace of marching_cubes_indexed on volumes of this shape (6 bytes per voxel; keep it between calls)"""
+    _lib.lib().sobfu_hip_mc_indexed_workspace_bytes.restype = C.c_size_t
+    n = int(_lib.lib().sobfu_hip_mc_indexed_workspace_bytes(*_xyz(vol)))
+    return torch.empty(n, dtype=torch.uint8, device=vol.device)
+
+
+def marching_cubes_indexed(vol, volume_size, R=np.eye(3), t=(0, 0, 0), workspace=None, colour=None):
+    """Indexed (welded) marching cubes: one vertex per cut edge, shared by its triangles -> (vertices (V, 4), normals (V, 4) float32,
+    faces (F, 3) int32) GPU tensors; with a colour volume of the same dims, + colours (V, 4) uint8 BGRA (sample_colour's rule).  Face k
+    is marching_cubes' triangle k with corners 1 and 2 swapped; vertex normals are the TSDF gradient.  Rules: sobfu_amd/csrc/mc_kernels.hip."""
+    L = _lib.lib()
+    if workspace is None:
+        workspace = mc_indexed_workspace(vol)
+    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
+    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    active, nv, nt = C.c_int(0), C.c_int(0), C.c_int(0)
+    ws = _ws(workspace)
+    check(L.sobfu_hip_mc_indexed_count(_stream(), _ptr(vol), *_xyz(vol), *ws, C.byref(active), C.byref(nv), C.byref(nt)), "mc_indexed_count")
+    v = torch.zeros((nv.value, 4), dtype=torch.float32, device=vol.device)
+    n = torch.zeros_like(v)
+    f = torch.zeros((nt.value, 3), dtype=torch.int32, device=vol.device)
+    if nt.value > 0:
+        check(L.sobfu_hip_mc_indexed_generate(_stream(), _ptr(vol), *_xyz(vol), _f(volume_size[0]), _f(volume_size[1]), _f(volume_size[2]), Rm, tv,
+                                              *ws, _ptr(v), _ptr(n), C.c_int(nv.value), _ptr(f, torch.int32), C.c_int(nt.value)),
+              "mc_indexed_generate")
+    if colour is not None:
+        Z, Y, X = vol.shape[:3]
+        vs = [float(np.float32(volume_size[i]) / np.float32(d)) for i, d in enumerate((X, Y, Z))]
+        return v, n, f, sample_colour(colour, vs, R, t, v, mc_vertices=True)
+    return v, n, f
+
+
 # ---- rendering (kfusion::cuda::renderImage / renderTangentColors; KinectFusion raycaster) ---------------------------------------
 def _image_ptr(t, dtype, channels):
     if not (t.is_cuda and t.dtype == dtype and t.dim() == 3 and t.shape[2] == channels and t.stride(2) == 1 and t.stride(1) == channels):
