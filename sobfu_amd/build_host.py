@@ -86,12 +86,27 @@ def build_ply_tool(force: bool = False) -> str:
     return PLY_TOOL
 
 
+VARIANT_TOOL = os.path.join(ROOT, "build", "variant_tool")
+
+
+def build_variant_tool(force: bool = False) -> str:
+    """tests/cpp/variant_tool.cpp: CPU-only driver of the fused passes' instantiation choice (sobfu_amd/csrc/sobfu_variant.hpp, no HIP)."""
+    src = os.path.join(ROOT, "tests", "cpp", "variant_tool.cpp")
+    deps = [src, os.path.join(HERE, "csrc", "sobfu_variant.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h")]
+    if force or not os.path.exists(VARIANT_TOOL) or any(os.path.getmtime(VARIANT_TOOL) < os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(VARIANT_TOOL), exist_ok=True)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", f"-I{os.path.join(HERE, 'csrc')}", f"-I{os.path.join(ROOT, 'include')}", src, "-o",
+                               VARIANT_TOOL])
+    return VARIANT_TOOL
+
+
 def build_host(force: bool = False) -> str:
     build_app(force)
     build_io_tool(force)
     build_png_tool(force)
     build_colour_tool(force)
     build_ply_tool(force)
+    build_variant_tool(force)
     src = os.path.join(ROOT, "tests", "cpp", "host_shell_tests.cpp")
     deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
             os.path.join(HERE, "libsobfu_hip.so")]

@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "sobfu_variant.hpp"
+
 namespace sobfu_hip {
 // A box of cells [x0, x1) x [y0, y1) x [z0, z1) of the (local) array a fused pass produces; direct: a THIN box, evaluated one
 // lane per cell straight from the caches instead of by a z-march (the one-cell shells of a tile, halo messages).  Up to 6 boxes
@@ -13,6 +15,66 @@ struct LaunchBox {
     int x0, x1, y0, y1, z0, z1;
     bool direct;
 };
+constexpr int kMaxLaunchBoxes = 6;
+// A launch of one of the two fused passes: set the fields by name, the rest keep their defaults.  (X, Y, Z): extents of the field
+// arrays.  The gate: the launch returns at once when the max-norm row prev_slots (null: never gated) is <= max_update_norm.
+// warp: the single-GPU loop without the phi_n o psi stream (loop_warps_in_pass_a) -- pass A samples phi_n (passed as pnp) at psi
+// itself, pass B neither gathers phi_n nor stores phi_n o psi.  A launch that cannot take that path is refused (SOBFU_E_UNSUPPORTED).
+struct PassALaunch {
+    const float* pnp = nullptr;  // phi_n o psi (phi_n where warp)
+    const float* pg  = nullptr;  // phi_global
+    const float* psi = nullptr;
+    float* nU        = nullptr;
+    float w_reg      = 0.f;
+    int X = 0, Y = 0, Z = 0;
+    LaunchBox boxes[kMaxLaunchBoxes] = {};
+    int n_boxes = 0;
+    const uint32_t* prev_slots = nullptr;
+    float max_update_norm      = 0.f;
+    bool compact = false;  // the solver's iteration format (12-byte psi / nabla_U, tsdf-only volumes); false: the API format
+    bool warp    = false;
+};
+struct PassBLaunch {
+    const float* nU     = nullptr;
+    float* psi          = nullptr;
+    float* psi_out      = nullptr;  // null: update psi in place
+    const float* phi_n  = nullptr;
+    float* pnp          = nullptr;  // phi_n o psi out
+    float* updates      = nullptr;  // null: no `updates` array
+    uint32_t* slots     = nullptr;  // this launch's max-norm row
+    const float* taps   = nullptr;  // [7]
+    float alpha         = 0.f;
+    int X = 0, Y = 0, Z = 0;
+    int pX = 0, pY = 0, pZ = 0;  // extents of phi_n (the whole volume)
+    int own[6] = {};             // the cells that enter the max-norm (x0, x1, y0, y1, z0, z1)
+    LaunchBox boxes[kMaxLaunchBoxes] = {};
+    int n_boxes = 0;
+    const uint32_t* prev_slots = nullptr;
+    float max_update_norm      = 0.f;
+    int prev_rows = 1;  // rows the gate reads, see solver_converged
+    bool compact  = false;
+    // the launch reads cells other GPUs stored: nabla_U and the max-norm rows are READ AT SYSTEM SCOPE (sc0 sc1 loads of the pipelined
+    // march / the thin shells / the gate; there is no invalidate -- + 39 us, measured); a launch that cannot take that march is refused
+    bool sys_acquire = false;
+    bool warp        = false;
+};
+// the whole grid as the launch's one box (and, for pass B, as phi_n and the cells that enter the max-norm): the single-GPU solver and
+// the launcher-level entry points
+inline void set_whole_grid(PassALaunch& l, int X, int Y, int Z) {
+    l.X = X; l.Y = Y; l.Z = Z;
+    l.boxes[0] = LaunchBox{0, X, 0, Y, 0, Z, false};
+    l.n_boxes  = 1;
+}
+inline void set_whole_grid(PassBLaunch& l, int X, int Y, int Z) {
+    l.X = X; l.Y = Y; l.Z = Z;
+    l.pX = X; l.pY = Y; l.pZ = Z;
+    const int own[6] = {0, X, 0, Y, 0, Z};
+    for (int i = 0; i < 6; ++i) l.own[i] = own[i];
+    l.boxes[0] = LaunchBox{0, X, 0, Y, 0, Z, false};
+    l.n_boxes  = 1;
+}
+int launch_pass_a(const PassALaunch& l, hipStream_t stream);
+int launch_pass_b(const PassBLaunch& l, hipStream_t stream);
 // A box of a tile's pass A.  dst != null: a PUSH box -- the cells of one halo message, whose results go to
 // dst + 3 * ((x + ox) + px * ((y + oy) + py * (z + oz))): the neighbour's halo cells (peer-mapped) or a packed send buffer.
 // A MARCHING push box may be larger than its message and serve the owned block too (which then leaves those cells out): only rows
@@ -23,11 +85,6 @@ struct TileLaunchBox {
     int ox, oy, oz, px, py;
     int push_y0, push_y1, local_z0, local_z1;
 };
-// (X, Y, Z): extents of the field arrays; (pX, pY, pZ): extents of phi_n (the whole volume); own: the cells that enter the
-// max-norm (x0, x1, y0, y1, z0, z1).
-int launch_pass_a_boxes(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const LaunchBox* boxes,
-                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact,
-                        bool warp = false /* pnp is phi_n: pass A samples phi_n at psi itself (see loop_warps_in_pass_a) */);
 // Signalling state of the direct transport (device memory, one per tiled handle; filled by sobfu_hip_tiled_connect and read by
 // the tail of tile_potential_gradient_kernel).
 constexpr int kMaxSync = 64;
@@ -57,27 +114,6 @@ int launch_tile_flush(TileSync* sync, uint32_t seq, int wait, const uint32_t* ro
 // diagnostics: `reps` flag round trips between this rank and sync-set member `q` (both sides launch it; `first` serves); sequence
 // numbers seq0 .. seq0 + 2 * reps - 1
 int launch_tile_pingpong(TileSync* sync, int q, int first, uint32_t seq0, int reps, hipStream_t stream);
-int launch_pass_b_boxes(const float* nU, float* psi, const float* phi_n, float* pnp, float* updates, uint32_t* slots, const float taps[7],
-                        float alpha, int X, int Y, int Z, int pX, int pY, int pZ, const int own[6], const LaunchBox* boxes, int n,
-                        const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact,
-                        float* psi_out = nullptr /* null: update psi in place */, int prev_rows = 1,
-                        bool sys_acquire = false /* the launch reads cells other GPUs stored: nabla_U and the max-norm rows are READ AT SYSTEM SCOPE
-                                                     (sc0 sc1 loads of the pipelined march / the thin shells / the gate; there is no invalidate -- + 39 us,
-                                                     measured); a launch that cannot take that march is refused with SOBFU_E_UNSUPPORTED */,
-                        bool apply = true /* false: no phi_n o psi (loop_warps_in_pass_a); refused where the launch would not take the plain march */);
-// Pass A / pass B over planes [z_lo, z_hi) (z_hi <= 0: the whole grid) and, optionally, a second range [z_lo2, z_hi2)
-// in the same launch (both boundary regions of a multi-GPU slab).  zc <= 0: z-chunk chosen by the cost model.
-int launch_pass_a(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z,
-                  const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, int z_lo = 0, int z_hi = 0,
-                  int z_lo2 = 0, int z_hi2 = 0, bool warp = false);
-int launch_pass_b(const float* nU, float* psi, const float* phi_n, float* pnp, float* updates, uint32_t* slots,
-                  const float taps[7], float alpha, int X, int Y, int Z, const uint32_t* prev_slots,
-                  float max_update_norm, int zc, hipStream_t stream, int phi_Z, int own_lo, int own_hi, bool compact, int z_lo = 0,
-                  int z_hi = 0, int z_lo2 = 0, int z_hi2 = 0, float* psi_out = nullptr /* null: update psi in place */,
-                  int prev_rows = 1 /* rows the gate reads, see solver_converged */, bool apply = true);
-// Does the compact single-GPU loop of this grid run without the phi_n o psi stream?  Then its pass A takes phi_n for pnp and
-// warp = true, its pass B apply = false (solver_kernels.hip).
-bool loop_warps_in_pass_a(int X, int Y, int Z);
 int launch_pack_vec(const float* src4, float* dst3, size_t N, hipStream_t stream);
 int launch_unpack_vec(const float* src3, float* dst4, size_t N, hipStream_t stream);
 int launch_extract_tsdf(const float* src2, float* dst1, size_t N, hipStream_t stream);

@@ -239,6 +239,18 @@ int session_enqueue(sobfu_hip_solver* s, int n, bool poll, float* per_iter, hipS
     const sobfu_hip_solver_params& p = s->p;
     const bool can_converge = p.max_update_norm >= 0.f;  // ||u|| >= 0 > negative threshold: never fires
     const int last = q.launched + n;
+    sobfu_hip::PassALaunch A;
+    sobfu_hip::set_whole_grid(A, X, Y, Z);
+    A.pnp = q.warp ? q.it_pn : q.it_pnp; A.pg = q.it_pg; A.psi = q.it_psi; A.nU = s->nabla_U; A.w_reg = p.w_reg;
+    A.max_update_norm = p.max_update_norm;
+    A.compact = q.compact;
+    A.warp    = q.warp;
+    sobfu_hip::PassBLaunch B;
+    sobfu_hip::set_whole_grid(B, X, Y, Z);
+    B.nU = s->nabla_U; B.psi = q.it_psi; B.phi_n = q.it_pn; B.pnp = q.it_out; B.updates = q.upd; B.taps = s->taps; B.alpha = p.alpha;
+    B.max_update_norm = p.max_update_norm;
+    B.compact = q.compact;
+    B.warp    = q.warp;
     for (int it = q.launched + 1; it <= last && !q.converged; ++it) {
         const uint32_t* prev = (it > 1) ? s->slots + (size_t) (it - 1) * kSlots : nullptr;
         uint32_t* cur        = s->slots + (size_t) it * kSlots;
@@ -247,11 +259,11 @@ int session_enqueue(sobfu_hip_solver* s, int n, bool poll, float* per_iter, hipS
         const bool ev = s->prof_stride > 0 && (it % s->prof_stride == 0) && (size_t) 3 * (s->prof_pending + 1) <= s->events.size();
         const int e0  = 3 * s->prof_pending;
         if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0], st));
-        SOBFU_TRY(sobfu_hip::launch_pass_a(q.warp ? q.it_pn : q.it_pnp, q.it_pg, q.it_psi, s->nabla_U, p.w_reg, X, Y, Z, prev, p.max_update_norm, 0,
-                                           st, q.compact, 0, 0, 0, 0, q.warp));
+        A.prev_slots = B.prev_slots = prev;
+        B.slots = cur;
+        SOBFU_TRY(sobfu_hip::launch_pass_a(A, st));
         if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 1], st));
-        SOBFU_TRY(sobfu_hip::launch_pass_b(s->nabla_U, q.it_psi, q.it_pn, q.it_out, q.upd, cur, s->taps, p.alpha, X, Y, Z, prev,
-                                           p.max_update_norm, 0, st, 0, 0, 0, q.compact, 0, 0, 0, 0, nullptr, 1, !q.warp));
+        SOBFU_TRY(sobfu_hip::launch_pass_b(B, st));
         if (ev) {
             SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 2], st));
             s->prof_pending += 1;
@@ -367,6 +379,15 @@ int run_verbose(sobfu_hip_solver* s, const float* pg, const float* pn, float* pn
         const int rc_ = (int) (expr);       \
         if (rc_ != 0) return fail(rc_);     \
     } while (0)
+    // a reporting iteration: ungated, and its pass B stores `updates`
+    sobfu_hip::PassALaunch A;
+    sobfu_hip::set_whole_grid(A, X, Y, Z);
+    A.pnp = q.it_pnp; A.pg = q.it_pg; A.psi = q.it_psi; A.nU = s->nabla_U; A.w_reg = p.w_reg;
+    A.compact = q.compact;
+    sobfu_hip::PassBLaunch B;
+    sobfu_hip::set_whole_grid(B, X, Y, Z);
+    B.nU = s->nabla_U; B.psi = q.it_psi; B.phi_n = q.it_pn; B.pnp = q.it_out; B.updates = s->updates; B.taps = s->taps; B.alpha = p.alpha;
+    B.compact = q.compact;
     for (int it = 1; it <= max_iter && !q.converged;) {
         if (!reports(it)) {  // a run of quiet iterations it .. to
             int to = it;
@@ -387,9 +408,9 @@ int run_verbose(sobfu_hip_solver* s, const float* pg, const float* pn, float* pn
         const float e = e_data + p.w_reg * e_reg;
         s->log("data energy + w_reg * reg energy = " + fmt_g(e_data) + " + " + fmt_g(p.w_reg) + " * " + fmt_g(e_reg) + " = " + fmt_g(e));
         uint32_t* cur = s->slots + (size_t) it * kSlots;  // the row the next quiet iteration's gate reads
-        SOBFU_VTRY(sobfu_hip::launch_pass_a(q.it_pnp, q.it_pg, q.it_psi, s->nabla_U, p.w_reg, X, Y, Z, nullptr, 0.f, 0, st, q.compact));
-        SOBFU_VTRY(sobfu_hip::launch_pass_b(s->nabla_U, q.it_psi, q.it_pn, q.it_out, s->updates, cur, s->taps, p.alpha, X, Y, Z, nullptr, 0.f, 0, st, 0,
-                                            0, 0, q.compact));
+        B.slots = cur;
+        SOBFU_VTRY(sobfu_hip::launch_pass_a(A, st));
+        SOBFU_VTRY(sobfu_hip::launch_pass_b(B, st));
         float mx[2];
         SOBFU_VTRY(sobfu_hip_max_update_norm(s->updates, (int) s->N, s->red_scratch, mx, st));  // solver.cu:172 (synchronises)
         if (per_iter) per_iter[it - 1] = mx[0];

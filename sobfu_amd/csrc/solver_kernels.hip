@@ -13,7 +13,7 @@
 // Arithmetic is op-for-op the reference's (see sobfu_device.hpp): results are bit-identical to the launcher-for-launcher kernels.
 #include <algorithm>
 #include <cstdlib>
-#include <vector>
+#include <type_traits>
 
 #include "sobfu_device.hpp"
 #include "sobfu_hip.h"
@@ -45,6 +45,7 @@ constexpr int kMaxMsgs = 18;  // 6 face + 12 edge neighbours of a 3-D tile
 // tile of a workgroup: 64 lanes x 8 waves, one row per wave (rows-per-thread 2 / 4 and 4 / 16 waves were measured in rounds 1 - 2:
 // profiles/LABBOOK.md; the kernels keep RPT / WY as template parameters, the launchers instantiate this one shape)
 constexpr int kRPT = 1, kWY = 8;
+static_assert(sobfu_hip::kMaxLaunchBoxes == kMaxBoxes, "a launch descriptor holds the boxes of one launch");
 
 namespace sobfu_hip {
 
@@ -74,13 +75,6 @@ int pick_zc(int X, int Y, int nz, int ty, int capacity, int refill, const char* 
         if (cost < best - 1e-9) { best = cost; best_zc = zc; }
     }
     return best_zc;
-}
-
-// Does the iteration's state (76 B per cell of the local arrays) stay in the 256 MiB Infinity Cache from one launch to the next?
-// Then the streaming hints are off (they would push what the next launch reads out of the cache).  SOBFU_CACHE_CELLS overrides.
-static bool cache_resident(int X, int Y, int Z) {
-    const char* e = getenv("SOBFU_CACHE_CELLS");
-    return (long) X * Y * Z <= (e ? atol(e) : 3300000L);  // ~250 MB / 76 B
 }
 
 // direct boxes: lanes of a wave that run along x, and the workgroups (of WY waves) the box needs
@@ -135,8 +129,7 @@ static int finish_box(Box& b, const LaunchBox& s, int ty, int share, int refill,
 // Fills the launch geometry of a box list: z-chunk per marching box (cost model above, the chip's capacity shared between the
 // marching boxes; direct boxes are one short round trip and take no share) and the workgroup prefix -- marching boxes first.
 // Returns the workgroups.
-static int finish_boxes(BoxList& L, const LaunchBox* boxes, int n, int ty, int capacity, int refill, int zc_override, const char* env,
-                        bool even = false) {
+static int finish_boxes(BoxList& L, const LaunchBox* boxes, int n, int ty, int capacity, int refill, const char* env, bool even = false) {
     L.n = 0;
     int live = 0;
     bool thin = false;
@@ -157,7 +150,7 @@ static int finish_boxes(BoxList& L, const LaunchBox* boxes, int n, int ty, int c
             // the chip's workgroup slots are shared equally between the marching boxes (the two plane ranges of an overlapped slab
             // schedule): a thin range is latency-critical, so it gets as many short marches as the big one gets long ones
             L.first[L.n] = total;
-            total += finish_box(L.b[L.n], boxes[i], ty, std::max(capacity / std::max(live, 1), 1), refill, zc_override, env, true, even);
+            total += finish_box(L.b[L.n], boxes[i], ty, std::max(capacity / std::max(live, 1), 1), refill, 0, env, true, even);
             ++L.n;
         }
         if (!direct_pass) L.m1 = total;
@@ -168,8 +161,8 @@ static int finish_boxes(BoxList& L, const LaunchBox* boxes, int n, int ty, int c
 
 // Pass A of a multi-GPU tile (see tile_potential_gradient_kernel): the launch geometry of its box list.  The boxes with a
 // destination (push boxes: direct, their result goes to `dst` only) are numbered first, then the others; returns the workgroups
-// (< 0: too many boxes)
-static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, int X, int Y, int Z, int zc) {
+// (< 0: too many boxes).  resident: the tile's state stays in the Infinity Cache (GridTraits)
+static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, bool resident) {
     constexpr int TY = kRPT * kWY;
     L.n = 0;
     int live = 0, total = 0;
@@ -184,8 +177,8 @@ static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, in
             // z-chunks: a marching push box (a face with wide rows) marches up to 8 planes; the owned block of a cache-resident
             // tile is sized for TWO workgroups per CU -- the push boxes take slots too, and at that size 8-plane marches beat the 4-plane ones that
             // filling all four slots per CU would give (2 x 2 x 2 tile of 256^3: pass A 19.8 -> 19.1 us, 1 x 2 x 4: 18.9 -> 17.2)
-            const int zc_box = zc > 0 ? zc : ((s.dst != nullptr && !s.box.direct) ? std::min(8, s.box.z1 - s.box.z0) : 0);
-            total += finish_box(t.b, s.box, TY, std::max(256 * (cache_resident(X, Y, Z) ? 2 : 4) * 8 / kWY / std::max(live, 1), 1), 2, zc_box,
+            const int zc_box = (s.dst != nullptr && !s.box.direct) ? std::min(8, s.box.z1 - s.box.z0) : 0;
+            total += finish_box(t.b, s.box, TY, std::max(256 * (resident ? 2 : 4) * 8 / kWY / std::max(live, 1), 1), 2, zc_box,
                                 "SOBFU_ZC_A", false);
             t.push.base = s.dst;
             t.push.ox = s.ox; t.push.oy = s.oy; t.push.oz = s.oz; t.push.px = s.px; t.push.py = s.py;
@@ -198,61 +191,64 @@ static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, in
     return total;
 }
 
-// the launch of a box list in device memory; sync / seq / wait / row: the direct transport's signalling (sync null: none)
-static int launch_tile_boxes(const TileBoxList* d_boxes, int groups, const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X,
-                             int Y, int Z, TileSync* sync, uint32_t seq, int wait, const uint32_t* row, uint32_t row_index, hipStream_t stream,
-                             bool compact) {
-    if (groups == 0) return 0;
-    TilePassAArgsP a{{pnp, pg, psi, nU, {X, Y, Z}, w_reg, nullptr, 0.f}, d_boxes, {sync, seq, wait, row, row_index}};
+// Calls launch(std::integral_constant<size_t, I>{}) for the row I of `table` that equals `v`, which instantiates the kernel of that
+// row: only the table's rows are ever instantiated.  false: `v` is no row of the table.
+template <size_t I = 0, class Row, size_t N, class F>
+static bool launch_row(const Row (&table)[N], const Row& v, F&& launch) {
+    if constexpr (I < N) {
+        if (table[I] == v) {
+            launch(std::integral_constant<size_t, I>{});
+            return true;
+        }
+        return launch_row<I + 1>(table, v, launch);
+    } else {
+        return false;
+    }
+}
+
+// the launch of a box list in device memory by the tile kernel (v: choose_pass_a with tile = true)
+static int launch_tile_boxes(const TilePassAArgsP& a, int groups, const PassAVariant& v, hipStream_t stream) {
     const dim3 grid((unsigned) groups), block(TX, kWY);
-    if (compact && cache_resident(X, Y, Z)) hipLaunchKernelGGL((tile_potential_gradient_kernel<kRPT, kWY, true, 0>), grid, block, 0, stream, a);
-    else if (compact) hipLaunchKernelGGL((tile_potential_gradient_kernel<kRPT, kWY, true, kNT>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((tile_potential_gradient_kernel<kRPT, kWY, false, 0>), grid, block, 0, stream, a);
-    return (int) hipGetLastError();
+    const bool found = launch_row(kTilePassATable, v, [&](auto i) {
+        constexpr PassAVariant V = kTilePassATable[decltype(i)::value];
+        hipLaunchKernelGGL((tile_potential_gradient_kernel<kRPT, kWY, V.compact, V.nt ? kNT : 0>), grid, block, 0, stream, a);
+    });
+    return found ? (int) hipGetLastError() : SOBFU_E_UNSUPPORTED;
 }
 
-// The compact single-GPU loop of a grid beyond the Infinity Cache runs without the phi_n o psi stream: pass A warps phi_n itself
-// (pass_a_march, WARP), pass B neither warps nor stores F (APPLY = false) -- 68 instead of 76 B per cell and iteration.  The grids
-// whose pass B takes the plain march with buffer-addressed psi (NTBUF); SOBFU_WARP_A=0 turns the pair off (tuning override).
-bool loop_warps_in_pass_a(int X, int Y, int Z) {
-    const char* e = getenv("SOBFU_WARP_A");
-    if (e && atoi(e) == 0) return false;
-    const char* pipe_e = getenv("SOBFU_PIPE_B");
-    const size_t n = (size_t) X * Y * Z;
-    return !cache_resident(X, Y, Z) && !(pipe_e && atoi(pipe_e) != 0) && n * 12 < ((size_t) 1 << 32) && (size_t) X * Y * 16 < ((size_t) 1 << 32);
-}
-
-int launch_pass_a_boxes(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z, const LaunchBox* boxes,
-                        int n, const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, bool warp) {
+int launch_pass_a(const PassALaunch& L, hipStream_t stream) {
     constexpr int TY = kRPT * kWY;
+    if (L.n_boxes > kMaxLaunchBoxes) return SOBFU_E_BADARG;
     bool direct = false;
-    for (int i = 0; i < n; ++i) direct = direct || (boxes[i].direct && box_cells(boxes[i]) > 0);
-    // warp: pnp is phi_n (tsdf-only, extents X, Y, Z), sampled with 32-bit byte offsets
-    if (warp && (direct || !compact || cache_resident(X, Y, Z) || (size_t) X * Y * Z * 4 >= ((size_t) 1 << 32))) return SOBFU_E_UNSUPPORTED;
-    if (direct) {  // thin boxes: the tile kernel (no messages, no signalling) with a list of this call's own
-        std::vector<TileLaunchBox> tb((size_t) n);
-        for (int i = 0; i < n; ++i) tb[(size_t) i] = TileLaunchBox{boxes[i], nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        TileBoxList L{};
-        const int total = fill_tile_boxes(L, tb.data(), n, X, Y, Z, zc);
+    for (int i = 0; i < L.n_boxes; ++i) direct = direct || (L.boxes[i].direct && box_cells(L.boxes[i]) > 0);
+    const GridTraits g = grid_traits(L.X, L.Y, L.Z, L.X, L.Y, L.Z, env_cache_cells());
+    PassAVariant v;
+    SOBFU_TRY(choose_pass_a(g, L.compact, L.warp, direct, &v));
+    if (direct) {  // thin boxes: the tile kernel (no messages, no signalling, no gate) with a list of this call's own
+        TileLaunchBox tb[kMaxLaunchBoxes];
+        for (int i = 0; i < L.n_boxes; ++i) tb[i] = TileLaunchBox{L.boxes[i], nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        TileBoxList B{};
+        const int total = fill_tile_boxes(B, tb, L.n_boxes, g.resident);
         if (total <= 0) return total < 0 ? SOBFU_E_BADARG : 0;
-        // a stream-ordered device copy, freed behind the launch (hipMemcpyAsync from pageable memory has read L when it returns)
+        // a stream-ordered device copy, freed behind the launch (hipMemcpyAsync from pageable memory has read B when it returns)
         TileBoxList* d = nullptr;
-        SOBFU_HIP_TRY(hipMallocAsync((void**) &d, sizeof L, stream));
-        const hipError_t e = hipMemcpyAsync(d, &L, sizeof L, hipMemcpyHostToDevice, stream);
-        const int rc = e != hipSuccess ? (int) e : launch_tile_boxes(d, total, pnp, pg, psi, nU, w_reg, X, Y, Z, nullptr, 0, 0, nullptr, 0, stream, compact);
+        SOBFU_HIP_TRY(hipMallocAsync((void**) &d, sizeof B, stream));
+        const hipError_t e = hipMemcpyAsync(d, &B, sizeof B, hipMemcpyHostToDevice, stream);
+        const TilePassAArgsP a{{L.pnp, L.pg, L.psi, L.nU, {L.X, L.Y, L.Z}, L.w_reg, nullptr, 0.f}, d, {nullptr, 0, 0, nullptr, 0}};
+        const int rc = e != hipSuccess ? (int) e : launch_tile_boxes(a, total, v, stream);
         const hipError_t f = hipFreeAsync(d, stream);
         return rc != 0 ? rc : (int) f;
     }
-    PassAArgs a{{pnp, pg, psi, nU, {X, Y, Z}, w_reg, prev_slots, max_update_norm}, {}};
+    PassAArgs a{{L.pnp, L.pg, L.psi, L.nU, {L.X, L.Y, L.Z}, L.w_reg, L.prev_slots, L.max_update_norm}, {}};
     // <= 64 VGPR (the warping march included), 22 KB LDS: 4 workgroups of 8 waves per CU
-    const int groups = finish_boxes(a.boxes, boxes, n, TY, 256 * 4 * 8 / kWY, 2, zc, "SOBFU_ZC_A");
+    const int groups = finish_boxes(a.boxes, L.boxes, L.n_boxes, TY, 256 * 4 * 8 / kWY, 2, "SOBFU_ZC_A");
     if (groups == 0) return 0;
     const dim3 grid((unsigned) groups), block(TX, kWY);
-    if (warp) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, kNT, true>), grid, block, 0, stream, a);
-    else if (compact && cache_resident(X, Y, Z)) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, 0>), grid, block, 0, stream, a);
-    else if (compact) hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, true, kNT>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, false, 0>), grid, block, 0, stream, a);
-    return (int) hipGetLastError();
+    const bool found = launch_row(kPassATable, v, [&](auto i) {
+        constexpr PassAVariant V = kPassATable[decltype(i)::value];
+        hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, V.compact, V.nt ? kNT : 0, V.warp>), grid, block, 0, stream, a);
+    });
+    return found ? (int) hipGetLastError() : SOBFU_E_UNSUPPORTED;
 }
 
 // A PLANNED launch of the same pass (compact format): the geometry is worked out once per handle and half of the nabla_U ping-pong
@@ -262,7 +258,7 @@ struct TilePassAPlan {
 };
 int tile_pass_a_plan_create(TilePassAPlan** out, const TileLaunchBox* boxes, int n, int X, int Y, int Z) {
     TileBoxList L{};
-    const int total = fill_tile_boxes(L, boxes, n, X, Y, Z, 0);
+    const int total = fill_tile_boxes(L, boxes, n, grid_traits(X, Y, Z, X, Y, Z, env_cache_cells()).resident);
     if (total < 0) return SOBFU_E_BADARG;
     auto* p = new TilePassAPlan();
     p->groups = total; p->X = X; p->Y = Y; p->Z = Z;
@@ -288,7 +284,11 @@ void tile_pass_a_plan_destroy(TilePassAPlan* p) {
 }
 int launch_tile_pass_a_plan(const TilePassAPlan* p, const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, TileSync* sync,
                             uint32_t seq, int wait, const uint32_t* row, uint32_t row_index, hipStream_t stream) {
-    return launch_tile_boxes(p->d_boxes, p->groups, pnp, pg, psi, nU, w_reg, p->X, p->Y, p->Z, sync, seq, wait, row, row_index, stream, true);
+    if (p->groups == 0) return 0;
+    PassAVariant v;
+    SOBFU_TRY(choose_pass_a(grid_traits(p->X, p->Y, p->Z, p->X, p->Y, p->Z, env_cache_cells()), true, false, true, &v));
+    const TilePassAArgsP a{{pnp, pg, psi, nU, {p->X, p->Y, p->Z}, w_reg, nullptr, 0.f}, p->d_boxes, {sync, seq, wait, row, row_index}};
+    return launch_tile_boxes(a, p->groups, v, stream);
 }
 
 int launch_tile_pingpong(TileSync* sync, int q, int first, uint32_t seq0, int reps, hipStream_t stream) {
@@ -301,101 +301,39 @@ int launch_tile_flush(TileSync* sync, uint32_t seq, int wait, const uint32_t* ro
     return (int) hipGetLastError();
 }
 
-int launch_pass_b_boxes(const float* nU, float* psi, const float* phi_n, float* pnp, float* updates, uint32_t* slots, const float taps[7],
-                        float alpha, int X, int Y, int Z, int pX, int pY, int pZ, const int own[6], const LaunchBox* boxes, int n,
-                        const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, float* psi_out, int prev_rows,
-                        bool sys_acquire, bool apply) {
+int launch_pass_b(const PassBLaunch& L, hipStream_t stream) {
     constexpr int TY = kRPT * kWY;
-    PassBArgs a{nU, psi, phi_n, pnp, (float4*) updates, slots, {X, Y, Z}, {}, alpha, {}, prev_slots, max_update_norm, {pX, pY, pZ},
-                {own[0], own[1], own[2], own[3], own[4], own[5]}, prev_rows, psi_out ? psi_out : psi, sys_acquire ? 1 : 0};
-    for (int i = 0; i < 7; ++i) a.S.s[i] = taps[i];
-    if ((size_t) X * Y * 16 >= ((size_t) 1 << 32)) return SOBFU_E_UNSUPPORTED;  // in-plane byte offsets are 32-bit
-    if (sys_acquire && (size_t) X * Y * Z * 12 >= ((size_t) 1 << 32)) return SOBFU_E_UNSUPPORTED;  // scope-carrying loads are buffer loads: arrays below 4 GiB
-    const bool idx32 = (size_t) pX * pY * pZ < ((size_t) 1 << 30);  // tsdf-only phi_n below 4 GiB: 32-bit byte offsets for the corner gather
-    // the solver's own format (compact, 32-bit gather offsets, no `updates`): streaming hints only for grids beyond the Infinity
-    // Cache; the pipelined march where the launch is latency-bound (cache-resident sizes; SOBFU_PIPE_B=0/1 overrides)
-    const bool resident = cache_resident(X, Y, Z);
-    const char* pipe_e = getenv("SOBFU_PIPE_B");
-    // (buffer addressing: arrays below 4 GiB.  Connected handles ALWAYS take the pipelined march, whatever SOBFU_PIPE_B says: it is the
-    // march whose loads carry the system scope for the halo cells other GPUs stored)
-    const bool pipe = compact && idx32 && !updates && (size_t) X * Y * Z * 12 < ((size_t) 1 << 32) && (sys_acquire || (pipe_e ? atoi(pipe_e) != 0 : resident));
-    if (sys_acquire && !pipe) return SOBFU_E_UNSUPPORTED;  // never fall back to a march that reads peer-written cells with ordinary loads
+    if (L.n_boxes > kMaxLaunchBoxes) return SOBFU_E_BADARG;
+    PassBArgs a{L.nU, L.psi, L.phi_n, L.pnp, (float4*) L.updates, L.slots, {L.X, L.Y, L.Z}, {}, L.alpha, {}, L.prev_slots, L.max_update_norm,
+                {L.pX, L.pY, L.pZ}, {L.own[0], L.own[1], L.own[2], L.own[3], L.own[4], L.own[5]}, L.prev_rows, L.psi_out ? L.psi_out : L.psi,
+                L.sys_acquire ? 1 : 0};
+    for (int i = 0; i < 7; ++i) a.S.s[i] = L.taps[i];
+    const GridTraits g = grid_traits(L.X, L.Y, L.Z, L.pX, L.pY, L.pZ, env_cache_cells(), env_pipe_b());
+    const PassBAsk ask{L.compact, L.updates != nullptr, L.sys_acquire, !L.warp};
+    PassBMarch m;
+    SOBFU_TRY(pass_b_march(g, ask, &m));
     // workgroups a CU holds: <= 80 VGPR (launch bounds) and 32 - 48 KB LDS: 3 of 8 waves; the pipelined march (<= 128 VGPR): 2
     // cache-resident launches are ONE resident round of workgroups, which lasts as long as its longest march: the planes are
     // split evenly over as many z-chunks as fill the marching workgroups' share of the chip
-    const int groups = finish_boxes(a.boxes, boxes, n, TY, 256 * (pipe ? 2 : 3) * 8 / kWY, 6, zc, "SOBFU_ZC_B", resident && pipe);
-    if (groups == 0) return 0;
-    bool direct = false;
+    const int groups = finish_boxes(a.boxes, L.boxes, L.n_boxes, TY, 256 * (m.pipe ? 2 : 3) * 8 / kWY, 6, "SOBFU_ZC_B", g.resident && m.pipe);
+    if (groups == 0) return 0;  // an empty launch is no launch, whatever stage 2 would say of it
     int zc_max = 0;
     for (int i = 0; i < a.boxes.n; ++i) {
-        direct = direct || a.boxes.b[i].kind != 0;
+        m.direct = m.direct || a.boxes.b[i].kind != 0;
         if (a.boxes.b[i].kind == 0) zc_max = std::max(zc_max, a.boxes.b[i].zc + (a.boxes.b[i].rem > 0 ? 1 : 0));  // the first `rem` chunks march one plane more
-        if (a.boxes.b[i].kind == 0 && pipe && resident && SOBFU_PAIR_B) a.boxes.b[i].pair = 1;  // neighbouring z-chunks march towards / away from each other
+        if (a.boxes.b[i].kind == 0 && m.pipe && g.resident && SOBFU_PAIR_B) a.boxes.b[i].pair = 1;  // neighbouring z-chunks march towards / away from each other
     }
-    const bool ntbuf = (size_t) X * Y * Z * 12 < ((size_t) 1 << 32);  // the plain march's 12-byte psi load / store as buffer instructions (their cache-policy operand carries the streaming hint): arrays below 4 GiB
-    // !apply (loop_warps_in_pass_a): the plain march with buffer-addressed psi only -- any other launch would leave phi_n o psi stale
-    if (!apply && (direct || !compact || !idx32 || updates || resident || pipe || !ntbuf || sys_acquire)) return SOBFU_E_UNSUPPORTED;
+    m.long_marches = SOBFU_HLEAD > 0 && zc_max >= SOBFU_HLEAD_MIN_ZC;
+    PassBVariant v;
+    SOBFU_TRY(choose_pass_b(g, ask, m, &v));
     const dim3 grid((unsigned) groups), block(TX, kWY);
-#define SOBFU_LAUNCH_B(UPD, CMP, DIR) \
-    hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, UPD, CMP, DIR>), grid, block, 0, stream, a)
-#define SOBFU_LAUNCH_BX(DIR, HLV, NTV, PIP) \
-    hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, DIR, true, HLV, NTV, PIP>), grid, block, 0, stream, a)
-    if (direct) {
-        if (updates && compact) SOBFU_LAUNCH_B(true, true, true);
-        else if (updates) SOBFU_LAUNCH_B(true, false, true);
-        else if (compact && idx32) {
-            if (resident && pipe) SOBFU_LAUNCH_BX(true, 0, 0, true);
-            else if (resident) SOBFU_LAUNCH_BX(true, 0, 0, false);
-            else if (pipe) SOBFU_LAUNCH_BX(true, 0, kNT, true);
-            else if (ntbuf) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, true, true, 0, kNT, false, true>), grid, block, 0, stream, a);
-            else SOBFU_LAUNCH_BX(true, 0, kNT, false);
-        }
-        else if (compact) SOBFU_LAUNCH_B(false, true, true);
-        else SOBFU_LAUNCH_B(false, false, true);
-    } else {
-        if (updates && compact) SOBFU_LAUNCH_B(true, true, false);
-        else if (updates) SOBFU_LAUNCH_B(true, false, false);
-        else if (compact && idx32) {
-            // long marches (big grids): halo requests run SOBFU_HLEAD planes ahead; short ones (small grids, multi-GPU tiles) skip
-            // the extra prologue round trip
-            const bool lead = SOBFU_HLEAD > 0 && zc_max >= SOBFU_HLEAD_MIN_ZC && !resident && !pipe;
-            if (!apply && lead) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, SOBFU_HLEAD, kNT, false, true, false>), grid, block, 0, stream, a);
-            else if (!apply) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, 0, kNT, false, true, false>), grid, block, 0, stream, a);
-            else if (lead && ntbuf) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, SOBFU_HLEAD, kNT, false, true>), grid, block, 0, stream, a);
-            else if (lead) SOBFU_LAUNCH_BX(false, SOBFU_HLEAD, kNT, false);
-            else if (resident && pipe) SOBFU_LAUNCH_BX(false, 0, 0, true);
-            else if (resident) SOBFU_LAUNCH_BX(false, 0, 0, false);
-            else if (pipe) SOBFU_LAUNCH_BX(false, 0, kNT, true);
-            else if (ntbuf) hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, false, true, false, true, 0, kNT, false, true>), grid, block, 0, stream, a);
-            else SOBFU_LAUNCH_BX(false, 0, kNT, false);
-        }
-        else if (compact) SOBFU_LAUNCH_B(false, true, false);
-        else SOBFU_LAUNCH_B(false, false, false);
-    }
-#undef SOBFU_LAUNCH_BX
-#undef SOBFU_LAUNCH_B
-    return (int) hipGetLastError();
-}
-
-// z-range forms (whole x-y planes of the array): the single-GPU solver and the z-slab loop
-int launch_pass_a(const float* pnp, const float* pg, const float* psi, float* nU, float w_reg, int X, int Y, int Z,
-                  const uint32_t* prev_slots, float max_update_norm, int zc, hipStream_t stream, bool compact, int z_lo, int z_hi,
-                  int z_lo2, int z_hi2, bool warp) {
-    if (z_hi <= 0 && z_hi2 <= z_lo2) { z_lo = 0; z_hi = Z; }  // no range given: the whole grid
-    const LaunchBox b[2] = {{0, X, 0, Y, z_lo, z_hi, false}, {0, X, 0, Y, z_lo2, z_hi2, false}};
-    return launch_pass_a_boxes(pnp, pg, psi, nU, w_reg, X, Y, Z, b, 2, prev_slots, max_update_norm, zc, stream, compact, warp);
-}
-
-int launch_pass_b(const float* nU, float* psi, const float* phi_n, float* pnp, float* updates, uint32_t* slots,
-                  const float taps[7], float alpha, int X, int Y, int Z, const uint32_t* prev_slots,
-                  float max_update_norm, int zc, hipStream_t stream, int phi_Z, int own_lo, int own_hi, bool compact, int z_lo,
-                  int z_hi, int z_lo2, int z_hi2, float* psi_out, int prev_rows, bool apply) {
-    if (phi_Z <= 0) { phi_Z = Z; own_lo = 0; own_hi = Z; }
-    if (z_hi <= 0 && z_hi2 <= z_lo2) { z_lo = 0; z_hi = Z; }  // no range given: the whole grid
-    const LaunchBox b[2] = {{0, X, 0, Y, z_lo, z_hi, false}, {0, X, 0, Y, z_lo2, z_hi2, false}};
-    const int own[6] = {0, X, 0, Y, own_lo, own_hi};
-    return launch_pass_b_boxes(nU, psi, phi_n, pnp, updates, slots, taps, alpha, X, Y, Z, X, Y, phi_Z, own, b, 2, prev_slots, max_update_norm, zc,
-                               stream, compact, psi_out, prev_rows, false, apply);
+    const bool found = launch_row(kPassBTable, v, [&](auto i) {
+        constexpr PassBVariant V = kPassBTable[decltype(i)::value];
+        hipLaunchKernelGGL((fused_smooth_update_apply_kernel<kRPT, kWY, V.updates, V.compact, V.direct, V.idx32, V.lead ? SOBFU_HLEAD : 0,
+                                                             V.nt ? kNT : 0, V.pipe, V.ntbuf, V.apply>),
+                           grid, block, 0, stream, a);
+    });
+    return found ? (int) hipGetLastError() : SOBFU_E_UNSUPPORTED;
 }
 
 #define SOBFU_LIN(N) dim3((unsigned) (((N) + 255) / 256)), dim3(256), 0, stream
@@ -464,7 +402,10 @@ int sobfu_hip_fused_potential_gradient(const float* d_phi_n_psi, const float* d_
                                        float* d_nabla_U, float w_reg, int X, int Y, int Z, void* stream) {
     SOBFU_CHECK_ARGS(d_phi_n_psi && d_phi_global && d_psi && d_nabla_U && X > 1 && Y > 1 && Z > 1);
     if ((size_t) X * Y * Z > (size_t) 0x7fffffff) return SOBFU_E_UNSUPPORTED;
-    return sobfu_hip::launch_pass_a(d_phi_n_psi, d_phi_global, d_psi, d_nabla_U, w_reg, X, Y, Z, nullptr, 0.f, 0, (hipStream_t) stream, false, 0, 0);
+    sobfu_hip::PassALaunch L;
+    sobfu_hip::set_whole_grid(L, X, Y, Z);
+    L.pnp = d_phi_n_psi; L.pg = d_phi_global; L.psi = d_psi; L.nU = d_nabla_U; L.w_reg = w_reg;
+    return sobfu_hip::launch_pass_a(L, (hipStream_t) stream);
 }
 
 int sobfu_hip_fused_smooth_update_apply(const float* d_nabla_U, float* d_psi, const float* d_phi_n, float* d_phi_n_psi,
@@ -472,8 +413,11 @@ int sobfu_hip_fused_smooth_update_apply(const float* d_nabla_U, float* d_psi, co
                                         int X, int Y, int Z, void* stream) {
     SOBFU_CHECK_ARGS(d_nabla_U && d_psi && d_phi_n && d_phi_n_psi && d_max_sq_slots && taps && X > 0 && Y > 0 && Z > 0);
     if ((size_t) X * Y * Z > (size_t) 0x7fffffff) return SOBFU_E_UNSUPPORTED;
-    return sobfu_hip::launch_pass_b(d_nabla_U, d_psi, d_phi_n, d_phi_n_psi, d_updates, d_max_sq_slots, taps, alpha, X, Y, Z,
-                                    nullptr, 0.f, 0, (hipStream_t) stream, 0, 0, 0, false, 0, 0);
+    sobfu_hip::PassBLaunch L;
+    sobfu_hip::set_whole_grid(L, X, Y, Z);
+    L.nU = d_nabla_U; L.psi = d_psi; L.phi_n = d_phi_n; L.pnp = d_phi_n_psi; L.updates = d_updates; L.slots = d_max_sq_slots;
+    L.taps = taps; L.alpha = alpha;
+    return sobfu_hip::launch_pass_b(L, (hipStream_t) stream);
 }
 
 int sobfu_hip_pack_vec3(const float* d_src4, float* d_dst3, size_t n, void* stream) {
@@ -498,9 +442,14 @@ int sobfu_hip_tile3_potential_gradient(const float* d_phi_n_psi, const float* d_
                                        float max_update_norm, int compact, void* stream) {
     SOBFU_CHECK_ARGS(d_phi_n_psi && d_phi_global && d_psi && d_nabla_U && Lx > 1 && Ly > 1 && Lz > 1 && box && box_ok(box, Lx, Ly, Lz));
     if ((size_t) Lx * Ly * Lz > (size_t) 0x7fffffff) return SOBFU_E_UNSUPPORTED;
-    const sobfu_hip::LaunchBox b{box[0], box[1], box[2], box[3], box[4], box[5], thin != 0};
-    return sobfu_hip::launch_pass_a_boxes(d_phi_n_psi, d_phi_global, d_psi, d_nabla_U, w_reg, Lx, Ly, Lz, &b, 1, d_prev_slots, max_update_norm, 0,
-                                          (hipStream_t) stream, compact != 0);
+    sobfu_hip::PassALaunch L;
+    L.pnp = d_phi_n_psi; L.pg = d_phi_global; L.psi = d_psi; L.nU = d_nabla_U; L.w_reg = w_reg;
+    L.X = Lx; L.Y = Ly; L.Z = Lz;
+    L.boxes[0] = sobfu_hip::LaunchBox{box[0], box[1], box[2], box[3], box[4], box[5], thin != 0};
+    L.n_boxes = 1;
+    L.prev_slots = d_prev_slots; L.max_update_norm = max_update_norm;
+    L.compact = compact != 0;
+    return sobfu_hip::launch_pass_a(L, (hipStream_t) stream);
 }
 
 int sobfu_hip_tile3_smooth_update_apply(const float* d_nabla_U, float* d_psi, const float* d_phi_n, float* d_phi_n_psi, float* d_updates,
@@ -510,9 +459,17 @@ int sobfu_hip_tile3_smooth_update_apply(const float* d_nabla_U, float* d_psi, co
     SOBFU_CHECK_ARGS(d_nabla_U && d_psi && d_phi_n && d_phi_n_psi && d_max_sq_slots && taps && Lx > 0 && Ly > 0 && Lz > 0 && Xg > 0 && Yg > 0 &&
                      Zg > 0 && own && box && box_ok(own, Lx, Ly, Lz) && box_ok(box, Lx, Ly, Lz));
     if ((size_t) Lx * Ly * Lz > (size_t) 0x7fffffff || (size_t) Xg * Yg * Zg > (size_t) 0x7fffffff) return SOBFU_E_UNSUPPORTED;
-    const sobfu_hip::LaunchBox b{box[0], box[1], box[2], box[3], box[4], box[5], thin != 0};
-    return sobfu_hip::launch_pass_b_boxes(d_nabla_U, d_psi, d_phi_n, d_phi_n_psi, d_updates, d_max_sq_slots, taps, alpha, Lx, Ly, Lz, Xg, Yg, Zg,
-                                          own, &b, 1, d_prev_slots, max_update_norm, 0, (hipStream_t) stream, compact != 0);
+    sobfu_hip::PassBLaunch L;
+    L.nU = d_nabla_U; L.psi = d_psi; L.phi_n = d_phi_n; L.pnp = d_phi_n_psi; L.updates = d_updates; L.slots = d_max_sq_slots;
+    L.taps = taps; L.alpha = alpha;
+    L.X = Lx; L.Y = Ly; L.Z = Lz;
+    L.pX = Xg; L.pY = Yg; L.pZ = Zg;
+    for (int i = 0; i < 6; ++i) L.own[i] = own[i];
+    L.boxes[0] = sobfu_hip::LaunchBox{box[0], box[1], box[2], box[3], box[4], box[5], thin != 0};
+    L.n_boxes = 1;
+    L.prev_slots = d_prev_slots; L.max_update_norm = max_update_norm;
+    L.compact = compact != 0;
+    return sobfu_hip::launch_pass_b(L, (hipStream_t) stream);
 }
 
 int sobfu_hip_tile3_apply_tsdf_only(const float* d_phi1, int Xg, int Yg, int Zg, float* d_out1, const float* d_psi3, int Lx, int Ly, int Lz,

@@ -653,10 +653,12 @@ int sobfu_hip_tiled_exports_get(const sobfu_hip_tiled* t, sobfu_hip_tiled_export
 int sobfu_hip_tiled_connect(sobfu_hip_tiled* t, int n_peers, const int* peer_ranks, const sobfu_hip_tiled_exports* peers) {
     SOBFU_CHECK_ARGS(t && n_peers >= 0 && (n_peers == 0 || (peer_ranks && peers)) && !t->q.active && !t->comm);
     if (t->world > kMaxSync) return SOBFU_E_UNSUPPORTED;
-    // Cells other GPUs stored are read at system scope, which only the pipelined march of pass B does (launch_pass_b_boxes): it needs
-    // 32-bit gather offsets (phi_n below 2^30 voxels) and buffer addressing (the local arrays below 4 GiB).  Refused HERE, not by a
-    // launch in the middle of a solve whose pass A has already pushed into the peers.
-    if ((size_t) t->X * t->Y * t->Z >= ((size_t) 1 << 30) || (size_t) t->L[0] * t->L[1] * t->L[2] * 12 >= ((size_t) 1 << 32)) return SOBFU_E_UNSUPPORTED;
+    // Cells other GPUs stored are read at system scope, which only the pipelined march of pass B does (sobfu_hip::pass_b_march): it
+    // needs 32-bit gather offsets (phi_n below 2^30 voxels) and buffer addressing (the local arrays below 4 GiB).  Refused HERE, not by
+    // a launch in the middle of a solve whose pass A has already pushed into the peers.
+    sobfu_hip::PassBMarch m;
+    const sobfu_hip::PassBAsk connected{true, false, true, true};
+    if (sobfu_hip::pass_b_march(sobfu_hip::grid_traits(t->L[0], t->L[1], t->L[2], t->X, t->Y, t->Z, 0), connected, &m) != 0) return SOBFU_E_UNSUPPORTED;
     if (t->grows_own) {  // a longer solve on the unconnected handle moved the rows to a private array: back to the exported ones
         SOBFU_HIP_TRY(hipFree(t->grows_own));
         if (t->slots) SOBFU_HIP_TRY(hipFree(t->slots));
@@ -1059,7 +1061,6 @@ static int tiled_step_impl(sobfu_hip_tiled* t, int n_steps, hipStream_t st, int 
     // timing experiments only (results are wrong): bit 0 no push boxes, bit 1 no thin shells, bit 2 no pass A, bit 3 no pass B,
     // bit 4 no owned block in pass B, bit 5 no y shells, bit 6 no x shells; in build_a_boxes: bit 7 no thin push boxes (x faces, edges,
     // corners), bit 8 no marched push boxes (y / z faces), bit 9 the marched push boxes store at home only
-    const bool b_direct = false;
     const int dbg = t->debug_skip;
     // pass A split into boundary + interior launches so that the exchange starts after 4 planes per face instead of after
     // the whole pass: an extra launch (+6-7 us per iteration in the compute-only timing at N = 4 and 8), worth it only where
@@ -1084,20 +1085,35 @@ static int tiled_step_impl(sobfu_hip_tiled* t, int n_steps, hipStream_t st, int 
         const uint32_t* prev = (it > 2 && can_converge) ? rows + (size_t) (it - 2) * kSlots : nullptr;  // the late gate
         uint32_t* row        = t->slots + (size_t) it * kSlots;
         auto A = [&](int za, int zb, int za2 = 0, int zb2 = 0) {  // pass A writes scratch only: never gated
-            const sobfu_hip::LaunchBox bx[2] = {{ax0, ax1, ay0, ay1, za, zb, false}, {ax0, ax1, ay0, ay1, za2, zb2, false}};
-            return sobfu_hip::launch_pass_a_boxes(f_in, t->c_g, psi_in, nu, p.w_reg, Lx, Ly, Lz, bx, 2, nullptr, 0.f, 0, st, true);
+            sobfu_hip::PassALaunch L;
+            L.pnp = f_in; L.pg = t->c_g; L.psi = psi_in; L.nU = nu; L.w_reg = p.w_reg;
+            L.X = Lx; L.Y = Ly; L.Z = Lz;
+            L.boxes[0] = {ax0, ax1, ay0, ay1, za, zb, false};
+            L.boxes[1] = {ax0, ax1, ay0, ay1, za2, zb2, false};
+            L.n_boxes  = 2;
+            L.compact  = true;
+            return sobfu_hip::launch_pass_a(L, st);
         };
         auto B = [&](int za, int zb, int za2 = 0, int zb2 = 0, bool shells = false) {
             // the owned block with its z shells (extra planes of the march); the one-cell x / y shells are direct boxes
             const bool ysh = shells && !(dbg & 32), xsh = shells && !(dbg & 64);
-            const sobfu_hip::LaunchBox bx[6] = {{ax0, ax1, ay0, ay1, za, (dbg & 16) ? za : zb, b_direct}, {ax0, ax1, ay0, ay1, za2, zb2, b_direct},
-                                                {ax0, ax1, ay0 - 1, (ysh && t->lo[1]) ? ay0 : ay0 - 1, lo, hi, true},
-                                                {ax0, ax1, ay1, (ysh && t->hi[1]) ? ay1 + 1 : ay1, lo, hi, true},
-                                                {ax0 - 1, (xsh && t->lo[0]) ? ax0 : ax0 - 1, ay0, ay1, lo, hi, true},
-                                                {ax1, (xsh && t->hi[0]) ? ax1 + 1 : ax1, ay0, ay1, lo, hi, true}};
-            return sobfu_hip::launch_pass_b_boxes(nu, const_cast<float*>(psi_in), t->c_n, f_out, nullptr, row, t->taps, p.alpha, Lx, Ly, Lz, X, Y,
-                                                  Z, own, bx, 6, prev, p.max_update_norm, 0, st, true, psi_out, it > 3 ? 2 : 1,
-                                                  sync /* direct transport (and the handles that time its launches): peer-written cells are read at system scope */);
+            sobfu_hip::PassBLaunch L;
+            L.nU = nu; L.psi = const_cast<float*>(psi_in); L.psi_out = psi_out; L.phi_n = t->c_n; L.pnp = f_out; L.slots = row;
+            L.taps = t->taps; L.alpha = p.alpha;
+            L.X = Lx; L.Y = Ly; L.Z = Lz;
+            L.pX = X; L.pY = Y; L.pZ = Z;
+            for (int i = 0; i < 6; ++i) L.own[i] = own[i];
+            L.boxes[0] = {ax0, ax1, ay0, ay1, za, (dbg & 16) ? za : zb, false};
+            L.boxes[1] = {ax0, ax1, ay0, ay1, za2, zb2, false};
+            L.boxes[2] = {ax0, ax1, ay0 - 1, (ysh && t->lo[1]) ? ay0 : ay0 - 1, lo, hi, true};
+            L.boxes[3] = {ax0, ax1, ay1, (ysh && t->hi[1]) ? ay1 + 1 : ay1, lo, hi, true};
+            L.boxes[4] = {ax0 - 1, (xsh && t->lo[0]) ? ax0 : ax0 - 1, ay0, ay1, lo, hi, true};
+            L.boxes[5] = {ax1, (xsh && t->hi[0]) ? ax1 + 1 : ax1, ay0, ay1, lo, hi, true};
+            L.n_boxes  = 6;
+            L.prev_slots = prev; L.max_update_norm = p.max_update_norm; L.prev_rows = it > 3 ? 2 : 1;
+            L.compact     = true;
+            L.sys_acquire = sync;  // direct transport (and the handles that time its launches): peer-written cells are read at system scope
+            return sobfu_hip::launch_pass_b(L, st);
         };
         auto wait_gate = [&]() -> int {  // row it-2 must be global before the first pass-B launch of this iteration
             if (prev && red_issued[it & 1]) SOBFU_HIP_TRY(hipStreamWaitEvent(st, t->ev_red[it & 1], 0));
