@@ -16,9 +16,13 @@
 // fused through psi: --mesh writes per-vertex colours for phi_global and phi_global_psi_inv, the phi_global / phi_global_psi_inv
 // screenshot panels are coloured (the live panels of --screenshots-detailed stay grey) and --dump adds colour_global.npy (Z, Y, X, 4)
 // uint8 (b, g, r, weight).  Without colour frames every output is the geometry-only one.
+// Camera tracking (opt-in): --track (or TRACK_CAMERA=1 in the .ini) estimates each frame's camera pose with projective ICP against the
+// model raycast at the previous pose before the non-rigid solve, and integrates the frame at that pose; the screenshots are then drawn
+// from the current tracked pose.  --poses FILE writes one TUM-format line per frame, "frame tx ty tz qx qy qz qw" (identity without
+// tracking).
 //
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
-//                  [--screenshots DIR [--screenshots-detailed]]
+//                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
 //                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | frame0.pgm frame1.pgm ...)
 #include <dirent.h>
 #include <sys/stat.h>
@@ -111,12 +115,13 @@ struct Screenshots {
         rgb.resize(bgra.size() * 3);
     }
     // shades `v` (or leaves the panel black when v is null) into panel (pr, pc), in colour when `colour` is given
-    void panel(kfusion::cuda::TsdfVolume* v, const kfusion::Intr& intr, int pr, int pc, const kfusion::cuda::ColourVolume* colour = nullptr) {
+    void panel(kfusion::cuda::TsdfVolume* v, const cv::Affine3f& pose, const kfusion::Intr& intr, int pr, int pc,
+               const kfusion::cuda::ColourVolume* colour = nullptr) {
         if (!v) return;
-        v->raycast(cv::Affine3f::Identity(), intr, points, normals);  // the depth camera (SobFusion's camera_pose_)
+        v->raycast(pose, intr, points, normals);  // the depth camera (SobFusion's camera_pose_: identity unless tracking)
         uint8_t* dst = (uint8_t*) image.ptr() + (size_t) pr * rows * image.step() + (size_t) pc * cols * sizeof(kfusion::RGB);
         if (colour) {
-            colour->sample(points, normals, cv::Affine3f::Identity().inv() * v->getPose(), v->getVoxelSize(), colours);
+            colour->sample(points, normals, pose.inv() * v->getPose(), v->getVoxelSize(), colours);
             sobfuSafeCall(sobfu_hip_render_colour((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
                                                   (const uint8_t*) colours.ptr(), (int) colours.step(), rows, cols, 0.f, 0.f, 0.f, dst,
                                                   (int) image.step(), nullptr));
@@ -128,11 +133,12 @@ struct Screenshots {
     bool write(int frame, SobFusion& fusion, bool solved, const kfusion::Intr& intr) {
         if (points.empty()) create(fusion.getParams().rows, fusion.getParams().cols);
         sobfuSafeCall(hipMemset2D(image.ptr(), image.step(), 0, (size_t) image.cols() * sizeof(kfusion::RGB), image.rows()));
-        panel(fusion.phi_global.get(), intr, detailed ? 1 : 0, 0, fusion.colour_global.get());
-        panel(solved ? fusion.phi_global_psi_inv.get() : nullptr, intr, 0, 1, solved ? fusion.get_colour_global_psi_inv().get() : nullptr);
+        const cv::Affine3f pose = fusion.getCameraPose();
+        panel(fusion.phi_global.get(), pose, intr, detailed ? 1 : 0, 0, fusion.colour_global.get());
+        panel(solved ? fusion.phi_global_psi_inv.get() : nullptr, pose, intr, 0, 1, solved ? fusion.get_colour_global_psi_inv().get() : nullptr);
         if (detailed) {
-            panel(frame > 0 ? fusion.phi_n.get() : nullptr, intr, 0, 0);
-            panel(solved ? fusion.phi_n_psi.get() : nullptr, intr, 1, 1);
+            panel(frame > 0 ? fusion.phi_n.get() : nullptr, pose, intr, 0, 0);
+            panel(solved ? fusion.phi_n_psi.get() : nullptr, pose, intr, 1, 1);
         }
         image.download(bgra.data(), (size_t) image.cols() * sizeof(kfusion::RGB));
         for (size_t i = 0; i < bgra.size(); ++i) {
@@ -149,7 +155,7 @@ struct Screenshots {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -162,7 +168,7 @@ int main(int argc, char** argv) {
     int synthetic = 0;
     double shift = 0.005;
     bool textured = false;
-    std::string dump, mesh_dir, data_dir, mesh_format = "vtk";
+    std::string dump, mesh_dir, data_dir, mesh_format = "vtk", poses_path;
     Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
     std::vector<std::string> files;
@@ -182,6 +188,8 @@ int main(int argc, char** argv) {
         else if (a == "--no-stats") print_stats = false;
         else if (a == "--screenshots" && i + 1 < argc) shots.dir = argv[++i];
         else if (a == "--screenshots-detailed") shots.detailed = true;
+        else if (a == "--track") p.track_camera = true;
+        else if (a == "--poses" && i + 1 < argc) poses_path = argv[++i];
         else files.push_back(a);
     }
     if (mesh_format != "vtk" && mesh_format != "ply") {
@@ -304,6 +312,34 @@ int main(int argc, char** argv) {
                 std::printf("solver: iterations=%d converged=%d last_max_update_norm=%g\n", r.iterations, r.converged, r.last_max_update_norm);
             }
         }
+    }
+    if (!poses_path.empty()) {  // TUM trajectory format: frame tx ty tz qx qy qz qw
+        FILE* f = std::fopen(poses_path.c_str(), "w");
+        if (!f) {
+            std::printf("cannot write %s\n", poses_path.c_str());
+            return 2;
+        }
+        const std::vector<cv::Affine3f>& poses = fusion.getPoses();
+        for (size_t n = 0; n < poses.size(); ++n) {
+            const float* R = poses[n].R;
+            double q[4];  // x, y, z, w from the rotation matrix (Shepperd's branch on the largest diagonal term)
+            const double tr = (double) R[0] + R[4] + R[8];
+            if (tr > 0) {
+                const double s = std::sqrt(tr + 1.0) * 2;
+                q[3] = 0.25 * s, q[0] = (R[7] - R[5]) / s, q[1] = (R[2] - R[6]) / s, q[2] = (R[3] - R[1]) / s;
+            } else if (R[0] > R[4] && R[0] > R[8]) {
+                const double s = std::sqrt(1.0 + R[0] - R[4] - R[8]) * 2;
+                q[3] = (R[7] - R[5]) / s, q[0] = 0.25 * s, q[1] = (R[1] + R[3]) / s, q[2] = (R[2] + R[6]) / s;
+            } else if (R[4] > R[8]) {
+                const double s = std::sqrt(1.0 + R[4] - R[0] - R[8]) * 2;
+                q[3] = (R[2] - R[6]) / s, q[0] = (R[1] + R[3]) / s, q[1] = 0.25 * s, q[2] = (R[5] + R[7]) / s;
+            } else {
+                const double s = std::sqrt(1.0 + R[8] - R[0] - R[4]) * 2;
+                q[3] = (R[3] - R[1]) / s, q[0] = (R[2] + R[6]) / s, q[1] = (R[5] + R[7]) / s, q[2] = 0.25 * s;
+            }
+            std::fprintf(f, "%zu %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", n, poses[n].t[0], poses[n].t[1], poses[n].t[2], q[0], q[1], q[2], q[3]);
+        }
+        std::fclose(f);
     }
     if (!dump.empty() && fusion.psi) {  // .npy dumps (replace the reference's commented-out .vti writer, demo.cpp:252-283)
         cv::Vec3i d = p.volume_dims;

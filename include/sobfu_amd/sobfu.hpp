@@ -179,6 +179,11 @@ struct Params {
     int verbosity = 0;
     int s = 7, max_iter = 0;
     float max_update_norm = 0.f, lambda = 0.1f, alpha = 0.f, w_reg = 0.f;
+    // camera tracking (opt-in; KinFuParams' icp_* fields, include/kfusion/kinfu.hpp): projective ICP ahead of the non-rigid solve
+    bool track_camera = false;
+    float icp_dist_thres = 0.1f;                          // metres
+    float icp_angle_thres = 30.f * 0.017453293f;          // radians (KinFuParams::default_params: 30 degrees)
+    std::vector<int> icp_iter_num = {10, 5, 4, 0};        // iterations per pyramid level, finest first
     cv::Vec3f voxel_sizes() const {
         return cv::Vec3f(volume_size[0] / volume_dims[0], volume_size[1] / volume_dims[1], volume_size[2] / volume_dims[2]);
     }
@@ -396,6 +401,130 @@ inline void computeDists(const Depth& depth, Dists& dists, const Intr& intr) {
     sobfuSafeCall(sobfu_hip_compute_dists(depth.ptr(), (int) depth.step(), dists.ptr(), (int) dists.step(), depth.rows(),
                                           depth.cols(), intr.fx, intr.fy, intr.cx, intr.cy, nullptr));
 }
+
+// ---- camera-tracking image helpers (include/kfusion/cuda/imgproc.hpp:15-26; rules in sobfu_amd/csrc/icp_kernels.hip) ---------------
+// Invalid pixels are NaN; the outputs are (re)created at the size each function produces.
+inline void depthBuildPyramid(const Depth& depth, Depth& pyramid, float sigma_depth) {
+    pyramid.create(depth.rows() / 2, depth.cols() / 2);
+    sobfuSafeCall(sobfu_hip_depth_pyramid(depth.ptr(), (int) depth.step(), depth.rows(), depth.cols(), pyramid.ptr(), (int) pyramid.step(),
+                                          sigma_depth, nullptr));
+}
+inline void computeNormalsAndMaskDepth(const Intr& intr, Depth& depth, Normals& normals) {
+    normals.create(depth.rows(), depth.cols());
+    sobfuSafeCall(sobfu_hip_compute_normals_mask_depth(depth.ptr(), (int) depth.step(), depth.rows(), depth.cols(), intr.fx, intr.fy, intr.cx, intr.cy,
+                                                       (float*) normals.ptr(), (int) normals.step(), nullptr));
+}
+inline void computePointNormals(const Intr& intr, const Depth& depth, Cloud& points, Normals& normals) {
+    points.create(depth.rows(), depth.cols());
+    normals.create(depth.rows(), depth.cols());
+    sobfuSafeCall(sobfu_hip_compute_point_normals(depth.ptr(), (int) depth.step(), depth.rows(), depth.cols(), intr.fx, intr.fy, intr.cx, intr.cy,
+                                                  (float*) points.ptr(), (int) points.step(), (float*) normals.ptr(), (int) normals.step(), nullptr));
+}
+inline void resizeDepthNormals(const Depth& depth, const Normals& normals, Depth& depth_out, Normals& normals_out) {
+    depth_out.create(depth.rows() / 2, depth.cols() / 2);
+    normals_out.create(depth.rows() / 2, depth.cols() / 2);
+    sobfuSafeCall(sobfu_hip_resize_depth_normals(depth.ptr(), (int) depth.step(), (const float*) normals.ptr(), (int) normals.step(), depth.rows(),
+                                                 depth.cols(), depth_out.ptr(), (int) depth_out.step(), (float*) normals_out.ptr(),
+                                                 (int) normals_out.step(), nullptr));
+}
+inline void resizePointsNormals(const Cloud& points, const Normals& normals, Cloud& points_out, Normals& normals_out) {
+    points_out.create(points.rows() / 2, points.cols() / 2);
+    normals_out.create(points.rows() / 2, points.cols() / 2);
+    sobfuSafeCall(sobfu_hip_resize_points_normals((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(),
+                                                  points.rows(), points.cols(), (float*) points_out.ptr(), (int) points_out.step(),
+                                                  (float*) normals_out.ptr(), (int) normals_out.step(), nullptr));
+}
+
+// include/kfusion/types.hpp:90-96
+struct Frame {
+    bool use_points = false;
+    std::vector<Depth> depth_pyr;
+    std::vector<Cloud> points_pyr;
+    std::vector<Normals> normals_pyr;
+};
+
+// ---- ProjectiveICP (include/kfusion/cuda/projective_icp.hpp, src/kfusion/projective_icp.cpp) -----------------------------------------
+// The whole coarse-to-fine loop runs on the device (sobfu_hip_icp_estimate): an estimate enqueues two launches per iteration on the
+// null stream and synchronises ONCE, to read the pose and the status.  The pose maps the current frame into the previous one.
+class ProjectiveICP {
+public:
+    enum { MAX_PYRAMID_LEVELS = 4 };
+    typedef std::vector<Depth> DepthPyr;
+    typedef std::vector<Cloud> PointsPyr;
+    typedef std::vector<Normals> NormalsPyr;
+
+    ProjectiveICP() : angle_thres_(20.f * 0.017453293f), dist_thres_(0.1f) {
+        setIterationsNum(std::vector<int>{10, 5, 4, 0});
+        workspace_.create(sobfu_hip_icp_workspace_bytes() + 16 * sizeof(float) + 4 * sizeof(int));
+    }
+    virtual ~ProjectiveICP() {}
+    float getDistThreshold() const { return dist_thres_; }
+    void setDistThreshold(float distance) { dist_thres_ = distance; }
+    float getAngleThreshold() const { return angle_thres_; }
+    void setAngleThreshold(float angle) { angle_thres_ = angle; }
+    void setIterationsNum(const std::vector<int>& iters) {
+        iters_.assign(MAX_PYRAMID_LEVELS, 0);
+        for (size_t i = 0; i < iters.size() && i < (size_t) MAX_PYRAMID_LEVELS; ++i) iters_[i] = iters[i];
+    }
+    int getUsedLevelsNum() const {
+        int i = MAX_PYRAMID_LEVELS - 1;
+        for (; i >= 0 && !iters_[i]; --i) {}
+        return i + 1;
+    }
+    // dispatches on curr.use_points (the reference leaves this overload unimplemented)
+    virtual bool estimateTransform(Affine3f& affine, const Intr& intr, const Frame& curr, const Frame& prev) {
+        if (curr.use_points) return estimateTransform(affine, intr, curr.points_pyr, curr.normals_pyr, prev.points_pyr, prev.normals_pyr);
+        return estimateTransform(affine, intr, curr.depth_pyr, curr.normals_pyr, prev.depth_pyr, prev.normals_pyr);
+    }
+    // masked depth (computeNormalsAndMaskDepth) and its normals; depth is reprojected with the level's intrinsics
+    virtual bool estimateTransform(Affine3f& affine, const Intr& intr, const DepthPyr& dcurr, const NormalsPyr ncurr, const DepthPyr dprev,
+                                   const NormalsPyr nprev) {
+        return run(affine, intr, 1, [&](int l) {
+            return sobfu_hip_icp_level{dcurr[l].ptr(), (int) dcurr[l].step(), (const float*) ncurr[l].ptr(), (int) ncurr[l].step(), dprev[l].ptr(),
+                                       (int) dprev[l].step(), (const float*) nprev[l].ptr(), (int) nprev[l].step(), nprev[l].rows(), nprev[l].cols()};
+        }, std::min(std::min(dcurr.size(), ncurr.size()), std::min(dprev.size(), nprev.size())));
+    }
+    virtual bool estimateTransform(Affine3f& affine, const Intr& intr, const PointsPyr& vcurr, const NormalsPyr ncurr, const PointsPyr vprev,
+                                   const NormalsPyr nprev) {
+        return run(affine, intr, 0, [&](int l) {
+            return sobfu_hip_icp_level{vcurr[l].ptr(), (int) vcurr[l].step(), (const float*) ncurr[l].ptr(), (int) ncurr[l].step(), vprev[l].ptr(),
+                                       (int) vprev[l].step(), (const float*) nprev[l].ptr(), (int) nprev[l].step(), nprev[l].rows(), nprev[l].cols()};
+        }, std::min(std::min(vcurr.size(), ncurr.size()), std::min(vprev.size(), nprev.size())));
+    }
+    // (level, iteration) of the last failed estimate's singular system; (-1, -1) after a successful one
+    int lastFailedLevel() const { return status_ ? (status_ >> 8) & 0xFF : -1; }
+    int lastFailedIteration() const { return status_ ? status_ & 0xFF : -1; }
+
+private:
+    template <class F>
+    bool run(Affine3f& affine, const Intr& intr, int depth_mode, F level, size_t available) {
+        const int n = getUsedLevelsNum();
+        affine = Affine3f::Identity();
+        if (n < 1 || available < (size_t) n) error("ProjectiveICP: fewer pyramid levels than iterations need", __FILE__, __LINE__);
+        sobfu_hip_icp_level lv[MAX_PYRAMID_LEVELS];
+        for (int l = 0; l < n; ++l) lv[l] = level(l);
+        char* ws = workspace_.ptr<char>();
+        const size_t wsb = sobfu_hip_icp_workspace_bytes();
+        float* d_pose = (float*) (ws + wsb);
+        int* d_status = (int*) (ws + wsb + 16 * sizeof(float));
+        sobfuSafeCall(sobfu_hip_icp_estimate(lv, n, iters_.data(), depth_mode, intr.fx, intr.fy, intr.cx, intr.cy, dist_thres_, angle_thres_, ws, wsb,
+                                             d_pose, d_status, nullptr, nullptr));
+        float P[16];
+        sobfuSafeCall(hipMemcpy(P, d_pose, sizeof P, hipMemcpyDeviceToHost));  // the one synchronisation of the estimate
+        sobfuSafeCall(hipMemcpy(&status_, d_status, sizeof status_, hipMemcpyDeviceToHost));
+        if (status_ != 0) return false;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) affine.R[3 * i + j] = P[4 * i + j];
+            affine.t[i] = P[4 * i + 3];
+        }
+        return true;
+    }
+    std::vector<int> iters_;
+    float angle_thres_;
+    float dist_thres_;
+    DeviceMemory workspace_;  // partial sums | pose (16 floats) | status
+    int status_ = 0;
+};
 }  // namespace cuda
 
 // ---- device PODs + launchers (include/kfusion/internal.hpp:59-78,189-198) ----------------------------------------
@@ -1069,6 +1198,23 @@ inline bool read_params_ini(const std::string& path, Params& p, std::map<std::st
     I("START_FRAME", p.start_frame); I("MAX_ITER", p.max_iter);
     F("MAX_UPDATE_NORM", p.max_update_norm);
     I("S", p.s); F("LAMBDA", p.lambda); F("ALPHA", p.alpha); F("W_REG", p.w_reg);
+    {  // camera tracking (optional keys): TRACK_CAMERA (0 / 1), ICP_DIST_THRES (metres), ICP_ANGLE_THRES (degrees), ICP_ITERS (e.g. 10,5,4)
+        int track = p.track_camera ? 1 : 0;
+        I("TRACK_CAMERA", track);
+        p.track_camera = track != 0;
+        F("ICP_DIST_THRES", p.icp_dist_thres);
+        auto it = kv.find("ICP_ANGLE_THRES");
+        if (it != kv.end()) p.icp_angle_thres = std::strtof(it->second.c_str(), nullptr) * 0.017453293f;
+        it = kv.find("ICP_ITERS");
+        if (it != kv.end()) {
+            std::vector<int> iters;
+            std::stringstream ss(it->second);
+            std::string tok;
+            while (std::getline(ss, tok, ',')) iters.push_back((int) std::strtol(tok.c_str(), nullptr, 10));
+            iters.resize(4, 0);
+            p.icp_iter_num = iters;
+        }
+    }
     float trunc_vox = 0.f, eta_vox = 0.f, tz = 0.f;
     for (const char* k : {"TSDF_TRUNC_DIST", "ETA", "VOL_POSE_T_Z"})
         if (!kv.count(k)) {
@@ -1105,8 +1251,12 @@ public:
         dists_.create(params.rows, params.cols);
         mc = std::make_shared<kfusion::cuda::MarchingCubes>();  // sob_fusion.cpp:35-36
         mc->setPose(params.volume_pose);
+        poses_.reserve(4096);  // sob_fusion.cpp:31-33
     }
     Params& getParams() { return params; }
+    // camera poses (camera -> frame 0's camera) of the frames so far; identities unless params.track_camera
+    const std::vector<cv::Affine3f>& getPoses() const { return poses_; }
+    cv::Affine3f getCameraPose() const { return camera_pose_; }
     // `image` (optional, the reference's signature, sob_fusion.hpp:44): a BGRA colour frame registered to the depth frame, of its size.
     // An empty image is the geometry-only path (no colour allocation, no colour launch); a colour frame is fused into colour_global
     // through the TSDF that is fused into phi_global in this frame (phi_global itself on frame 0) and psi on solved frames.
@@ -1119,6 +1269,8 @@ public:
                                             params.bilateral_sigma_depth);                              // sob_fusion.cpp:78
         kfusion::cuda::depthTruncation(filtered_, params.icp_truncate_depth_dist);                     // :85
         kfusion::cuda::computeDists(filtered_, dists_, params.intr);                                   // :91
+        if (params.track_camera) track();
+        poses_.push_back(camera_pose_);
         if (frame_counter_ == 0) {                                                                     // :93-123
             phi_global = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
             phi_global->integrate(dists_, camera_pose_, params.intr);
@@ -1193,9 +1345,38 @@ private:
         if (!colour_global) colour_global = std::make_shared<kfusion::cuda::ColourVolume>(params.volume_dims);
         colour_global->integrate(image, tsdf, d_psi, camera_pose_, params.intr);
     }
+    // Camera tracking (params.track_camera): the current frame's depth / point / normal pyramids from the filtered depth; on frame n >= 1
+    // projective ICP (points) against the previous frame's pyramids gives aff (frame n -> frame n-1) and pose_n = pose_{n-1} * aff.  The
+    // previous FRAME, not a raycast of the model: the integration stores ray length - camera z (tsdf_kernels.hip), so the model's surface
+    // lies lambda = |ray| / z times too far along each ray, a radial stretch that frame-to-model ICP cannot undo.
+    // A failed estimate keeps pose_{n-1}.
+    void track() {
+        kfusion::cuda::ProjectiveICP probe;
+        probe.setIterationsNum(params.icp_iter_num);
+        const int levels = std::max(1, probe.getUsedLevelsNum());
+        curr_.use_points = prev_.use_points = true;
+        curr_.depth_pyr.resize(levels), curr_.points_pyr.resize(levels), curr_.normals_pyr.resize(levels);
+        curr_.depth_pyr[0] = filtered_;  // shares the block (the pyramid is rebuilt every frame)
+        for (int l = 1; l < levels; ++l) kfusion::cuda::depthBuildPyramid(curr_.depth_pyr[l - 1], curr_.depth_pyr[l], params.bilateral_sigma_depth);
+        for (int l = 0; l < levels; ++l) kfusion::cuda::computePointNormals(params.intr(l), curr_.depth_pyr[l], curr_.points_pyr[l], curr_.normals_pyr[l]);
+        if (frame_counter_ > 0) {
+            if (!icp_) icp_ = std::make_shared<kfusion::cuda::ProjectiveICP>();
+            icp_->setIterationsNum(params.icp_iter_num);
+            icp_->setDistThreshold(params.icp_dist_thres);
+            icp_->setAngleThreshold(params.icp_angle_thres);
+            cv::Affine3f aff;
+            if (icp_->estimateTransform(aff, params.intr, curr_, prev_)) camera_pose_ = camera_pose_ * aff;
+            else std::printf("camera tracking failed on frame %d (level %d, iteration %d): keeping the previous pose\n", frame_counter_,
+                             icp_->lastFailedLevel(), icp_->lastFailedIteration());
+        }
+        std::swap(curr_, prev_);
+    }
     int frame_counter_;
     Params params;
-    cv::Affine3f camera_pose_;  // fixed to identity, sob_fusion.cpp:33
+    cv::Affine3f camera_pose_;  // the current frame's pose: identity (sob_fusion.cpp:33) unless params.track_camera
+    std::vector<cv::Affine3f> poses_;
+    kfusion::cuda::Frame curr_, prev_;
+    std::shared_ptr<kfusion::cuda::ProjectiveICP> icp_;
     kfusion::cuda::Depth filtered_;
     kfusion::cuda::Dists dists_;
 };

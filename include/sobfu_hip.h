@@ -369,6 +369,60 @@ int sobfu_hip_render_colour(const float* d_points, int points_step, const float*
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * camera tracking -- kfusion::cuda::ProjectiveICP (include/kfusion/cuda/projective_icp.hpp, src/kfusion/projective_icp.cpp) and the image
+ * helpers of include/kfusion/cuda/imgproc.hpp it needs (depthBuildPyramid, computePointNormals, computeNormalsAndMaskDepth,
+ * resizeDepthNormals, resizePointsNormals), which the reference declares but never calls.  Depth: pitched uint16 mm; points / normals:
+ * pitched float4 (16-byte aligned); invalid pixels are NaN (the raycaster's all-zero misses are invalid too).  The rules are in
+ * sobfu_amd/csrc/icp_kernels.hip.  Every argument is checked before any device call.
+ * ---------------------------------------------------------------------------------------------------- */
+/* depthBuildPyramid: d_dst is (rows / 2) x (cols / 2); sigma_depth in metres. */
+int sobfu_hip_depth_pyramid(const uint16_t* d_src, int src_step, int rows, int cols, uint16_t* d_dst, int dst_step, float sigma_depth,
+                            void* stream);
+/* computePointNormals: camera-frame points and normals of a depth image with intrinsics (fx, fy, cx, cy). */
+int sobfu_hip_compute_point_normals(const uint16_t* d_depth, int depth_step, int rows, int cols, float fx, float fy, float cx, float cy,
+                                    float* d_points, int points_step, float* d_normals, int normals_step, void* stream);
+/* computeNormalsAndMaskDepth: normals of a depth image; the depth is zeroed in place where the normal is NaN. */
+int sobfu_hip_compute_normals_mask_depth(uint16_t* d_depth, int depth_step, int rows, int cols, float fx, float fy, float cx, float cy,
+                                         float* d_normals, int normals_step, void* stream);
+/* resizeDepthNormals / resizePointsNormals: rows x cols in, (rows / 2) x (cols / 2) out. */
+int sobfu_hip_resize_depth_normals(const uint16_t* d_depth, int depth_step, const float* d_normals, int normals_step, int rows, int cols,
+                                   uint16_t* d_depth_out, int depth_out_step, float* d_normals_out, int normals_out_step, void* stream);
+int sobfu_hip_resize_points_normals(const float* d_points, int points_step, const float* d_normals, int normals_step, int rows, int cols,
+                                    float* d_points_out, int points_out_step, float* d_normals_out, int normals_out_step, void* stream);
+/* One pyramid level of an ICP pair: current and previous frame, both rows x cols.  curr / prev are float4 points (points mode) or uint16
+ * depth (depth mode); ncurr / nprev are float4 normals.  Steps in bytes. */
+typedef struct {
+    const void* curr;
+    int curr_step;
+    const float* ncurr;
+    int ncurr_step;
+    const void* prev;
+    int prev_step;
+    const float* nprev;
+    int nprev_step;
+    int rows, cols;
+} sobfu_hip_icp_level;
+/* Device workspace of sobfu_hip_icp_step / _estimate (the per-workgroup partial sums). */
+size_t sobfu_hip_icp_workspace_bytes(void);
+/* One correspondence + reduction pass of pyramid level `level_index` (intrinsics (fx, fy, cx, cy) / 2^level_index) at the pose d_aff
+ * (16 floats on the device, row-major 4 x 4, maps the current frame into the previous one).  d_sums (device, 29 doubles): the 21
+ * upper-triangular entries of A (row-major), b (6), the inlier count and the sum of squared residuals.  d_codes (optional): rows x cols
+ * uint8 per-pixel codes (0 inlier, 40 invalid source, 80 projects behind / outside, 120 invalid target, 160 too far, 200 angle).
+ * depth_mode: 0 = points, 1 = depth; angle_thres in radians. */
+int sobfu_hip_icp_step(const sobfu_hip_icp_level* level, int level_index, int depth_mode, float fx, float fy, float cx, float cy,
+                       float dist_thres, float angle_thres, const float* d_aff, void* d_workspace, size_t workspace_bytes,
+                       double* d_sums, uint8_t* d_codes, int codes_step, void* stream);
+/* The whole coarse-to-fine estimate (ProjectiveICP::estimateTransform): levels[0] is full resolution with intrinsics (fx, fy, cx, cy),
+ * levels[l] is half of levels[l - 1]; 1 <= n_levels <= 4; iters[l] iterations at level l, from level n_levels - 1 down to 0, starting
+ * from identity.  Writes the pose (16 floats, row-major 4 x 4: current frame -> previous frame) to d_pose and 0 to *d_status, or, on the
+ * first singular system, 0x10000 | level << 8 | iteration to *d_status and leaves the pose of the iteration before.  d_trace (optional):
+ * (inliers, rms residual) per iteration, in launch order.  Enqueues only: no synchronisation, allocation or copy -- the caller reads the
+ * results (the chain can be captured into a graph). */
+int sobfu_hip_icp_estimate(const sobfu_hip_icp_level* levels, int n_levels, const int iters[4], int depth_mode, float fx, float fy, float cx,
+                           float cy, float dist_thres, float angle_thres, void* d_workspace, size_t workspace_bytes, float* d_pose,
+                           int* d_status, float* d_trace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * native multi-GPU loop: one rank per z-slab, RCCL halo exchange issued from C++ and overlapped with the interior
  * compute (no reference counterpart; schedule documented in sobfu_amd/tiled.py)
  * ---------------------------------------------------------------------------------------------------- */

@@ -100,6 +100,19 @@ def build_variant_tool(force: bool = False) -> str:
     return VARIANT_TOOL
 
 
+ICP_TOOL = os.path.join(ROOT, "build", "icp_shell_tool")
+
+
+def build_icp_tool(force: bool = False) -> str:
+    """tests/cpp/icp_shell_tool.cpp: camera tracking through ProjectiveICP, Frame and the imgproc shells."""
+    src = os.path.join(ROOT, "tests", "cpp", "icp_shell_tool.cpp")
+    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(HERE, "libsobfu_hip.so")]
+    if force or not os.path.exists(ICP_TOOL) or any(os.path.getmtime(ICP_TOOL) < os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(ICP_TOOL), exist_ok=True)
+        _compile(src, ICP_TOOL)
+    return ICP_TOOL
+
+
 def build_host(force: bool = False) -> str:
     build_app(force)
     build_io_tool(force)
@@ -107,6 +120,7 @@ def build_host(force: bool = False) -> str:
     build_colour_tool(force)
     build_ply_tool(force)
     build_variant_tool(force)
+    build_icp_tool(force)
     src = os.path.join(ROOT, "tests", "cpp", "host_shell_tests.cpp")
     deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
             os.path.join(HERE, "libsobfu_hip.so")]

@@ -5,10 +5,36 @@ that is fused in the same frame and psi (sobfu_amd/csrc/colour_kernels.hip).  Th
 (what apps/sobfu_headless drives); bench.py times it for the frames/s figures (BASELINE config 5)."""
 from __future__ import annotations
 
+import numpy as np
+
+
+def affine_mul(a, b):
+    """a o b of two rigid 4 x 4 transforms in float32, in the operation order of cv::Affine3f's stand-in (include/sobfu_amd/sobfu.hpp)"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    r = np.eye(4, dtype=np.float32)
+    for i in range(3):
+        for j in range(3):
+            acc = np.float32(0)
+            for k in range(3):
+                acc = np.float32(acc + a[i, k] * b[k, j])
+            r[i, j] = acc
+        r[i, 3] = np.float32(np.float32(np.float32(a[i, 0] * b[0, 3]) + np.float32(a[i, 1] * b[1, 3])) + np.float32(a[i, 2] * b[2, 3])) + a[i, 3]
+    return r
+
+
+def affine_inv(a):
+    """R^T, -R^T t in float32 (cv::Affine3f::inv of the stand-in)"""
+    a = np.asarray(a, np.float32)
+    r = np.eye(4, dtype=np.float32)
+    r[:3, :3] = a[:3, :3].T
+    for i in range(3):
+        r[i, 3] = -(np.float32(np.float32(r[i, 0] * a[0, 3]) + np.float32(r[i, 1] * a[1, 3])) + np.float32(r[i, 2] * a[2, 3]))
+    return r
+
 
 class SobFusion:
     """params: a dict as sobfu_amd.params.read_ini returns (dims, vs, trunc, eta, max_weight, intr, R, t, start_frame, bilateral,
-    trunc_depth, max_iter, max_update_norm, s, lam, alpha, w_reg)."""
+    trunc_depth, max_iter, max_update_norm, s, lam, alpha, w_reg; track_camera and the icp_* settings for camera tracking)."""
 
     def __init__(self, params, max_iter=None):
         from . import ops
@@ -20,6 +46,41 @@ class SobFusion:
         self.last_report = None
         self.colour_global = None  # (Z, Y, X, 4) uint8 (b, g, r, weight), allocated on the first colour frame
         self.image_shape = None  # (rows, cols) of the depth frames: the camera render() draws with
+        self.track = bool(params.get("track_camera", False))
+        self.pose = np.eye(4, dtype=np.float32)  # the current frame's camera pose (camera -> frame 0's camera); identity unless tracking
+        self.poses = []  # one 4 x 4 float32 pose per frame
+        self.icp = None
+        self._prev = None  # the previous frame's (points, normals) pyramid
+
+    def vol2cam(self):
+        """(R, t) of the volume in the current camera frame: pose^-1 * volume_pose (the volume pose itself without tracking)"""
+        P = self.P
+        if not self.track:
+            return P["R"], P["t"]
+        vp = np.eye(4, dtype=np.float32)
+        vp[:3, :3], vp[:3, 3] = P["R"], P["t"]
+        m = affine_mul(affine_inv(self.pose), vp)
+        return m[:3, :3], m[:3, 3]
+
+    def _track(self, d):
+        """camera tracking of frame n against frame n-1 (the rules of SobFusion::track in include/sobfu_amd/sobfu.hpp)"""
+        ops, P = self.ops, self.P
+        if self.icp is None:
+            self.icp = ops.ICP(P["icp_dist_thres"], P["icp_angle_thres"], P["icp_iter_num"])
+        levels = max(1, self.icp.used_levels())
+        depth = [d]
+        for _ in range(1, levels):
+            depth.append(ops.depth_pyramid(depth[-1], P["bilateral"][2]))
+        curr = [ops.point_normals(x, tuple(float(np.float32(np.float32(v) / np.float32(1 << l))) for v in P["intr"])) for l, x in enumerate(depth)]
+        prev, self._prev = self._prev, curr
+        if prev is None:
+            return
+        ok, aff = self.icp.estimate(P["intr"], [c[0] for c in curr], [c[1] for c in curr], [p[0] for p in prev], [p[1] for p in prev])
+        if ok:
+            self.pose = affine_mul(self.pose, aff)
+        else:
+            level, it = self.icp.failure()
+            print(f"camera tracking failed on frame {self.frame} (level {level}, iteration {it}): keeping the previous pose")
 
     def __call__(self, depth_u16, colour=None):
         """colour (optional): a (rows, cols, 4) uint8 BGRA frame registered to depth_u16, of its size; None = the geometry-only path"""
@@ -32,9 +93,13 @@ class SobFusion:
         d = ops.bilateral_filter(depth_u16, ks, ss, sd)                                       # sob_fusion.cpp:78
         ops.truncate_depth(d, P["trunc_depth"])                                               # :85
         dists = ops.compute_dists(d, P["intr"])                                               # :91
+        if self.track:
+            self._track(d)
+        self.poses.append(self.pose.copy())
+        R, t = self.vol2cam()
         if self.frame == 0:                                                                   # :93-123
             self.phi_global = ops.new_volume(dims)
-            ops.integrate_depth(dists, self.phi_global, vs, P["trunc"], P["eta"], P["R"], P["t"], P["intr"])
+            ops.integrate_depth(dists, self.phi_global, vs, P["trunc"], P["eta"], R, t, P["intr"])
             self._colour(colour, self.phi_global, None)
             self.phi_global_psi_inv, self.phi_n, self.phi_n_psi = ops.new_volume(dims), ops.new_volume(dims), ops.new_volume(dims)
             self.psi, self.psi_inv = ops.new_field(dims), ops.new_field(dims)
@@ -45,7 +110,7 @@ class SobFusion:
             self.frame += 1
             return None
         ops.clear_volume(self.phi_n)                                                          # :129
-        ops.integrate_depth(dists, self.phi_n, vs, P["trunc"], P["eta"], P["R"], P["t"], P["intr"])  # :130
+        ops.integrate_depth(dists, self.phi_n, vs, P["trunc"], P["eta"], R, t, P["intr"])    # :130
         if self.frame < P["start_frame"]:                                                     # :136-139
             self._colour(colour, self.phi_n, None)
             ops.integrate_fuse(self.phi_global, self.phi_n, P["max_weight"])
@@ -63,7 +128,8 @@ class SobFusion:
         P = self.P
         if self.colour_global is None:
             self.colour_global = self.ops.new_colour_volume(P["dims"])
-        self.ops.integrate_colour(colour, tsdf, psi, self.colour_global, P["vs"], P["R"], P["t"], P["intr"],
+        R, t = self.vol2cam()
+        self.ops.integrate_colour(colour, tsdf, psi, self.colour_global, P["vs"], R, t, P["intr"],
                                   self.ops.colour_weight_cap(P["max_weight"]))
 
     def colour_global_psi_inv(self):
@@ -76,7 +142,7 @@ class SobFusion:
 
     def render(self, which="phi_global", light=(0.0, 0.0, 0.0), colour=True):
         """Raycast + shade one of the volumes ("phi_global", "phi_global_psi_inv", "phi_n", "phi_n_psi") from the sequence's own depth
-        camera (the pose and intrinsics its frames are integrated with) -> (rows, cols, 4) uint8 BGRA image; light in the camera frame.
+        camera (the current tracked pose -- identity without tracking -- and the intrinsics its frames are integrated with) -> (rows, cols, 4) uint8 BGRA image; light in the camera frame.
         With colour frames fused and colour=True, the canonical volumes phi_global and phi_global_psi_inv are shaded in colour
         (colour_global, colour_global o psi_inv); the live volumes are always grey."""
         if which not in ("phi_global", "phi_global_psi_inv", "phi_n", "phi_n_psi"):
@@ -85,10 +151,11 @@ class SobFusion:
         if vol is None:
             raise RuntimeError(f"{which} does not exist before the first frame")
         P, (rows, cols) = self.P, self.image_shape
-        pts, nrm = self.ops.raycast(vol, P["vs"], P["trunc"], P["R"], P["t"], P["intr"], rows=rows, cols=cols)
+        R, t = self.vol2cam()
+        pts, nrm = self.ops.raycast(vol, P["vs"], P["trunc"], R, t, P["intr"], rows=rows, cols=cols)
         if colour and self.colour_global is not None and which in ("phi_global", "phi_global_psi_inv"):
             col = self.colour_global if which == "phi_global" else self.colour_global_psi_inv()
-            return self.ops.render_colour(pts, nrm, self.ops.sample_colour(col, P["vs"], P["R"], P["t"], pts, nrm), light)
+            return self.ops.render_colour(pts, nrm, self.ops.sample_colour(col, P["vs"], R, t, pts, nrm), light)
         return self.ops.render_image(pts, nrm, light)
 
     def close(self):

@@ -580,3 +580,150 @@ def render_colour(points, normals, colours, light=(0.0, 0.0, 0.0), image=None):
                                              *_image_ptr(colours, torch.uint8, 4), C.c_int(rows), C.c_int(cols), _f(light[0]), _f(light[1]),
                                              _f(light[2]), *_image_ptr(image, torch.uint8, 4), _stream()), "render_colour")
     return image
+
+
+# ---- camera tracking (sobfu_amd/csrc/icp_kernels.hip): projective ICP and its image pyramids -------------------------------------
+class IcpLevel(C.Structure):
+    """sobfu_hip_icp_level"""
+    _fields_ = [("curr", C.c_void_p), ("curr_step", C.c_int), ("ncurr", C.c_void_p), ("ncurr_step", C.c_int), ("prev", C.c_void_p),
+                ("prev_step", C.c_int), ("nprev", C.c_void_p), ("nprev_step", C.c_int), ("rows", C.c_int), ("cols", C.c_int)]
+
+
+def _depth_image(t):
+    if not (t.is_cuda and t.dim() == 2 and t.dtype in (torch.int16, torch.uint16) and t.stride(1) == 1):
+        raise ValueError("depth images must be (rows, cols) 16-bit tensors on the GPU with contiguous rows")
+    return C.c_void_p(t.data_ptr()), C.c_int(t.stride(0) * 2)
+
+
+def depth_pyramid(depth, sigma_depth, out=None):
+    """depthBuildPyramid: (rows, cols) -> (rows // 2, cols // 2) uint16 (as int16) depth; sigma_depth in metres"""
+    rows, cols = depth.shape
+    if out is None:
+        out = torch.empty((rows // 2, cols // 2), dtype=depth.dtype, device=depth.device)
+    check(_lib.lib().sobfu_hip_depth_pyramid(*_depth_image(depth), C.c_int(rows), C.c_int(cols), *_depth_image(out), _f(sigma_depth), _stream()),
+          "depth_pyramid")
+    return out
+
+
+def point_normals(depth, intr, points=None, normals=None):
+    """computePointNormals -> (points, normals), (rows, cols, 4) float32 in the camera frame; invalid pixels are NaN"""
+    rows, cols = depth.shape
+    points = torch.empty((rows, cols, 4), dtype=torch.float32, device=depth.device) if points is None else points
+    normals = torch.empty((rows, cols, 4), dtype=torch.float32, device=depth.device) if normals is None else normals
+    check(_lib.lib().sobfu_hip_compute_point_normals(*_depth_image(depth), C.c_int(rows), C.c_int(cols), _f(intr[0]), _f(intr[1]), _f(intr[2]),
+                                                     _f(intr[3]), *_image_ptr(points, torch.float32, 4), *_image_ptr(normals, torch.float32, 4),
+                                                     _stream()), "point_normals")
+    return points, normals
+
+
+def normals_mask_depth(depth, intr, normals=None):
+    """computeNormalsAndMaskDepth: normals of `depth`; `depth` is zeroed in place where the normal is NaN"""
+    rows, cols = depth.shape
+    normals = torch.empty((rows, cols, 4), dtype=torch.float32, device=depth.device) if normals is None else normals
+    check(_lib.lib().sobfu_hip_compute_normals_mask_depth(*_depth_image(depth), C.c_int(rows), C.c_int(cols), _f(intr[0]), _f(intr[1]), _f(intr[2]),
+                                                          _f(intr[3]), *_image_ptr(normals, torch.float32, 4), _stream()), "normals_mask_depth")
+    return normals
+
+
+def resize_depth_normals(depth, normals):
+    """resizeDepthNormals: half resolution of (depth, normals)"""
+    rows, cols = depth.shape
+    d = torch.empty((rows // 2, cols // 2), dtype=depth.dtype, device=depth.device)
+    n = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=depth.device)
+    check(_lib.lib().sobfu_hip_resize_depth_normals(*_depth_image(depth), *_image_ptr(normals, torch.float32, 4), C.c_int(rows), C.c_int(cols),
+                                                    *_depth_image(d), *_image_ptr(n, torch.float32, 4), _stream()), "resize_depth_normals")
+    return d, n
+
+
+def resize_points_normals(points, normals):
+    """resizePointsNormals: half resolution of (points, normals); an output pixel is valid iff its four source pixels are"""
+    rows, cols = points.shape[:2]
+    p = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=points.device)
+    n = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=points.device)
+    check(_lib.lib().sobfu_hip_resize_points_normals(*_image_ptr(points, torch.float32, 4), *_image_ptr(normals, torch.float32, 4), C.c_int(rows),
+                                                     C.c_int(cols), *_image_ptr(p, torch.float32, 4), *_image_ptr(n, torch.float32, 4), _stream()),
+          "resize_points_normals")
+    return p, n
+
+
+def _icp_level(curr, ncurr, prev, nprev):
+    depth = curr.dim() == 2
+    if depth:
+        c, p = _depth_image(curr), _depth_image(prev)
+    else:
+        c, p = _image_ptr(curr, torch.float32, 4), _image_ptr(prev, torch.float32, 4)
+    if tuple(curr.shape[:2]) != tuple(prev.shape[:2]) or tuple(ncurr.shape[:2]) != tuple(curr.shape[:2]) or tuple(nprev.shape[:2]) != tuple(curr.shape[:2]):
+        raise ValueError("the current and previous images of a level must have the same size")
+    return IcpLevel(c[0], c[1], *_image_ptr(ncurr, torch.float32, 4), p[0], p[1], *_image_ptr(nprev, torch.float32, 4), curr.shape[0], curr.shape[1]), depth
+
+
+class ICP:
+    """kfusion::cuda::ProjectiveICP on the device: owns the workspace, the pose and the status word.  Angles in radians.
+    estimate() enqueues the whole coarse-to-fine loop and synchronises once (to read the result); enqueue() does not synchronise."""
+
+    def __init__(self, dist_thres=0.1, angle_thres=np.deg2rad(20.0), iters=(10, 5, 4, 0), device="cuda"):
+        _require_gpu()
+        self.dist_thres, self.angle_thres = float(dist_thres), float(angle_thres)
+        self.iters = (list(iters) + [0, 0, 0, 0])[:4]
+        self.workspace = torch.empty(int(_lib.lib().sobfu_hip_icp_workspace_bytes()), dtype=torch.uint8, device=device)
+        self.pose = torch.empty(16, dtype=torch.float32, device=device)
+        self.status = torch.empty(1, dtype=torch.int32, device=device)
+        self.trace = torch.zeros(2 * sum(self.iters), dtype=torch.float32, device=device)
+
+    def used_levels(self):
+        """getUsedLevelsNum: the finest-to-coarsest count up to the last level with iterations"""
+        n = 4
+        while n > 0 and self.iters[n - 1] == 0:
+            n -= 1
+        return n
+
+    def enqueue(self, intr, curr, ncurr, prev, nprev):
+        """curr / prev: lists (finest first) of (rows, cols, 4) points or (rows, cols) depth; ncurr / nprev: the normals"""
+        n = self.used_levels()
+        if n < 1 or min(len(curr), len(ncurr), len(prev), len(nprev)) < n:
+            raise ValueError(f"{n} pyramid levels needed")
+        lv = [_icp_level(curr[i], ncurr[i], prev[i], nprev[i]) for i in range(n)]
+        if len({d for _, d in lv}) != 1:
+            raise ValueError("all levels must be points or all depth")
+        arr = (IcpLevel * n)(*[l for l, _ in lv])
+        check(_lib.lib().sobfu_hip_icp_estimate(arr, C.c_int(n), (C.c_int * 4)(*self.iters), C.c_int(1 if lv[0][1] else 0), _f(intr[0]), _f(intr[1]),
+                                                _f(intr[2]), _f(intr[3]), _f(self.dist_thres), _f(self.angle_thres), _ptr(self.workspace, torch.uint8),
+                                                C.c_size_t(self.workspace.numel()), _ptr(self.pose), _ptr(self.status, torch.int32), _ptr(self.trace),
+                                                _stream()), "icp_estimate")
+
+    def estimate(self, intr, curr, ncurr, prev, nprev):
+        """-> (ok, 4 x 4 float32 numpy pose mapping the current frame into the previous one)"""
+        self.enqueue(intr, curr, ncurr, prev, nprev)
+        return int(self.status.item()) == 0, self.pose.cpu().numpy().reshape(4, 4)
+
+    def failure(self):
+        """(level, iteration) of the failed solve, or None"""
+        s = int(self.status.item())
+        return None if s == 0 else ((s >> 8) & 0xFF, s & 0xFF)
+
+
+def icp_estimate(intr, curr, ncurr, prev, nprev, dist_thres=0.1, angle_thres=np.deg2rad(20.0), iters=(10, 5, 4, 0)):
+    """ProjectiveICP::estimateTransform on pyramids (lists, finest first) -> (ok, 4 x 4 pose: current frame -> previous frame)"""
+    return ICP(dist_thres, angle_thres, iters).estimate(intr, curr, ncurr, prev, nprev)
+
+
+def icp_step(level_index, intr, curr, ncurr, prev, nprev, aff, dist_thres=0.1, angle_thres=np.deg2rad(20.0), codes=False, workspace=None):
+    """One correspondence + reduction pass of pyramid level `level_index` (base intrinsics intr) at the 4 x 4 pose `aff` ->
+    (A 6 x 6, b (6,), inlier count, rms residual, code map (rows, cols) uint8 or None), float64 numpy"""
+    lvl, depth = _icp_level(curr, ncurr, prev, nprev)
+    dev = curr.device
+    aff_d = torch.as_tensor(np.asarray(aff, np.float32).reshape(16), device=dev)
+    ws = torch.empty(int(_lib.lib().sobfu_hip_icp_workspace_bytes()), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    sums = torch.empty(29, dtype=torch.float64, device=dev)
+    cm = torch.empty(tuple(curr.shape[:2]), dtype=torch.uint8, device=dev) if codes else None
+    check(_lib.lib().sobfu_hip_icp_step(C.byref(lvl), C.c_int(int(level_index)), C.c_int(1 if depth else 0), _f(intr[0]), _f(intr[1]), _f(intr[2]),
+                                        _f(intr[3]), _f(dist_thres), _f(angle_thres), _ptr(aff_d), _ptr(ws, torch.uint8), C.c_size_t(ws.numel()),
+                                        _ptr(sums, torch.float64), None if cm is None else _ptr(cm, torch.uint8),
+                                        C.c_int(0 if cm is None else cm.stride(0)), _stream()), "icp_step")
+    s = sums.cpu().numpy()
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = s[:21]
+    A = A + np.triu(A, 1).T
+    count = s[27]
+    rms = float(np.sqrt(s[28] / count)) if count > 0 else 0.0
+    return A, s[21:27].copy(), int(count), rms, None if cm is None else cm.cpu().numpy()

@@ -11,7 +11,8 @@ _REQUIRED = ("TSDF_TRUNC_DIST", "ETA", "VOL_POSE_T_Z")  # vm[...].as<float>() in
 def read_ini(path, dims=None):
     """-> dict with the raw keys plus the derived entries the frame driver uses (float32 arithmetic as in the reference):
     dims, size, vs (voxel sizes), trunc / eta in metres, intr, R / t (volume pose), bilateral, trunc_depth, max_weight,
-    start_frame, max_iter, max_update_norm, s, lam, alpha, w_reg.  `dims` overrides VOL_DIMS_* (a cubic grid edge or a triple);
+    start_frame, max_iter, max_update_norm, s, lam, alpha, w_reg and the camera-tracking settings track_camera, icp_dist_thres (m),
+    icp_angle_thres (radians), icp_iter_num (4 levels, finest first).  `dims` overrides VOL_DIMS_* (a cubic grid edge or a triple);
     the voxel-unit parameters follow the new voxel size, as in apps/sobfu_headless --dims.  Unknown keys are ignored."""
     kv = {}
     with open(path) as f:
@@ -48,6 +49,13 @@ def read_ini(path, dims=None):
         trunc_depth=float(raw.get("TRUNC_DEPTH", 0.0)), start_frame=int(raw.get("START_FRAME", 1)),
         max_iter=int(raw.get("MAX_ITER", 0)), max_update_norm=float(raw.get("MAX_UPDATE_NORM", 0.0)),
         s=int(raw.get("S", 7)), lam=float(raw.get("LAMBDA", 0.1)), alpha=float(raw.get("ALPHA", 0.0)), w_reg=float(raw.get("W_REG", 0.0)))
+    # camera tracking (optional keys, the C++ reader's defaults): TRACK_CAMERA, ICP_DIST_THRES (m), ICP_ANGLE_THRES (deg), ICP_ITERS (10,5,4)
+    iters = [int(x) for x in kv["ICP_ITERS"].split(",") if x.strip()] if "ICP_ITERS" in kv else [10, 5, 4, 0]
+    P.update(
+        track_camera=int(kv.get("TRACK_CAMERA", "0").strip() or 0) != 0,
+        icp_dist_thres=float(np.float32(kv.get("ICP_DIST_THRES", "0.1"))),
+        icp_angle_thres=float(np.float32(np.float32(kv.get("ICP_ANGLE_THRES", "30")) * np.float32(0.017453293))),
+        icp_iter_num=(iters + [0, 0, 0, 0])[:4])
     return P
 
 
