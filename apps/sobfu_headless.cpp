@@ -20,9 +20,15 @@
 // model raycast at the previous pose before the non-rigid solve, and integrates the frame at that pose; the screenshots are then drawn
 // from the current tracked pose.  --poses FILE writes one TUM-format line per frame, "frame tx ty tz qx qy qz qw" (identity without
 // tracking).
+// The canonical mesh carried to live (opt-in; sobfu_amd/csrc/warp_points_kernels.hip): --warp-mesh (with --mesh DIR) writes, on every solved
+// frame n, DIR/phi_global_warped_<n>.ply -- the indexed mesh of phi_global with its vertices and normals pushed through psi and the canonical
+// colours of its vertices.  --track-mesh K (with --mesh DIR) extracts that indexed mesh once, after frame K, and on every solved frame n >= K
+// writes DIR/tracked_<n>.ply: the kept mesh carried to frame n by that frame's psi, so vertex i and the faces are the same in every file.
+// --fit-stats prints one line per solved frame: phi_n sampled at the canonical mesh's vertices warped to live (and unwarped), in millimetres.
 //
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
+//                  [--warp-mesh] [--track-mesh K] [--fit-stats]
 //                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | frame0.pgm frame1.pgm ...)
 #include <dirent.h>
 #include <sys/stat.h>
@@ -155,7 +161,7 @@ struct Screenshots {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -167,7 +173,8 @@ int main(int argc, char** argv) {
     }
     int synthetic = 0;
     double shift = 0.005;
-    bool textured = false;
+    bool textured = false, warp_mesh = false, fit_stats = false;
+    int track_mesh = -1;  // the frame after which the tracked mesh is cut; -1: off
     std::string dump, mesh_dir, data_dir, mesh_format = "vtk", poses_path;
     Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
@@ -190,10 +197,17 @@ int main(int argc, char** argv) {
         else if (a == "--screenshots-detailed") shots.detailed = true;
         else if (a == "--track") p.track_camera = true;
         else if (a == "--poses" && i + 1 < argc) poses_path = argv[++i];
+        else if (a == "--warp-mesh") warp_mesh = true;
+        else if (a == "--track-mesh" && i + 1 < argc) track_mesh = std::atoi(argv[++i]);
+        else if (a == "--fit-stats") fit_stats = true;
         else files.push_back(a);
     }
     if (mesh_format != "vtk" && mesh_format != "ply") {
         std::printf("--mesh-format is vtk or ply, not %s\n", mesh_format.c_str());
+        return 2;
+    }
+    if ((warp_mesh || track_mesh >= 0) && mesh_dir.empty()) {
+        std::printf("--warp-mesh and --track-mesh need --mesh DIR\n");
         return 2;
     }
     if (argc > 2) {  // --dims changes the voxel size: re-derive the voxel-unit parameters
@@ -237,6 +251,7 @@ int main(int argc, char** argv) {
     kfusion::cuda::Depth depth;
     kfusion::cuda::Image colour;
     double time_ms = 0.0;
+    sobfu_amd::IndexedMesh tracked;  // --track-mesh: the canonical mesh cut after frame track_mesh
     for (int n = 0; n < nframes; ++n) {
         if (synthetic > 0) {
             render_sphere(shift * n, 0.0, 0.75, 0.1, p.intr, p.rows, p.cols, img);
@@ -298,6 +313,22 @@ int main(int argc, char** argv) {
                 save_mesh("phi_global_psi_inv", fusion.get_phi_global_psi_inv_mesh());
             }
         }
+        const bool solved_frame = n > 0 && n >= p.start_frame;
+        if (solved_frame && (warp_mesh || fit_stats)) {
+            if (!fit_stats) {
+                save_ply("phi_global_warped", fusion.get_phi_global_warped_indexed_mesh());
+            } else {
+                sobfu_amd::IndexedMesh m = fusion.get_phi_global_indexed_mesh();
+                const sobfu_amd::MeshFit before = fusion.fit_to_live(m);
+                m = fusion.warp_to_live(std::move(m));
+                const sobfu_amd::MeshFit f = fusion.fit_to_live(m);
+                if (warp_mesh) save_ply("phi_global_warped", m);
+                std::printf("fit %d: %zu vertices, %zu valid, mean |d| %.4f mm, rms %.4f mm, max %.4f mm (unwarped rms %.4f mm)\n", n, f.vertices, f.valid,
+                            1e3 * f.mean_abs, 1e3 * f.rms, 1e3 * f.max, 1e3 * before.rms);
+            }
+        }
+        if (track_mesh >= 0 && n == track_mesh) tracked = fusion.get_phi_global_indexed_mesh();
+        if (track_mesh >= 0 && n >= track_mesh && solved_frame) save_ply("tracked", fusion.warp_to_live(tracked));
         if (!shots.dir.empty()) {
             const bool solved = n > 0 && n >= p.start_frame;
             if (shots.write(n, fusion, solved, p.intr)) std::printf("screenshot %s/%06d.png\n", shots.dir.c_str(), n);

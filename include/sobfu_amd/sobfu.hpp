@@ -843,6 +843,9 @@ public:
         return m;
     }
     const DeviceArray<Point>& last_indexed_vertices() const { return indexed_vertices_; }
+    // the same vertices and their normals, writable: sobfu_amd::warp_mesh warps the last run_indexed's mesh in place on the device
+    DeviceArray<Point>& last_indexed_vertices() { return indexed_vertices_; }
+    DeviceArray<Normal>& last_indexed_normals() { return indexed_normals_; }
 
 private:
     DeviceArray2D<int> occupied_voxels_buffer_;
@@ -1239,6 +1242,68 @@ inline bool read_params_ini(const std::string& path, Params& p, std::map<std::st
 }
 }  // namespace sobfu_amd
 
+namespace sobfu_amd {
+// ---- the canonical mesh carried to the live frame (no reference counterpart; rules: sobfu_amd/csrc/warp_points_kernels.hip) ----------
+// Fit of mesh vertices to a TSDF volume: |tsdf| x truncation distance in metres (the TSDF's own projective metric) over the vertices
+// whose sample is valid (all eight corners observed)
+struct MeshFit {
+    size_t vertices = 0, valid = 0;
+    double mean_abs = 0, rms = 0, max = 0;
+};
+// Warps the vertices and normals of `m` (marching-cubes vertices under p.volume_pose) through psi, v -> psi(v); faces and colours stay.
+// d_vertices / d_normals (optional): the mesh's vertices and normals already on the device (MarchingCubes::last_indexed_*), warped in
+// place instead of an upload
+inline void warp_mesh(IndexedMesh& m, const sobfu::cuda::DeformationField& psi, const Params& p,
+                      kfusion::cuda::DeviceArray<kfusion::cuda::Point>* d_vertices = nullptr, kfusion::cuda::DeviceArray<kfusion::cuda::Normal>* d_normals = nullptr) {
+    const size_t n = m.vertices.size();
+    if (n == 0) return;
+    kfusion::cuda::DeviceArray<kfusion::cuda::Point> dv;
+    kfusion::cuda::DeviceArray<kfusion::cuda::Normal> dn;
+    const bool normals = m.normals.size() == n;
+    if (d_vertices && d_vertices->size() == n && (!normals || (d_normals && d_normals->size() == n))) {
+        dv = *d_vertices;
+        if (normals) dn = *d_normals;
+    } else {
+        dv.upload(m.vertices);
+        if (normals) dn.upload(m.normals);
+    }
+    const cv::Vec3i d = psi.get_dims();
+    const cv::Vec3f vs = p.voxel_sizes();
+    const float v[3] = {vs[0], vs[1], vs[2]};
+    sobfuSafeCall(sobfu_hip_warp_points(psi.get_data().ptr<float>(), d[0], d[1], d[2], v, p.volume_pose.R, p.volume_pose.t, 1, (const float*) dv.ptr(),
+                                        normals ? (const float*) dn.ptr() : nullptr, (int) n, (float*) dv.ptr(), normals ? (float*) dn.ptr() : nullptr,
+                                        nullptr));
+    dv.download(m.vertices);
+    if (normals) dn.download(m.normals);
+}
+// `vol` sampled at the mesh's vertices (marching-cubes vertices under p.volume_pose)
+inline MeshFit mesh_fit(const IndexedMesh& m, const kfusion::cuda::TsdfVolume& vol, const Params& p, std::vector<float>* samples = nullptr) {
+    MeshFit f;
+    const size_t n = f.vertices = m.vertices.size();
+    std::vector<float> h;
+    if (n > 0) {
+        kfusion::cuda::DeviceArray<kfusion::cuda::Point> dv;
+        kfusion::cuda::DeviceArray<float> out(n);
+        dv.upload(m.vertices);
+        const cv::Vec3i d = vol.getDims();
+        const cv::Vec3f vs = vol.getVoxelSize();
+        const float v[3] = {vs[0], vs[1], vs[2]};
+        sobfuSafeCall(sobfu_hip_sample_tsdf(vol.data().ptr<float>(), d[0], d[1], d[2], v, p.volume_pose.R, p.volume_pose.t, 1, (const float*) dv.ptr(), (int) n,
+                                            out.ptr(), nullptr));
+        out.download(h);
+    }
+    double s1 = 0, s2 = 0;
+    for (float x : h) {
+        if (x != x) continue;
+        const double a = std::fabs((double) x) * (double) vol.getTruncDist();
+        ++f.valid, s1 += a, s2 += a * a, f.max = std::max(f.max, a);
+    }
+    if (f.valid) f.mean_abs = s1 / (double) f.valid, f.rms = std::sqrt(s2 / (double) f.valid);
+    if (samples) samples->swap(h);
+    return f;
+}
+}  // namespace sobfu_amd
+
 // SobFusion (include/sobfu/sob_fusion.hpp, src/sobfu/sob_fusion.cpp:71-145) -- per-frame driver: bilateral filter ->
 // depth truncation -> dists; frame 0 builds phi_global and allocates everything; frame n builds phi_n, fuses it
 // directly while n < START_FRAME, otherwise estimates psi (warm-started) and fuses phi_n o psi.
@@ -1327,6 +1392,25 @@ public:
         sobfu_amd::IndexedMesh m = mc->run_indexed(*vol);
         if (colour && !m.empty()) colour->sample_vertices(mc->last_indexed_vertices(), params.volume_pose, vol->getVoxelSize(), m.colours);
         return m;
+    }
+    // The canonical model carried to the live frame: the indexed mesh of phi_global with its vertices and normals pushed through psi.  The
+    // colour travels with the vertex: it is sampled from colour_global at the CANONICAL vertices (no colour_global o psi_inv volume is built).
+    // Vertex i and the faces are those of get_phi_global_indexed_mesh(); before the first solved frame psi is the identity.
+    sobfu_amd::IndexedMesh get_phi_global_warped_indexed_mesh() {
+        sobfu_amd::IndexedMesh m = get_indexed_mesh(phi_global, colour_global.get());
+        if (!m.empty() && psi) sobfu_amd::warp_mesh(m, *psi, params, &mc->last_indexed_vertices(), &mc->last_indexed_normals());
+        return m;
+    }
+    // a mesh of the canonical model the caller kept from an earlier frame, carried to the current live frame (psi maps canonical space to
+    // the current frame whatever frame the mesh was cut in)
+    sobfu_amd::IndexedMesh warp_to_live(sobfu_amd::IndexedMesh m) {
+        if (psi) sobfu_amd::warp_mesh(m, *psi, params);
+        return m;
+    }
+    // phi_n (the current frame) sampled at the mesh's vertices
+    sobfu_amd::MeshFit fit_to_live(const sobfu_amd::IndexedMesh& m, std::vector<float>* samples = nullptr) {
+        if (!phi_n) kfusion::cuda::error("fit_to_live needs a second frame", __FILE__, __LINE__);
+        return sobfu_amd::mesh_fit(m, *phi_n, params, samples);
     }
     static sobfu_amd::TriangleMesh convert_to_mesh(const kfusion::cuda::DeviceArray<kfusion::cuda::Point>& triangles) {
         sobfu_amd::TriangleMesh m;

@@ -369,6 +369,23 @@ int sobfu_hip_render_colour(const float* d_points, int points_step, const float*
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * points through the deformation -- the canonical mesh carried to the live frame (no reference counterpart: the reference's live meshes
+ * are fresh marching-cubes runs on warped volumes).  Point and normal lists: n dense float4, 16-byte aligned.  (R row-major, t), voxel_size
+ * and mc_vertices as in sobfu_hip_sample_colour.  The rules are in sobfu_amd/csrc/warp_points_kernels.hip.  Every argument is checked
+ * before any device call; n = 0 succeeds and launches nothing.
+ * ---------------------------------------------------------------------------------------------------- */
+/* warp_points: point v -> v + the displacement of d_psi (float4 per voxel, absolute positions in voxel units) interpolated at v, w = 1;
+ * normals (optional: d_normals and d_normals_out are both given or both NULL) through the cofactor matrix of psi's Jacobian in the same
+ * cell, normalised, w = 1; a zero normal stays (0, 0, 0, 1).  Outputs may be the inputs. */
+int sobfu_hip_warp_points(const float* d_psi, int X, int Y, int Z, const float voxel_size[3], const float R[9], const float t[3],
+                          int mc_vertices, const float* d_points, const float* d_normals, int n, float* d_points_out, float* d_normals_out,
+                          void* stream);
+/* sample_tsdf: the trilinear TSDF of d_vol ({tsdf, weight} per voxel) at the points, one float per point in units of the truncation
+ * distance; NaN where one of the eight corners has weight <= 0 (the raycaster's validity rule). */
+int sobfu_hip_sample_tsdf(const float* d_vol, int X, int Y, int Z, const float voxel_size[3], const float R[9], const float t[3],
+                          int mc_vertices, const float* d_points, int n, float* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * camera tracking -- kfusion::cuda::ProjectiveICP (include/kfusion/cuda/projective_icp.hpp, src/kfusion/projective_icp.cpp) and the image
  * helpers of include/kfusion/cuda/imgproc.hpp it needs (depthBuildPyramid, computePointNormals, computeNormalsAndMaskDepth,
  * resizeDepthNormals, resizePointsNormals), which the reference declares but never calls.  Depth: pitched uint16 mm; points / normals:

@@ -113,6 +113,20 @@ def build_icp_tool(force: bool = False) -> str:
     return ICP_TOOL
 
 
+MESH_WARP_TOOL = os.path.join(ROOT, "build", "mesh_warp_tool")
+
+
+def build_mesh_warp_tool(force: bool = False) -> str:
+    """tests/cpp/mesh_warp_tool.cpp: the canonical mesh carried to live through SobFusion's shells (warp_mesh, fit_to_live)."""
+    src = os.path.join(ROOT, "tests", "cpp", "mesh_warp_tool.cpp")
+    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp"),
+            os.path.join(HERE, "libsobfu_hip.so")]
+    if force or not os.path.exists(MESH_WARP_TOOL) or any(os.path.getmtime(MESH_WARP_TOOL) < os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(MESH_WARP_TOOL), exist_ok=True)
+        _compile(src, MESH_WARP_TOOL)
+    return MESH_WARP_TOOL
+
+
 def build_host(force: bool = False) -> str:
     build_app(force)
     build_io_tool(force)
@@ -121,6 +135,7 @@ def build_host(force: bool = False) -> str:
     build_ply_tool(force)
     build_variant_tool(force)
     build_icp_tool(force)
+    build_mesh_warp_tool(force)
     src = os.path.join(ROOT, "tests", "cpp", "host_shell_tests.cpp")
     deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
             os.path.join(HERE, "libsobfu_hip.so")]

@@ -158,6 +158,28 @@ class SobFusion:
             return self.ops.render_colour(pts, nrm, self.ops.sample_colour(col, P["vs"], R, t, pts, nrm), light)
         return self.ops.render_image(pts, nrm, light)
 
+    def warp_to_live(self, vertices, normals=None):
+        """Carries marching-cubes vertices of the canonical model (ops.marching_cubes_indexed of phi_global at the volume pose), and their
+        normals when given, to the live frame through the current psi: vertex i stays the same surface point from frame to frame.
+        -> vertices, or (vertices, normals), new tensors.  Before the first solved frame (psi is still the identity) the input is returned."""
+        if self.last_report is None:
+            return vertices if normals is None else (vertices, normals)
+        P = self.P
+        return self.ops.warp_points(self.psi, P["vs"], P["R"], P["t"], vertices, normals, mc_vertices=True)
+
+    def fit(self, vertices):
+        """How well marching-cubes vertices (at the volume pose) fit the current frame: phi_n sampled at them, in metres (TSDF x truncation
+        distance: the TSDF's own projective metric, not a Euclidean point-to-surface distance), over the samples whose eight corners
+        were all observed -> dict(valid, mean_abs, rms, max)."""
+        if self.phi_n is None:
+            raise RuntimeError("phi_n does not exist before the second frame")
+        P = self.P
+        d = self.ops.sample_tsdf(self.phi_n, P["vs"], P["R"], P["t"], vertices, mc_vertices=True).cpu().numpy().astype(np.float64)
+        d = np.abs(d[~np.isnan(d)]) * float(P["trunc"])
+        if d.size == 0:
+            return dict(valid=0, mean_abs=0.0, rms=0.0, max=0.0)
+        return dict(valid=int(d.size), mean_abs=float(d.mean()), rms=float(np.sqrt((d * d).mean())), max=float(d.max()))
+
     def close(self):
         if self.solver is not None:
             self.solver.close()

@@ -582,6 +582,52 @@ def render_colour(points, normals, colours, light=(0.0, 0.0, 0.0), image=None):
     return image
 
 
+# ---- points through the deformation (sobfu_amd/csrc/warp_points_kernels.hip): (n, 4) float32 point / normal lists --------------------
+def _point_list(t, what):
+    if not (t.dim() == 2 and t.shape[1] == 4):
+        raise ValueError(f"expected an (n, 4) float32 list of {what}, got {tuple(t.shape)}")
+    return _ptr(t)
+
+
+def warp_points(psi, voxel_size, R, t, points, normals=None, mc_vertices=False, out=None):
+    """Carries (n, 4) points of a frame whose pose from volume metres is (R, t) (marching-cubes vertices with mc_vertices=True and the
+    marching-cubes pose) through psi, v -> psi(v), and their normals (optional) through the cofactor matrix of psi's Jacobian -> points,
+    or (points, normals).  `out`: a tensor (or, with normals, a pair) to write into; it may be the input."""
+    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
+    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    po, no = (out if normals is not None else (out, None)) if out is not None else (None, None)
+    po = torch.empty_like(points) if po is None else po
+    if normals is not None:
+        no = torch.empty_like(normals) if no is None else no
+        if tuple(normals.shape) != tuple(points.shape) or tuple(no.shape) != tuple(points.shape):
+            raise ValueError("points and normals must have the same shape")
+    if tuple(po.shape) != tuple(points.shape):
+        raise ValueError("the output must have the points' shape")
+    if points.shape[0] == 0:  # an empty tensor has no address to hand over
+        return po if normals is None else (po, no)
+    check(_lib.lib().sobfu_hip_warp_points(_ptr(psi), *_xyz(psi), _F3(*[float(v) for v in voxel_size]), Rm, tv, C.c_int(1 if mc_vertices else 0),
+                                           _point_list(points, "points"), None if normals is None else _point_list(normals, "normals"),
+                                           C.c_int(points.shape[0]), _point_list(po, "points"), None if normals is None else _point_list(no, "normals"),
+                                           _stream()), "warp_points")
+    return po if normals is None else (po, no)
+
+
+def sample_tsdf(vol, voxel_size, R, t, points, mc_vertices=False, out=None):
+    """The trilinear TSDF of `vol` (Z, Y, X, 2) at (n, 4) points (pose and mc_vertices as in warp_points) -> (n,) float32 in units of the
+    truncation distance; NaN where one of the eight corners has no weight (the raycaster's validity rule)."""
+    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
+    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    if out is None:
+        out = torch.empty(points.shape[0], dtype=torch.float32, device=points.device)
+    if tuple(out.shape) != (points.shape[0],):
+        raise ValueError("the output must hold one float per point")
+    if points.shape[0] == 0:
+        return out
+    check(_lib.lib().sobfu_hip_sample_tsdf(_ptr(vol), *_xyz(vol), _F3(*[float(v) for v in voxel_size]), Rm, tv, C.c_int(1 if mc_vertices else 0),
+                                           _point_list(points, "points"), C.c_int(points.shape[0]), _ptr(out), _stream()), "sample_tsdf")
+    return out
+
+
 # ---- camera tracking (sobfu_amd/csrc/icp_kernels.hip): projective ICP and its image pyramids -------------------------------------
 class IcpLevel(C.Structure):
     """sobfu_hip_icp_level"""
