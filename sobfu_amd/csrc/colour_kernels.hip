@@ -19,18 +19,16 @@
 //              outermost, z innermost, g = lower, h = upper); a = 1.  No weighted corner with colour (sum w_i == 0): (0, 0, 0, 0)
 //   apply      c_live(y) = sample(c_global, psi_inv(y))  (apply_kernel, field_kernels.hip)
 //   sample     point p (float4) of a frame whose pose from the volume is (R, t): q = p, or (p.x, -p.y, -p.z) for marching-cubes
-//              vertices (include/sobfu_hip.h, marching cubes); g_i = dot3(R^T_i, q - t) / vs_i - 0.5f; with a normals image, a
-//              point whose normal.w == 0 (a raycast miss) gives (0, 0, 0, 0)
-//   render     I = 0.2 + 0.8 max(0, n . l) as render_image_kernel (render_kernels.hip); a hit with colour: (c_i * I) rounded
+//              vertices (include/sobfu_hip.h, marching cubes); g_i = dot3(R^T_i, q - t) / vs_i - 0.5f (grid_position,
+//              sobfu_frame.hpp); with a normals image, a point whose normal.w == 0 (a raycast miss) gives (0, 0, 0, 0)
+//   render     I = 0.2 + 0.8 max(0, n . l), render_image_kernel's (lambert, sobfu_frame.hpp); a hit with colour: (c_i * I) rounded
 //              to a byte per channel, alpha 255; a hit without colour: render_image's grey; a miss: (0, 0, 0, 0)
 //
 // Launch shapes: integrate / apply one lane per voxel, waves of 64 consecutive x (the TSDF read is 512 B per wave, coalesced); only
 // the |tsdf| < 1 shell touches psi, the image and the colour volume.  Images and point lists: 64 x 4 lanes per workgroup.  No LDS.
-#include "sobfu_device.hpp"
+#include "sobfu_frame.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
-
-#include <cmath>
 
 using namespace sobfu_hip;
 
@@ -70,7 +68,7 @@ __global__ void __launch_bounds__(256) integrate_colour_kernel(ColourArgs a) {
     if (!(camz > 0)) return;
     if (!(coox == coox) || !(cooy == cooy)) return;
     const int u = (int) floorf(coox), v = (int) floorf(cooy);
-    const uchar4 n = *((const uchar4*) ((const char*) a.image + (size_t) v * a.image_step) + u);
+    const uchar4 n = row_ptr(a.image, a.image_step, v)[u];
     const uchar4 c = a.colour[i];
     const float w = (float) c.w, w1 = w + 1.f;
     auto avg = [&](unsigned char old, unsigned char obs) { return (unsigned char) rintf(((float) old * w + (float) obs) / w1); };
@@ -131,15 +129,13 @@ __global__ void __launch_bounds__(256) sample_colour_kernel(SampleArgs a) {
     const int u = blockIdx.x * 64 + threadIdx.x, v = blockIdx.y * 4 + threadIdx.y;
     if (u >= a.cols || v >= a.rows) return;
     uchar4 px = make_uchar4(0, 0, 0, 0);
-    const bool hit = !a.normals || ((const float4*) ((const char*) a.normals + (size_t) v * a.normals_step) + u)->w != 0.f;
+    const bool hit = !a.normals || row_ptr(a.normals, a.normals_step, v)[u].w != 0.f;
     if (hit) {
-        const float4 p = *((const float4*) ((const char*) a.points + (size_t) v * a.points_step) + u);
-        const float qx = p.x - a.t[0], qy = (a.flip ? -p.y : p.y) - a.t[1], qz = (a.flip ? -p.z : p.z) - a.t[2];
-        const float gx = dot3(a.Rt + 0, qx, qy, qz) / a.vsx - 0.5f, gy = dot3(a.Rt + 3, qx, qy, qz) / a.vsy - 0.5f,
-                    gz = dot3(a.Rt + 6, qx, qy, qz) / a.vsz - 0.5f;
+        float wx, wy, wz, gx, gy, gz;
+        grid_position(a, row_ptr(a.points, a.points_step, v)[u], wx, wy, wz, gx, gy, gz);
         px = sample_colour_at(a.col, a.d, gx, gy, gz);
     }
-    *((uchar4*) ((char*) a.out + (size_t) v * a.out_step) + u) = px;
+    row_ptr(a.out, a.out_step, v)[u] = px;
 }
 
 struct RenderColourArgs {
@@ -155,20 +151,14 @@ struct RenderColourArgs {
     int image_step;
 };
 
-SOBFU_DEV unsigned char to_byte(float x) { return (unsigned char) fminf(255.f, fmaxf(0.f, floorf(x + 0.5f))); }
-
 __global__ void __launch_bounds__(256) render_colour_kernel(RenderColourArgs a) {
     const int u = blockIdx.x * 64 + threadIdx.x, v = blockIdx.y * 4 + threadIdx.y;
     if (u >= a.cols || v >= a.rows) return;
-    const float4 n = *((const float4*) ((const char*) a.normals + (size_t) v * a.normals_step) + u);
+    const float4 n = row_ptr(a.normals, a.normals_step, v)[u];
     uchar4 px = make_uchar4(0, 0, 0, 0);
     if (n.w != 0.f) {
-        const float4 p = *((const float4*) ((const char*) a.points + (size_t) v * a.points_step) + u);
-        const float lx = a.lx - p.x, ly = a.ly - p.y, lz = a.lz - p.z;
-        const float ll = __builtin_sqrtf(lx * lx + ly * ly + lz * lz);
-        const float ndl = n.x * (lx / ll) + n.y * (ly / ll) + n.z * (lz / ll);
-        const float I = 0.2f + 0.8f * fmaxf(0.f, ndl);
-        const uchar4 c = *((const uchar4*) ((const char*) a.colour + (size_t) v * a.colour_step) + u);
+        const float I = lambert(n, row_ptr(a.points, a.points_step, v)[u], a.lx, a.ly, a.lz);
+        const uchar4 c = row_ptr(a.colour, a.colour_step, v)[u];
         if (c.w != 0) {
             px = make_uchar4(to_byte((float) c.x * I), to_byte((float) c.y * I), to_byte((float) c.z * I), 255);
         } else {
@@ -176,13 +166,8 @@ __global__ void __launch_bounds__(256) render_colour_kernel(RenderColourArgs a) 
             px = make_uchar4(g, g, g, 255);
         }
     }
-    *((uchar4*) ((char*) a.image + (size_t) v * a.image_step) + u) = px;
+    row_ptr(a.image, a.image_step, v)[u] = px;
 }
-
-bool aligned(const void* p, long long step, int to) { return ((uintptr_t) p % (uintptr_t) to) == 0 && step % to == 0; }
-bool positive_finite(float x) { return std::isfinite(x) && x > 0.f; }
-dim3 image_grid(int rows, int cols) { return dim3((unsigned) ((cols + 63) / 64), (unsigned) ((rows + 3) / 4)); }
-bool volume_ok(int X, int Y, int Z) { return X > 0 && Y > 0 && Z > 0 && Z <= 65535 && (long long) X * Y * Z <= (1LL << 40); }
 
 }  // namespace
 
@@ -192,21 +177,20 @@ int sobfu_hip_integrate_colour(const uint8_t* d_image, int image_step, int rows,
                                uint8_t* d_colour, int X, int Y, int Z, const float vs[3], const float R[9], const float t[3], float fx, float fy,
                                float cx, float cy, int cap, void* stream) {
     SOBFU_CHECK_ARGS(d_image && d_tsdf && d_colour && vs && R && t);
-    SOBFU_CHECK_ARGS(volume_ok(X, Y, Z) && rows >= 1 && cols >= 1 && (long long) image_step >= (long long) cols * 4);
+    SOBFU_CHECK_ARGS(volume_ok(X, Y, Z, kGridZ) && rows >= 1 && cols >= 1 && (long long) image_step >= (long long) cols * 4);
     SOBFU_CHECK_ARGS(aligned(d_image, image_step, 4) && aligned(d_colour, 0, 4) && aligned(d_tsdf, 0, 8) && (!d_psi || aligned(d_psi, 0, 16)));
     SOBFU_CHECK_ARGS(cap >= 1 && cap <= 255);
     SOBFU_CHECK_ARGS(positive_finite(vs[0]) && positive_finite(vs[1]) && positive_finite(vs[2]));
-    SOBFU_CHECK_ARGS(std::isfinite(fx) && std::isfinite(fy) && fx != 0.f && fy != 0.f && std::isfinite(cx) && std::isfinite(cy));
+    SOBFU_CHECK_ARGS(intr_ok(fx, fy, cx, cy));
     ColourArgs a{(const uchar4*) d_image, image_step, rows, cols, (const float2*) d_tsdf, (const float4*) d_psi, (uchar4*) d_colour, {X, Y, Z},
                  vs[0], vs[1], vs[2], {}, {}, fx, fy, cx, cy, cap};
-    for (int i = 0; i < 9; ++i) a.R[i] = R[i];
-    for (int i = 0; i < 3; ++i) a.t[i] = t[i];
+    fill_pose(R, t, a.R, nullptr, a.t);
     hipLaunchKernelGGL(integrate_colour_kernel, voxel_grid(X, Y, Z), voxel_block(), 0, (hipStream_t) stream, a);
     return (int) hipGetLastError();
 }
 
 int sobfu_hip_apply_colour(const uint8_t* d_colour, uint8_t* d_colour_warped, const float* d_psi_inv, int X, int Y, int Z, void* stream) {
-    SOBFU_CHECK_ARGS(d_colour && d_colour_warped && d_psi_inv && d_colour != d_colour_warped && volume_ok(X, Y, Z));
+    SOBFU_CHECK_ARGS(d_colour && d_colour_warped && d_psi_inv && d_colour != d_colour_warped && volume_ok(X, Y, Z, kGridZ));
     SOBFU_CHECK_ARGS(aligned(d_colour, 0, 4) && aligned(d_colour_warped, 0, 4) && aligned(d_psi_inv, 0, 16));
     hipLaunchKernelGGL(apply_colour_kernel, voxel_grid(X, Y, Z), voxel_block(), 0, (hipStream_t) stream, (const uchar4*) d_colour,
                        (uchar4*) d_colour_warped, (const float4*) d_psi_inv, Dims{X, Y, Z});
@@ -216,7 +200,7 @@ int sobfu_hip_apply_colour(const uint8_t* d_colour, uint8_t* d_colour_warped, co
 int sobfu_hip_sample_colour(const uint8_t* d_colour, int X, int Y, int Z, const float vs[3], const float R[9], const float t[3], int mc_vertices,
                             const float* d_points, int points_step, const float* d_normals, int normals_step, int rows, int cols, uint8_t* d_out,
                             int out_step, void* stream) {
-    SOBFU_CHECK_ARGS(d_colour && vs && R && t && d_points && d_out && volume_ok(X, Y, Z) && rows >= 1 && cols >= 1 && rows <= 65535 * 4);
+    SOBFU_CHECK_ARGS(d_colour && vs && R && t && d_points && d_out && volume_ok(X, Y, Z, kGridZ) && rows >= 1 && cols >= 1 && rows <= 65535 * 4);
     SOBFU_CHECK_ARGS((long long) points_step >= (long long) cols * 16 && (long long) out_step >= (long long) cols * 4);
     SOBFU_CHECK_ARGS(!d_normals || (long long) normals_step >= (long long) cols * 16);
     SOBFU_CHECK_ARGS(aligned(d_colour, 0, 4) && aligned(d_points, points_step, 16) && aligned(d_out, out_step, 4));
@@ -224,10 +208,7 @@ int sobfu_hip_sample_colour(const uint8_t* d_colour, int X, int Y, int Z, const 
     SOBFU_CHECK_ARGS(positive_finite(vs[0]) && positive_finite(vs[1]) && positive_finite(vs[2]));
     SampleArgs a{(const uchar4*) d_colour, {X, Y, Z}, vs[0], vs[1], vs[2], {}, {}, mc_vertices ? 1 : 0, (const float4*) d_points, points_step,
                  (const float4*) d_normals, normals_step, rows, cols, (uchar4*) d_out, out_step};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) a.Rt[3 * i + j] = R[3 * j + i];
-        a.t[i] = t[i];
-    }
+    fill_pose(R, t, nullptr, a.Rt, a.t);
     hipLaunchKernelGGL(sample_colour_kernel, image_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, a);
     return (int) hipGetLastError();
 }

@@ -55,7 +55,7 @@
 // one 32-float slab.  No float atomics anywhere: the sums, and so the pose, are bitwise reproducible.  The solve is one 256-thread
 // workgroup: thread j converts slab j to fp64, the same butterfly and LDS order reduce the slabs, lane 0 solves.  Every index of the
 // 6 x 6 system is a compile-time constant (fully unrolled loops): nothing goes to scratch.
-#include "sobfu_device.hpp"
+#include "sobfu_frame.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
 
@@ -69,11 +69,6 @@ constexpr int kSums = 29;
 constexpr int kSlab = 32;       // floats per partial slab
 constexpr int kMaxParts = 256;  // partial slabs of one correspondence pass (= the solve's workgroup size)
 constexpr int kThreads = 256;
-
-template <class T>
-SOBFU_DEV T* row_ptr(T* base, int step, int y) { return (T*) ((char*) base + (size_t) y * step); }
-template <class T>
-SOBFU_DEV const T* row_ptr(const T* base, int step, int y) { return (const T*) ((const char*) base + (size_t) y * step); }
 
 SOBFU_DEV bool finite3(float x, float y, float z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 SOBFU_DEV bool valid_pn(const float4& p, const float4& n) {
@@ -407,11 +402,6 @@ __global__ void __launch_bounds__(kThreads) icp_solve_kernel(const float* __rest
     }
 }
 
-bool aligned(const void* p, int step, int to) { return ((uintptr_t) p % (uintptr_t) to) == 0 && step % to == 0; }
-dim3 image_grid(int rows, int cols) { return dim3((unsigned) ((cols + 63) / 64), (unsigned) ((rows + 3) / 4)); }
-bool intr_ok(float fx, float fy, float cx, float cy) {
-    return std::isfinite(fx) && std::isfinite(fy) && fx != 0.f && fy != 0.f && std::isfinite(cx) && std::isfinite(cy);
-}
 Reproj level_reproj(float fx, float fy, float cx, float cy, int level) {
     const float div = (float) (1 << level);
     Reproj r{fx / div, fy / div, cx / div, cy / div, 0.f, 0.f};
@@ -440,7 +430,7 @@ void launch_correspond(const IcpLevel& L, int depth_mode, const float* aff, cons
     if (depth_mode) hipLaunchKernelGGL(icp_correspond_kernel<true>, grid, dim3(kThreads), 0, s, L, aff, status, dist2, min_cos, parts, codes, codes_step);
     else hipLaunchKernelGGL(icp_correspond_kernel<false>, grid, dim3(kThreads), 0, s, L, aff, status, dist2, min_cos, parts, codes, codes_step);
 }
-bool thresholds_ok(float dist, float angle) { return std::isfinite(dist) && dist > 0.f && std::isfinite(angle) && angle >= 0.f; }
+bool thresholds_ok(float dist, float angle) { return positive_finite(dist) && std::isfinite(angle) && angle >= 0.f; }
 
 constexpr size_t kWorkspaceBytes = (size_t) kMaxParts * kSlab * sizeof(float);
 

@@ -8,7 +8,8 @@
 //   ray      pixel (u, v) -> d = ((u - cx) / fx, (v - cy) / fy, 1), parameter = camera depth z; in grid units the sample at z is
 //            g = fmaf(z, D, O) with D = (R^T d) / vs and O = (-R^T t) / vs - 0.5 (R^T, -R^T t from the host in double)
 //   clip     slab test against g in [0, dim - 1] per axis, and z >= 0
-//   sampler  trilinear tsdf with the clamp / upper-index rule of tri_setup; valid when all 8 corner weights are > 0
+//   sampler  trilinear tsdf with the clamp / upper-index rule of tri_setup; valid when all 8 corner weights are > 0 (sample_tsdf,
+//            sobfu_frame.hpp)
 //   march    step (in metres of ray length) = (valid && f > 0) ? max(fine, 0.8 f trunc) : fine, fine = step_factor * min(vs);
 //            hit = previous sample valid with f > 0, current sample valid with f < 0; one secant step refines z
 //   output   point (z d, 0), normal (normalize(R grad f), 1); grad f by central differences at +-1 grid unit (clamped into the box)
@@ -16,7 +17,7 @@
 //
 // Launch shape of the raycaster: 256-thread workgroups of 16 x 16 pixels, each 64-lane wave an 8 x 8 tile, so the rays of a wave
 // are neighbours in both image directions and gather the same cache lines of the volume.  No LDS.
-#include "sobfu_device.hpp"
+#include "sobfu_frame.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
 
@@ -43,44 +44,6 @@ struct RaycastArgs {
     int normals_step;
 };
 
-// corner offsets of one trilinear sample (the index rule of tri_setup: clamped, upper index = lower index on the box faces)
-struct Cell {
-    const float2* base;
-    size_t dx, dy, dz;
-    float tx, ty, tz;
-};
-
-SOBFU_DEV Cell cell_at(const float2* __restrict__ v, const Dims& d, float gx, float gy, float gz) {
-    const Tri a = tri_setup(gx, d.x), b = tri_setup(gy, d.y), c = tri_setup(gz, d.z);
-    const size_t sy = (size_t) d.x, sz = (size_t) d.x * d.y;
-    Cell r;
-    r.base = v + (size_t) a.g + (size_t) b.g * sy + (size_t) c.g * sz;
-    r.dx = (size_t) (a.h - a.g), r.dy = (size_t) (b.h - b.g) * sy, r.dz = (size_t) (c.h - c.g) * sz;
-    r.tx = a.t, r.ty = b.t, r.tz = c.t;
-    return r;
-}
-
-// lerp1(v0, v1, t) weights v0 by t (sobfu_device.hpp): the same nesting as interp_tsdf -- z, then y, then x
-SOBFU_DEV float tri_lerp(const Cell& c, float ggg, float ggh, float ghg, float ghh, float hgg, float hgh, float hhg, float hhh) {
-    return lerp1(lerp1(lerp1(hhh, hhg, c.tz), lerp1(hgh, hgg, c.tz), c.ty), lerp1(lerp1(ghh, ghg, c.tz), lerp1(ggh, ggg, c.tz), c.ty), c.tx);
-}
-
-// trilinear tsdf + validity (all 8 corner weights > 0).  Unlike interp_tsdf's nearest-floor weight, a cleared (0, 0) voxel or one
-// behind the surface beyond eta among the corners makes the sample invalid: it can never be one side of a surface crossing.
-SOBFU_DEV float sample_tsdf(const float2* __restrict__ v, const Dims& d, float gx, float gy, float gz, bool& valid) {
-    const Cell c = cell_at(v, d, gx, gy, gz);
-    const float2 ggg = c.base[0], ggh = c.base[c.dz], ghg = c.base[c.dy], ghh = c.base[c.dy + c.dz];
-    const float2 hgg = c.base[c.dx], hgh = c.base[c.dx + c.dz], hhg = c.base[c.dx + c.dy], hhh = c.base[c.dx + c.dy + c.dz];
-    valid = fminf(fminf(fminf(ggg.y, ggh.y), fminf(ghg.y, ghh.y)), fminf(fminf(hgg.y, hgh.y), fminf(hhg.y, hhh.y))) > 0.f;
-    return tri_lerp(c, ggg.x, ggh.x, ghg.x, ghh.x, hgg.x, hgh.x, hhg.x, hhh.x);
-}
-
-SOBFU_DEV float sample_tsdf_only(const float2* __restrict__ v, const Dims& d, float gx, float gy, float gz) {
-    const Cell c = cell_at(v, d, gx, gy, gz);
-    return tri_lerp(c, c.base[0].x, c.base[c.dz].x, c.base[c.dy].x, c.base[c.dy + c.dz].x, c.base[c.dx].x, c.base[c.dx + c.dz].x,
-                    c.base[c.dx + c.dy].x, c.base[c.dx + c.dy + c.dz].x);
-}
-
 // [tmin, tmax] &= the z range where o + z D stays in [0, top] (one slab; D == 0: all or nothing)
 SOBFU_DEV void clip_slab(float o, float D, float top, float& tmin, float& tmax) {
     if (D == 0.f) {
@@ -96,8 +59,8 @@ __global__ void __launch_bounds__(256) raycast_kernel(RaycastArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int u = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), v = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
     if (u >= a.cols || v >= a.rows) return;
-    float4* P = (float4*) ((char*) a.points + (size_t) v * a.points_step) + u;
-    float4* N = (float4*) ((char*) a.normals + (size_t) v * a.normals_step) + u;
+    float4* P = row_ptr(a.points, a.points_step, v) + u;
+    float4* N = row_ptr(a.normals, a.normals_step, v) + u;
 
     const float dx = ((float) u - a.cx) / a.fx, dy = ((float) v - a.cy) / a.fy;
     const float Dx = dot3(a.Rt + 0, dx, dy, 1.f) / a.vsx, Dy = dot3(a.Rt + 3, dx, dy, 1.f) / a.vsy, Dz = dot3(a.Rt + 6, dx, dy, 1.f) / a.vsz;
@@ -153,38 +116,28 @@ struct ShadeArgs {
     int image_step;
 };
 
-SOBFU_DEV unsigned char to_byte(float x) { return (unsigned char) fminf(255.f, fmaxf(0.f, floorf(x + 0.5f))); }
-
 // renderImage: headlight-style Lambertian grey, I = 0.2 + 0.8 max(0, n . l), BGRA
 __global__ void __launch_bounds__(256) render_image_kernel(ShadeArgs a) {
     const int u = blockIdx.x * 64 + threadIdx.x, v = blockIdx.y * 4 + threadIdx.y;
     if (u >= a.cols || v >= a.rows) return;
-    const float4 n = *((const float4*) ((const char*) a.normals + (size_t) v * a.normals_step) + u);
+    const float4 n = row_ptr(a.normals, a.normals_step, v)[u];
     uchar4 px = make_uchar4(0, 0, 0, 0);
     if (n.w != 0.f) {
-        const float4 p = *((const float4*) ((const char*) a.points + (size_t) v * a.points_step) + u);
-        const float lx = a.lx - p.x, ly = a.ly - p.y, lz = a.lz - p.z;
-        const float ll = __builtin_sqrtf(lx * lx + ly * ly + lz * lz);
-        const float ndl = n.x * (lx / ll) + n.y * (ly / ll) + n.z * (lz / ll);
-        const unsigned char g = to_byte(255.f * (0.2f + 0.8f * fmaxf(0.f, ndl)));
+        const unsigned char g = to_byte(255.f * lambert(n, row_ptr(a.points, a.points_step, v)[u], a.lx, a.ly, a.lz));
         px = make_uchar4(g, g, g, 255);
     }
-    *((uchar4*) ((char*) a.image + (size_t) v * a.image_step) + u) = px;
+    row_ptr(a.image, a.image_step, v)[u] = px;
 }
 
 // renderTangentColors: (r, g, b) = (n * 0.5 + 0.5) * 255, BGRA
 __global__ void __launch_bounds__(256) render_normals_kernel(ShadeArgs a) {
     const int u = blockIdx.x * 64 + threadIdx.x, v = blockIdx.y * 4 + threadIdx.y;
     if (u >= a.cols || v >= a.rows) return;
-    const float4 n = *((const float4*) ((const char*) a.normals + (size_t) v * a.normals_step) + u);
+    const float4 n = row_ptr(a.normals, a.normals_step, v)[u];
     uchar4 px = make_uchar4(0, 0, 0, 0);
     if (n.w != 0.f) px = make_uchar4(to_byte((n.z * 0.5f + 0.5f) * 255.f), to_byte((n.y * 0.5f + 0.5f) * 255.f), to_byte((n.x * 0.5f + 0.5f) * 255.f), 255);
-    *((uchar4*) ((char*) a.image + (size_t) v * a.image_step) + u) = px;
+    row_ptr(a.image, a.image_step, v)[u] = px;
 }
-
-bool aligned(const void* p, int step, int to) { return ((uintptr_t) p % (uintptr_t) to) == 0 && step % to == 0; }
-bool positive_finite(float x) { return std::isfinite(x) && x > 0.f; }
-dim3 shade_grid(int rows, int cols) { return dim3((unsigned) ((cols + 63) / 64), (unsigned) ((rows + 3) / 4)); }
 
 }  // namespace
 
@@ -199,16 +152,13 @@ int sobfu_hip_raycast(const float* d_vol, int X, int Y, int Z, float vsx, float 
     SOBFU_CHECK_ARGS(aligned(d_points, points_step, 16) && aligned(d_normals, normals_step, 16));
     SOBFU_CHECK_ARGS(positive_finite(trunc) && positive_finite(step_factor));
     SOBFU_CHECK_ARGS(positive_finite(vsx) && positive_finite(vsy) && positive_finite(vsz));
-    SOBFU_CHECK_ARGS(std::isfinite(fx) && std::isfinite(fy) && fx != 0.f && fy != 0.f && std::isfinite(cx) && std::isfinite(cy));
+    SOBFU_CHECK_ARGS(intr_ok(fx, fy, cx, cy));
     RaycastArgs a{(const float2*) d_vol, {X, Y, Z}, vsx, vsy, vsz, trunc, {}, {}, {}, fx, fy, cx, cy, rows, cols, 0.f, 0,
                   (float4*) d_points, points_step, (float4*) d_normals, normals_step};
-    for (int i = 0; i < 9; ++i) a.R[i] = R[i];
+    fill_pose(R, t, a.R, a.Rt, nullptr);
     for (int i = 0; i < 3; ++i) {
         double o = 0.0;
-        for (int j = 0; j < 3; ++j) {
-            a.Rt[3 * i + j] = R[3 * j + i];
-            o -= (double) R[3 * j + i] * (double) t[j];
-        }
+        for (int j = 0; j < 3; ++j) o -= (double) R[3 * j + i] * (double) t[j];
         a.o[i] = (float) o;
     }
     a.fine = step_factor * fminf(vsx, fminf(vsy, vsz));
@@ -226,7 +176,7 @@ int sobfu_hip_render_image(const float* d_points, int points_step, const float* 
     SOBFU_CHECK_ARGS(points_step >= cols * 16 && normals_step >= cols * 16 && image_step >= cols * 4);
     SOBFU_CHECK_ARGS(aligned(d_points, points_step, 16) && aligned(d_normals, normals_step, 16) && aligned(d_image, image_step, 4));
     ShadeArgs a{(const float4*) d_points, points_step, (const float4*) d_normals, normals_step, rows, cols, lx, ly, lz, (uchar4*) d_image, image_step};
-    hipLaunchKernelGGL(render_image_kernel, shade_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, a);
+    hipLaunchKernelGGL(render_image_kernel, image_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, a);
     return (int) hipGetLastError();
 }
 
@@ -235,7 +185,7 @@ int sobfu_hip_render_normals(const float* d_normals, int normals_step, int rows,
     SOBFU_CHECK_ARGS(normals_step >= cols * 16 && image_step >= cols * 4);
     SOBFU_CHECK_ARGS(aligned(d_normals, normals_step, 16) && aligned(d_image, image_step, 4));
     ShadeArgs a{nullptr, 0, (const float4*) d_normals, normals_step, rows, cols, 0.f, 0.f, 0.f, (uchar4*) d_image, image_step};
-    hipLaunchKernelGGL(render_normals_kernel, shade_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, a);
+    hipLaunchKernelGGL(render_normals_kernel, image_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, a);
     return (int) hipGetLastError();
 }
 

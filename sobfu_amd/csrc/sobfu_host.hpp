@@ -1,7 +1,12 @@
-// Host-side helpers shared by the C-ABI translation units.
+// Host-side helpers shared by the C-ABI translation units; the argument checks, image grid and pose fill are the frame-side units'
+// (their device-side rules: sobfu_frame.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdint>
 
 #include "sobfu_hip.h"
 
@@ -21,3 +26,25 @@
         int _rc = (expr);                     \
         if (_rc != 0) return _rc;             \
     } while (0)
+
+namespace sobfu_hip {
+
+// the pointer and the row size of its pitched image (bytes; 0 for a dense array) are multiples of `to`
+inline bool aligned(const void* p, long long step, int to) { return ((uintptr_t) p % (uintptr_t) to) == 0 && step % to == 0; }
+inline bool positive_finite(float x) { return std::isfinite(x) && x > 0.f; }
+inline bool intr_ok(float fx, float fy, float cx, float cy) {
+    return std::isfinite(fx) && std::isfinite(fy) && fx != 0.f && fy != 0.f && std::isfinite(cx) && std::isfinite(cy);
+}
+constexpr int kGridZ = 65535;  // volume_ok's max_z for a launch with one z-slice per blockIdx.z (voxel_grid); INT_MAX for a 1-D launch
+inline bool volume_ok(int X, int Y, int Z, int max_z) { return X > 0 && Y > 0 && Z > 0 && Z <= max_z && (long long) X * Y * Z <= (1LL << 40); }
+inline dim3 image_grid(int rows, int cols) { return dim3((unsigned) ((cols + 63) / 64), (unsigned) ((rows + 3) / 4)); }
+// (R row-major, t) of the C ABI into a kernel's arguments: R, its transpose and t, each where the kernel wants it (NULL: not wanted)
+inline void fill_pose(const float R[9], const float t[3], float* R_out, float* Rt_out, float* t_out) {
+    for (int i = 0; i < 9; ++i) {
+        if (R_out) R_out[i] = R[i];
+        if (Rt_out) Rt_out[i] = R[3 * (i % 3) + i / 3];
+    }
+    for (int i = 0; i < 3 && t_out; ++i) t_out[i] = t[i];
+}
+
+}  // namespace sobfu_hip

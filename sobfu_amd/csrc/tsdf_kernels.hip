@@ -3,7 +3,7 @@
 // Launch shape: true 3-D grids (sobfu_device.hpp) instead of the reference's 2-D block(64,16) z-loop; the
 // z-accumulated quantities (vc_cam.z, vc.z) are rebuilt per voxel by the same chain of float additions so
 // the values stay bit-identical to the reference's running sums.
-#include "sobfu_device.hpp"
+#include "sobfu_frame.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
 
@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(256) integrate_depth_kernel(IntegrateArgs a) {
         if (!(camz > 0)) continue;
         if (!(coox == coox) || !(cooy == cooy)) continue;
         int px = (int) floorf(coox), py = (int) floorf(cooy);
-        float Dp = *(const float*) ((const char*) a.dists + (size_t) py * a.step + (size_t) px * 4);
+        float Dp = row_ptr(a.dists, a.step, py)[px];
         if (Dp <= 0.f) continue;
         float psdf   = Dp - camz;
         float weight = (psdf > -a.eta) ? 1.f : 0.f;
@@ -137,13 +137,12 @@ __global__ void __launch_bounds__(256) bilateral_kernel(const uint16_t* src, int
                                                         int rows, int cols, int ksz, float sss, float sds) {
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= cols || y >= rows) return;
-    auto S = [&](int yy, int xx) { return (int) *(const uint16_t*) ((const char*) src + (size_t) yy * sstep + (size_t) xx * 2); };
-    int value = S(y, x);
+    int value = row_ptr(src, sstep, y)[x];
     int tx = min(x - ksz / 2 + ksz, cols - 1), ty = min(y - ksz / 2 + ksz, rows - 1);
     float sum1 = 0, sum2 = 0;
     for (int cy = max(y - ksz / 2, 0); cy < ty; ++cy)
         for (int cx = max(x - ksz / 2, 0); cx < tx; ++cx) {
-            int depth    = S(cy, cx);
+            int depth    = row_ptr(src, sstep, cy)[cx];
             float space2 = (float) ((x - cx) * (x - cx) + (y - cy) * (y - cy));
             float color2 = (float) (int) ((unsigned) (value - depth) * (unsigned) (value - depth));
             float weight = expf(-(space2 * sss + color2 * sds));
@@ -152,14 +151,14 @@ __global__ void __launch_bounds__(256) bilateral_kernel(const uint16_t* src, int
         }
     float q = sum1 / sum2;
     int r   = (q == q) ? (int) rintf(q) : 0;
-    *(uint16_t*) ((char*) dst + (size_t) y * dstep + (size_t) x * 2) = (uint16_t) r;
+    row_ptr(dst, dstep, y)[x] = (uint16_t) r;
 }
 
 // truncate_depth_kernel -- imgproc.cu:60-68
 __global__ void truncate_depth_kernel(uint16_t* depth, int step, int rows, int cols, uint16_t max_mm) {
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= cols || y >= rows) return;
-    uint16_t* p = (uint16_t*) ((char*) depth + (size_t) y * step) + x;
+    uint16_t* p = row_ptr(depth, step, y) + x;
     if (*p > max_mm) *p = 0;
 }
 
@@ -171,12 +170,11 @@ __global__ void compute_dists_kernel(const uint16_t* depth, int dstep, float* di
     if (x >= cols || y >= rows) return;
     float xl = (x - cx) * fix, yl = (y - cy) * fiy;
     float lambda = __builtin_sqrtf(xl * xl + yl * yl + 1);
-    int dv       = *((const uint16_t*) ((const char*) depth + (size_t) y * dstep) + x);
-    *((float*) ((char*) dists + (size_t) y * sstep) + x) = dv * lambda * 0.001f;
+    int dv       = row_ptr(depth, dstep, y)[x];
+    row_ptr(dists, sstep, y)[x] = dv * lambda * 0.001f;
 }
 
 inline dim3 chunk_grid(int X, int Y, int Z) { return dim3((X + kBX - 1) / kBX, (Y + kBY - 1) / kBY, (Z + kZC - 1) / kZC); }
-inline dim3 img_grid(int rows, int cols) { return dim3((cols + 63) / 64, (rows + 3) / 4); }
 
 template <int P>
 int launch_prim(float* d_vol, int X, int Y, int Z, const float vs[3], float trunc, float eta, const float* p, int np,
@@ -202,8 +200,7 @@ int sobfu_hip_integrate_depth(const float* d_dists, int step, int rows, int cols
                               float fy, float cx, float cy, void* stream) {
     SOBFU_CHECK_ARGS(d_dists && d_vol && vs && R && t && X > 0 && Y > 0 && Z > 0 && rows > 0 && cols > 0 && step >= cols * 4);
     IntegrateArgs a{d_dists, step, rows, cols, (float2*) d_vol, {X, Y, Z}, vs[0], vs[1], vs[2], trunc, eta, {}, {}, fx, fy, cx, cy, 0, 0, 0};
-    for (int i = 0; i < 9; ++i) a.R[i] = R[i];
-    for (int i = 0; i < 3; ++i) a.t[i] = t[i];
+    fill_pose(R, t, a.R, nullptr, a.t);
     hipLaunchKernelGGL(integrate_depth_kernel, chunk_grid(X, Y, Z), voxel_block(), 0, (hipStream_t) stream, a);
     return (int) hipGetLastError();
 }
@@ -214,8 +211,7 @@ int sobfu_hip_tile3_integrate_depth(const float* d_dists, int step, int rows, in
     SOBFU_CHECK_ARGS(d_dists && d_vol_local && vs && R && t && Lx > 0 && Ly > 0 && Lz > 0 && xb >= 0 && yb >= 0 && zb >= 0 && rows > 0 &&
                      cols > 0 && step >= cols * 4);
     IntegrateArgs a{d_dists, step, rows, cols, (float2*) d_vol_local, {Lx, Ly, Lz}, vs[0], vs[1], vs[2], trunc, eta, {}, {}, fx, fy, cx, cy, zb, xb, yb};
-    for (int i = 0; i < 9; ++i) a.R[i] = R[i];
-    for (int i = 0; i < 3; ++i) a.t[i] = t[i];
+    fill_pose(R, t, a.R, nullptr, a.t);
     hipLaunchKernelGGL(integrate_depth_kernel, chunk_grid(Lx, Ly, Lz), voxel_block(), 0, (hipStream_t) stream, a);
     return (int) hipGetLastError();
 }
@@ -256,14 +252,14 @@ int sobfu_hip_bilateral_filter(const uint16_t* d_src, int sstep, uint16_t* d_dst
     sigma_depth *= 1000;  // metres -> mm (imgproc.cu:43)
     // (VALU-bound on the 49 correctly rounded expf of a pixel -- the reference's build uses the 2-instruction __expf; block shapes 64x1 .. 16x16
     //  all give 16 - 17 us at 640 x 480, measured in round 6)
-    hipLaunchKernelGGL(bilateral_kernel, img_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, d_src, sstep, d_dst,
+    hipLaunchKernelGGL(bilateral_kernel, image_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, d_src, sstep, d_dst,
                        dstep, rows, cols, ksz, 0.5f / (sigma_spatial * sigma_spatial), 0.5f / (sigma_depth * sigma_depth));
     return (int) hipGetLastError();
 }
 
 int sobfu_hip_truncate_depth(uint16_t* d_depth, int step, int rows, int cols, float max_dist_m, void* stream) {
     SOBFU_CHECK_ARGS(d_depth && rows > 0 && cols > 0);
-    hipLaunchKernelGGL(truncate_depth_kernel, img_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, d_depth, step, rows,
+    hipLaunchKernelGGL(truncate_depth_kernel, image_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, d_depth, step, rows,
                        cols, (uint16_t) (max_dist_m * 1000.f));
     return (int) hipGetLastError();
 }
@@ -271,7 +267,7 @@ int sobfu_hip_truncate_depth(uint16_t* d_depth, int step, int rows, int cols, fl
 int sobfu_hip_compute_dists(const uint16_t* d_depth, int dstep, float* d_dists, int sstep, int rows, int cols, float fx,
                             float fy, float cx, float cy, void* stream) {
     SOBFU_CHECK_ARGS(d_depth && d_dists && rows > 0 && cols > 0);
-    hipLaunchKernelGGL(compute_dists_kernel, img_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, d_depth, dstep,
+    hipLaunchKernelGGL(compute_dists_kernel, image_grid(rows, cols), dim3(64, 4), 0, (hipStream_t) stream, d_depth, dstep,
                        d_dists, sstep, rows, cols, 1.f / fx, 1.f / fy, cx, cy);
     return (int) hipGetLastError();
 }

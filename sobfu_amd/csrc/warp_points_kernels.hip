@@ -10,7 +10,7 @@
 //             frame, and mc_vertices as in sobfu_hip_sample_colour: 1 = the points are marching-cubes vertices (x, -y, -z, 1) under the
 //             marching-cubes pose, and the flip is undone first; 0 = plain points
 //   direction v -> psi(v): psi maps a canonical position to its live position, so the canonical surface is carried forwards
-//   position  1. w = unflip(v); g_i = dot3(R^T_i, w - t) / vs_i - 0.5f: sample_colour's mapping (colour_kernels.hip)
+//   position  1. w = unflip(v); g_i = dot3(R^T_i, w - t) / vs_i - 0.5f: sample_colour's mapping (grid_position, sobfu_frame.hpp)
 //             2. u = interp_disp(psi, g) (sobfu_device.hpp): tri_setup's clamp and upper-index rule, corner displacement psi - id, the
 //                lerp chain z, then y, then x
 //             3. delta_i = dot3(R_i, u.x vs.x, u.y vs.y, u.z vs.z); the output is flip(w + delta), w = 1.  The vertex is not rebuilt
@@ -23,14 +23,14 @@
 //                division), each row (c0 m0 + c1 m1) + c2 m2, negated when det J = (J00 c00 + J01 c01) + J02 c02 < 0; m' times
 //                1 / sqrt((m'x^2 + m'y^2) + m'z^2); the output is flip(R m') with w = 1.  A zero input normal, or a zero or non-finite
 //                squared length, gives (0, 0, 0, 1): the indexed mesh's "no normal"
-//   sample    sample_tsdf: the mapping of step 1, then the raycaster's sampler (render_kernels.hip): trilinear TSDF, valid only when all
-//             eight corner weights are > 0.  One float per point: the TSDF (units of the truncation distance), NaN where not valid
+//   sample    sample_tsdf: the mapping of step 1, then the raycaster's sampler (sample_tsdf, sobfu_frame.hpp): trilinear TSDF, valid only
+//             when all eight corner weights are > 0.  One float per point: the TSDF (units of the truncation distance), NaN where not valid
 //
 // Launch shape: one lane per point, 256-thread workgroups.  Indexed-mesh vertices arrive in ascending owner-voxel order (x fastest), so
 // the lanes of a wave are neighbours on the surface and share psi's cache lines: psi and the volume are taken with plain cached loads,
 // points and normals as 16-byte loads and stores.  No LDS, no atomics.  Each lane reads its point and normal before it writes them:
 // output = input is allowed.
-#include "sobfu_device.hpp"
+#include "sobfu_frame.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
 
@@ -64,15 +64,6 @@ struct SampleTsdfArgs {
     float* out;
 };
 
-// step 1: the unflipped point w and its grid position g
-SOBFU_DEV void grid_position(const PointMap& m, const float4& p, float& wx, float& wy, float& wz, float& gx, float& gy, float& gz) {
-    wx = p.x, wy = m.flip ? -p.y : p.y, wz = m.flip ? -p.z : p.z;
-    const float qx = wx - m.t[0], qy = wy - m.t[1], qz = wz - m.t[2];
-    gx = dot3(m.Rt + 0, qx, qy, qz) / m.vsx - 0.5f;
-    gy = dot3(m.Rt + 3, qx, qy, qz) / m.vsy - 0.5f;
-    gz = dot3(m.Rt + 6, qx, qy, qz) / m.vsz - 0.5f;
-}
-
 SOBFU_DEV float4 diff4(const float4& a, const float4& b) { return f4(a.x - b.x, a.y - b.y, a.z - b.z); }
 
 template <bool NORMALS>
@@ -83,7 +74,7 @@ __global__ void __launch_bounds__(256) warp_points_kernel(WarpArgs a) {
     float4 nin = make_float4(0.f, 0.f, 0.f, 0.f);
     if (NORMALS) nin = a.normals[i];
     float wx, wy, wz, gx, gy, gz;
-    grid_position(a.m, p, wx, wy, wz, gx, gy, gz);
+    grid_position(a.m, p, wx, wy, wz, gx, gy, gz);  // step 1
 
     const Dims d = a.m.d;
     const Tri tx = tri_setup(gx, d.x), ty = tri_setup(gy, d.y), tz = tri_setup(gz, d.z);
@@ -132,30 +123,14 @@ __global__ void __launch_bounds__(256) sample_tsdf_points_kernel(SampleTsdfArgs 
     if (i >= a.m.n) return;
     float wx, wy, wz, gx, gy, gz;
     grid_position(a.m, a.points[i], wx, wy, wz, gx, gy, gz);
-    // the raycaster's sampler (render_kernels.hip: cell_at, sample_tsdf, tri_lerp)
-    const Dims d = a.m.d;
-    const Tri tx = tri_setup(gx, d.x), ty = tri_setup(gy, d.y), tz = tri_setup(gz, d.z);
-    const size_t sy = (size_t) d.x, sz = (size_t) d.x * d.y;
-    const float2* base = a.vol + (size_t) tx.g + (size_t) ty.g * sy + (size_t) tz.g * sz;
-    const size_t ex = (size_t) (tx.h - tx.g), ey = (size_t) (ty.h - ty.g) * sy, ez = (size_t) (tz.h - tz.g) * sz;
-    const float2 ggg = base[0], ggh = base[ez], ghg = base[ey], ghh = base[ey + ez];
-    const float2 hgg = base[ex], hgh = base[ex + ez], hhg = base[ex + ey], hhh = base[ex + ey + ez];
-    const bool valid = fminf(fminf(fminf(ggg.y, ggh.y), fminf(ghg.y, ghh.y)), fminf(fminf(hgg.y, hgh.y), fminf(hhg.y, hhh.y))) > 0.f;
-    const float f = lerp1(lerp1(lerp1(hhh.x, hhg.x, tz.t), lerp1(hgh.x, hgg.x, tz.t), ty.t),
-                          lerp1(lerp1(ghh.x, ghg.x, tz.t), lerp1(ggh.x, ggg.x, tz.t), ty.t), tx.t);
+    bool valid;
+    const float f = sample_tsdf(a.vol, a.m.d, gx, gy, gz, valid);
     a.out[i] = valid ? f : __builtin_nanf("");
 }
 
-bool aligned16(const void* p) { return ((uintptr_t) p % 16u) == 0; }
-bool positive_finite(float x) { return std::isfinite(x) && x > 0.f; }
-bool volume_ok(int X, int Y, int Z) { return X > 0 && Y > 0 && Z > 0 && (long long) X * Y * Z <= (1LL << 40); }
-
 PointMap point_map(int X, int Y, int Z, const float vs[3], const float R[9], const float t[3], int mc_vertices, int n) {
     PointMap m{{X, Y, Z}, vs[0], vs[1], vs[2], {}, {}, {}, mc_vertices ? 1 : 0, n};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) m.R[3 * i + j] = R[3 * i + j], m.Rt[3 * i + j] = R[3 * j + i];
-        m.t[i] = t[i];
-    }
+    fill_pose(R, t, m.R, m.Rt, m.t);
     return m;
 }
 
@@ -165,9 +140,10 @@ extern "C" {
 
 int sobfu_hip_warp_points(const float* d_psi, int X, int Y, int Z, const float vs[3], const float R[9], const float t[3], int mc_vertices,
                           const float* d_points, const float* d_normals, int n, float* d_points_out, float* d_normals_out, void* stream) {
-    SOBFU_CHECK_ARGS(d_psi && vs && R && t && d_points && d_points_out && volume_ok(X, Y, Z) && n >= 0);
+    SOBFU_CHECK_ARGS(d_psi && vs && R && t && d_points && d_points_out && volume_ok(X, Y, Z, INT_MAX) && n >= 0);
     SOBFU_CHECK_ARGS((d_normals != nullptr) == (d_normals_out != nullptr));
-    SOBFU_CHECK_ARGS(aligned16(d_psi) && aligned16(d_points) && aligned16(d_points_out) && aligned16(d_normals) && aligned16(d_normals_out));
+    SOBFU_CHECK_ARGS(aligned(d_psi, 0, 16) && aligned(d_points, 0, 16) && aligned(d_points_out, 0, 16));
+    SOBFU_CHECK_ARGS(aligned(d_normals, 0, 16) && aligned(d_normals_out, 0, 16));
     SOBFU_CHECK_ARGS(positive_finite(vs[0]) && positive_finite(vs[1]) && positive_finite(vs[2]));
     if (n == 0) return 0;
     WarpArgs a{(const float4*) d_psi, point_map(X, Y, Z, vs, R, t, mc_vertices, n), (const float4*) d_points, (const float4*) d_normals,
@@ -180,8 +156,8 @@ int sobfu_hip_warp_points(const float* d_psi, int X, int Y, int Z, const float v
 
 int sobfu_hip_sample_tsdf(const float* d_vol, int X, int Y, int Z, const float vs[3], const float R[9], const float t[3], int mc_vertices,
                           const float* d_points, int n, float* d_out, void* stream) {
-    SOBFU_CHECK_ARGS(d_vol && vs && R && t && d_points && d_out && volume_ok(X, Y, Z) && n >= 0);
-    SOBFU_CHECK_ARGS(((uintptr_t) d_vol % 8u) == 0 && aligned16(d_points) && ((uintptr_t) d_out % 4u) == 0);
+    SOBFU_CHECK_ARGS(d_vol && vs && R && t && d_points && d_out && volume_ok(X, Y, Z, INT_MAX) && n >= 0);
+    SOBFU_CHECK_ARGS(aligned(d_vol, 0, 8) && aligned(d_points, 0, 16) && aligned(d_out, 0, 4));
     SOBFU_CHECK_ARGS(positive_finite(vs[0]) && positive_finite(vs[1]) && positive_finite(vs[2]));
     if (n == 0) return 0;
     SampleTsdfArgs a{(const float2*) d_vol, point_map(X, Y, Z, vs, R, t, mc_vertices, n), (const float4*) d_points, d_out};

@@ -45,6 +45,14 @@ def _f(x):
     return C.c_float(float(x))
 
 
+def _pose(R, t):
+    return (_F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)]), _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)]))
+
+
+def _vs3(voxel_size):
+    return _F3(*[float(v) for v in voxel_size])
+
+
 def new_volume(dims, device="cuda"):
     X, Y, Z = dims
     return torch.zeros((Z, Y, X, 2), dtype=torch.float32, device=device)
@@ -66,24 +74,21 @@ def clear_volume(vol):
 
 
 def integrate_depth(dists, vol, voxel_size, trunc, eta, R, t, intr):
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     assert dists.is_cuda and dists.dtype == torch.float32 and dists.stride(1) == 1
     check(_lib.lib().sobfu_hip_integrate_depth(C.c_void_p(dists.data_ptr()), C.c_int(dists.stride(0) * 4),
                                                C.c_int(dists.shape[0]), C.c_int(dists.shape[1]), _ptr(vol), *_xyz(vol),
-                                               _F3(*[float(v) for v in voxel_size]), _f(trunc), _f(eta), Rm, tv,
-                                               _f(intr[0]), _f(intr[1]), _f(intr[2]), _f(intr[3]), _stream()),
-          "integrate_depth")
+                                               _vs3(voxel_size), _f(trunc), _f(eta), Rm, tv, _f(intr[0]), _f(intr[1]), _f(intr[2]), _f(intr[3]),
+                                               _stream()), "integrate_depth")
 
 
 def tile3_integrate_depth(dists, vol_local, base, voxel_size, trunc, eta, R, t, intr):
     """integrate(depth) into a tile whose local cell (0, 0, 0) is global cell `base` = (xb, yb, zb) (multi-GPU tiles)"""
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     assert dists.is_cuda and dists.dtype == torch.float32 and dists.stride(1) == 1
     check(_lib.lib().sobfu_hip_tile3_integrate_depth(C.c_void_p(dists.data_ptr()), C.c_int(dists.stride(0) * 4), C.c_int(dists.shape[0]),
                                                      C.c_int(dists.shape[1]), _ptr(vol_local), *_xyz(vol_local), *[C.c_int(int(b)) for b in base],
-                                                     _F3(*[float(v) for v in voxel_size]), _f(trunc), _f(eta), Rm, tv, _f(intr[0]),
+                                                     _vs3(voxel_size), _f(trunc), _f(eta), Rm, tv, _f(intr[0]),
                                                      _f(intr[1]), _f(intr[2]), _f(intr[3]), _stream()), "tile3_integrate_depth")
 
 
@@ -93,28 +98,28 @@ def integrate_fuse(phi_global, phi_n_psi, max_weight):
 
 
 def init_sphere(vol, voxel_size, trunc, eta, centre, radius):
-    check(_lib.lib().sobfu_hip_init_sphere(_ptr(vol), *_xyz(vol), _F3(*[float(v) for v in voxel_size]), _f(trunc),
+    check(_lib.lib().sobfu_hip_init_sphere(_ptr(vol), *_xyz(vol), _vs3(voxel_size), _f(trunc),
                                            _f(eta), _F3(*[float(np.float32(v)) for v in centre]), _f(np.float32(radius)),
                                            _stream()), "init_sphere")
 
 
 def init_box(vol, voxel_size, trunc, b):
-    check(_lib.lib().sobfu_hip_init_box(_ptr(vol), *_xyz(vol), _F3(*[float(v) for v in voxel_size]), _f(trunc),
+    check(_lib.lib().sobfu_hip_init_box(_ptr(vol), *_xyz(vol), _vs3(voxel_size), _f(trunc),
                                         _F3(*[float(v) for v in b]), _stream()), "init_box")
 
 
 def init_ellipsoid(vol, voxel_size, trunc, r):
-    check(_lib.lib().sobfu_hip_init_ellipsoid(_ptr(vol), *_xyz(vol), _F3(*[float(v) for v in voxel_size]), _f(trunc),
+    check(_lib.lib().sobfu_hip_init_ellipsoid(_ptr(vol), *_xyz(vol), _vs3(voxel_size), _f(trunc),
                                               _F3(*[float(v) for v in r]), _stream()), "init_ellipsoid")
 
 
 def init_plane(vol, voxel_size, trunc, z):
-    check(_lib.lib().sobfu_hip_init_plane(_ptr(vol), *_xyz(vol), _F3(*[float(v) for v in voxel_size]), _f(trunc), _f(z),
+    check(_lib.lib().sobfu_hip_init_plane(_ptr(vol), *_xyz(vol), _vs3(voxel_size), _f(trunc), _f(z),
                                           _stream()), "init_plane")
 
 
 def init_torus(vol, voxel_size, trunc, t):
-    check(_lib.lib().sobfu_hip_init_torus(_ptr(vol), *_xyz(vol), _F3(*[float(v) for v in voxel_size]), _f(trunc),
+    check(_lib.lib().sobfu_hip_init_torus(_ptr(vol), *_xyz(vol), _vs3(voxel_size), _f(trunc),
                                           _F2(*[float(v) for v in t]), _stream()), "init_torus")
 
 
@@ -402,8 +407,7 @@ def mc_offsets(occ, count, workspace=None):
 
 def mc_generate_triangles(vol, occ, count, volume_size, R, t, vertices, normals):
     """generateTriangles into float4 buffers (n, 4)"""
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     assert vertices.shape == normals.shape and vertices.shape[1] == 4
     check(_lib.lib().sobfu_hip_mc_generate_triangles(_stream(), _ptr(vol), *_xyz(vol), _ptr(occ, torch.int32), C.c_int(occ.shape[1]),
                                                      C.c_int(int(count)), _f(volume_size[0]), _f(volume_size[1]), _f(volume_size[2]), Rm, tv,
@@ -445,8 +449,7 @@ def marching_cubes_indexed(vol, volume_size, R=np.eye(3), t=(0, 0, 0), workspace
     L = _lib.lib()
     if workspace is None:
         workspace = mc_indexed_workspace(vol)
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     active, nv, nt = C.c_int(0), C.c_int(0), C.c_int(0)
     ws = _ws(workspace)
     check(L.sobfu_hip_mc_indexed_count(_stream(), _ptr(vol), *_xyz(vol), *ws, C.byref(active), C.byref(nv), C.byref(nt)), "mc_indexed_count")
@@ -475,8 +478,7 @@ def raycast(vol, voxel_size, trunc, R, t, intr, rows=480, cols=640, step_factor=
     """Raycasts a TSDF volume (Z, Y, X, 2) from the camera of vol2cam = (R, t) (the pose integrate_depth takes) with intrinsics
     intr = (fx, fy, cx, cy) -> (points, normals), two (rows, cols, 4) float32 tensors in the camera frame; normals[..., 3] is 1 on a
     hit and 0 on a miss (where both are all zero).  `points` / `normals` may be given to render into existing buffers."""
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     if points is None:
         points = torch.empty((rows, cols, 4), dtype=torch.float32, device=vol.device)
     if normals is None:
@@ -530,13 +532,12 @@ def _colour_ptr(t):
 def integrate_colour(image, tsdf, psi, colour, voxel_size, R, t, intr, cap):
     """Fuses a (rows, cols, 4) uint8 BGRA frame, registered to the depth camera of vol2cam = (R, t) with intr = (fx, fy, cx, cy), into
     `colour` through `tsdf` (the volume about to be fused) and `psi` (None = identity)."""
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     if tuple(colour.shape[:3]) != tuple(tsdf.shape[:3]) or (psi is not None and tuple(psi.shape[:3]) != tuple(tsdf.shape[:3])):
         raise ValueError("colour, tsdf and psi must have the same dims")
     check(_lib.lib().sobfu_hip_integrate_colour(*_image_ptr(image, torch.uint8, 4), C.c_int(image.shape[0]), C.c_int(image.shape[1]), _ptr(tsdf),
                                                 None if psi is None else _ptr(psi), _colour_ptr(colour), *_xyz(colour),
-                                                _F3(*[float(v) for v in voxel_size]), Rm, tv, _f(intr[0]), _f(intr[1]), _f(intr[2]), _f(intr[3]),
+                                                _vs3(voxel_size), Rm, tv, _f(intr[0]), _f(intr[1]), _f(intr[2]), _f(intr[3]),
                                                 C.c_int(int(cap)), _stream()), "integrate_colour")
 
 
@@ -553,8 +554,7 @@ def sample_colour(colour, voxel_size, R, t, points, normals=None, mc_vertices=Fa
     """Samples `colour` at float4 points of a frame whose pose from volume metres is (R, t): a (rows, cols, 4) raycast image (with its
     normals: misses give zeros) or an (n, 4) list (marching-cubes vertices with mc_vertices=True and the marching-cubes pose) -> uint8
     BGRA of the same leading shape; a point with no colour gives (0, 0, 0, 0)."""
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     flat = points.dim() == 2
     p3 = points.unsqueeze(0) if flat else points
     if out is None:
@@ -564,7 +564,7 @@ def sample_colour(colour, voxel_size, R, t, points, normals=None, mc_vertices=Fa
     if rows * cols == 0:
         return out
     nrm = (None, C.c_int(0)) if normals is None else _image_ptr(normals.unsqueeze(0) if normals.dim() == 2 else normals, torch.float32, 4)
-    check(_lib.lib().sobfu_hip_sample_colour(_colour_ptr(colour), *_xyz(colour), _F3(*[float(v) for v in voxel_size]), Rm, tv,
+    check(_lib.lib().sobfu_hip_sample_colour(_colour_ptr(colour), *_xyz(colour), _vs3(voxel_size), Rm, tv,
                                              C.c_int(1 if mc_vertices else 0), *_image_ptr(p3, torch.float32, 4), *nrm, C.c_int(rows),
                                              C.c_int(cols), *_image_ptr(o3, torch.uint8, 4), _stream()), "sample_colour")
     return out
@@ -593,8 +593,7 @@ def warp_points(psi, voxel_size, R, t, points, normals=None, mc_vertices=False, 
     """Carries (n, 4) points of a frame whose pose from volume metres is (R, t) (marching-cubes vertices with mc_vertices=True and the
     marching-cubes pose) through psi, v -> psi(v), and their normals (optional) through the cofactor matrix of psi's Jacobian -> points,
     or (points, normals).  `out`: a tensor (or, with normals, a pair) to write into; it may be the input."""
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     po, no = (out if normals is not None else (out, None)) if out is not None else (None, None)
     po = torch.empty_like(points) if po is None else po
     if normals is not None:
@@ -605,7 +604,7 @@ def warp_points(psi, voxel_size, R, t, points, normals=None, mc_vertices=False, 
         raise ValueError("the output must have the points' shape")
     if points.shape[0] == 0:  # an empty tensor has no address to hand over
         return po if normals is None else (po, no)
-    check(_lib.lib().sobfu_hip_warp_points(_ptr(psi), *_xyz(psi), _F3(*[float(v) for v in voxel_size]), Rm, tv, C.c_int(1 if mc_vertices else 0),
+    check(_lib.lib().sobfu_hip_warp_points(_ptr(psi), *_xyz(psi), _vs3(voxel_size), Rm, tv, C.c_int(1 if mc_vertices else 0),
                                            _point_list(points, "points"), None if normals is None else _point_list(normals, "normals"),
                                            C.c_int(points.shape[0]), _point_list(po, "points"), None if normals is None else _point_list(no, "normals"),
                                            _stream()), "warp_points")
@@ -615,15 +614,14 @@ def warp_points(psi, voxel_size, R, t, points, normals=None, mc_vertices=False, 
 def sample_tsdf(vol, voxel_size, R, t, points, mc_vertices=False, out=None):
     """The trilinear TSDF of `vol` (Z, Y, X, 2) at (n, 4) points (pose and mc_vertices as in warp_points) -> (n,) float32 in units of the
     truncation distance; NaN where one of the eight corners has no weight (the raycaster's validity rule)."""
-    Rm = _F9(*[float(v) for v in np.asarray(R, np.float32).reshape(9)])
-    tv = _F3(*[float(v) for v in np.asarray(t, np.float32).reshape(3)])
+    Rm, tv = _pose(R, t)
     if out is None:
         out = torch.empty(points.shape[0], dtype=torch.float32, device=points.device)
     if tuple(out.shape) != (points.shape[0],):
         raise ValueError("the output must hold one float per point")
     if points.shape[0] == 0:
         return out
-    check(_lib.lib().sobfu_hip_sample_tsdf(_ptr(vol), *_xyz(vol), _F3(*[float(v) for v in voxel_size]), Rm, tv, C.c_int(1 if mc_vertices else 0),
+    check(_lib.lib().sobfu_hip_sample_tsdf(_ptr(vol), *_xyz(vol), _vs3(voxel_size), Rm, tv, C.c_int(1 if mc_vertices else 0),
                                            _point_list(points, "points"), C.c_int(points.shape[0]), _ptr(out), _stream()), "sample_tsdf")
     return out
 
