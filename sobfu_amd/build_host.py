@@ -1,6 +1,8 @@
-"""Builds the C++ host-shell test driver (tests/cpp/host_shell_tests.cpp over include/sobfu_amd/sobfu.hpp) with g++.
+"""Builds the host-side C++ programs with g++: the headless app, the host-shell test driver (tests/cpp/host_shell_tests.cpp over
+include/sobfu_amd/sobfu.hpp) and the small tools under tests/cpp that the CPU tests drive.
 
-The shells are header-only host code; the driver links libsobfu_hip.so (C ABI) and libamdhip64.so."""
+The shells are header-only host code; what uses them links libsobfu_hip.so (C ABI) and libamdhip64.so.  The stand-alone tools need
+neither HIP nor the library."""
 from __future__ import annotations
 
 import os
@@ -8,142 +10,89 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, "build", "host_shell_tests")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+INC = os.path.join(ROOT, "include")
+CSRC = os.path.join(HERE, "csrc")
+LIB = os.path.join(HERE, "libsobfu_hip.so")
+SOBFU_HPP = os.path.join(INC, "sobfu_amd", "sobfu.hpp")
+DEPTH_IO_HPP = os.path.join(INC, "sobfu_amd", "depth_io.hpp")
+SOBFU_HIP_H = os.path.join(INC, "sobfu_hip.h")
 
 
-APP = os.path.join(ROOT, "build", "sobfu_headless")
+def _test_src(name: str) -> str:
+    return os.path.join(ROOT, "tests", "cpp", name)
 
 
-def _compile(src: str, out: str) -> None:
-    subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__",
-                           f"-I{ROCM}/include", f"-I{os.path.join(ROOT, 'include')}", src, "-o", out, f"-L{HERE}", "-lsobfu_hip",
-                           f"-L{ROCM}/lib", "-lamdhip64", "-lz", f"-Wl,-rpath,{HERE}", f"-Wl,-rpath,{ROCM}/lib", "-Wl,-rpath,$ORIGIN/../sobfu_amd"])
+def _build(out: str, src: str, deps, linked: bool, force: bool = False, flags=()) -> str:
+    """g++ `src` into build/`out` when it is missing or older than `src` / `deps`.  linked: against libsobfu_hip.so and the HIP
+    runtime (the library is then a dependency too); else a stand-alone program with `flags`."""
+    out = os.path.join(ROOT, "build", out)
+    deps = [src, *deps] + ([LIB] if linked else [])
+    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    if linked:
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__",
+                               f"-I{ROCM}/include", f"-I{INC}", src, "-o", out, f"-L{HERE}", "-lsobfu_hip",
+                               f"-L{ROCM}/lib", "-lamdhip64", "-lz", f"-Wl,-rpath,{HERE}", f"-Wl,-rpath,{ROCM}/lib", "-Wl,-rpath,$ORIGIN/../sobfu_amd"])
+    else:
+        subprocess.check_call(["g++", "-O2", "-Wall", f"-I{INC}", src, "-o", out, *flags])
+    return out
 
 
 def build_app(force: bool = False) -> str:
     """apps/sobfu_headless.cpp: the headless frame-loop app over the shells."""
-    src = os.path.join(ROOT, "apps", "sobfu_headless.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp"),
-            os.path.join(HERE, "libsobfu_hip.so")]
-    if force or not os.path.exists(APP) or any(os.path.getmtime(APP) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(APP), exist_ok=True)
-        _compile(src, APP)
-    return APP
-
-
-IO_TOOL = os.path.join(ROOT, "build", "depth_io_tool")
+    return _build("sobfu_headless", os.path.join(ROOT, "apps", "sobfu_headless.cpp"), [SOBFU_HPP, DEPTH_IO_HPP], True, force)
 
 
 def build_io_tool(force: bool = False) -> str:
     """tests/cpp/depth_io_tool.cpp: CPU-only driver of the depth readers / .npy writer (needs zlib only)."""
-    src = os.path.join(ROOT, "tests", "cpp", "depth_io_tool.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp")]
-    if force or not os.path.exists(IO_TOOL) or any(os.path.getmtime(IO_TOOL) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(IO_TOOL), exist_ok=True)
-        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", f"-I{os.path.join(ROOT, 'include')}", src, "-o", IO_TOOL, "-lz"])
-    return IO_TOOL
-
-
-PNG_TOOL = os.path.join(ROOT, "build", "png_write_tool")
+    return _build("depth_io_tool", _test_src("depth_io_tool.cpp"), [DEPTH_IO_HPP], False, force, ["-std=c++14", "-lz"])
 
 
 def build_png_tool(force: bool = False) -> str:
     """tests/cpp/png_write_tool.cpp: CPU-only driver of the PNG writer (needs zlib only)."""
-    src = os.path.join(ROOT, "tests", "cpp", "png_write_tool.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp")]
-    if force or not os.path.exists(PNG_TOOL) or any(os.path.getmtime(PNG_TOOL) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(PNG_TOOL), exist_ok=True)
-        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", f"-I{os.path.join(ROOT, 'include')}", src, "-o", PNG_TOOL, "-lz"])
-    return PNG_TOOL
-
-
-COLOUR_TOOL = os.path.join(ROOT, "build", "colour_io_tool")
+    return _build("png_write_tool", _test_src("png_write_tool.cpp"), [DEPTH_IO_HPP], False, force, ["-std=c++14", "-lz"])
 
 
 def build_colour_tool(force: bool = False) -> str:
     """tests/cpp/colour_io_tool.cpp: CPU-only driver of read_colour, the uint8 .npy writer and write_vtk (runs without a GPU)."""
-    src = os.path.join(ROOT, "tests", "cpp", "colour_io_tool.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp"), os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"),
-            os.path.join(ROOT, "include", "sobfu_hip.h"), os.path.join(HERE, "libsobfu_hip.so")]
-    if force or not os.path.exists(COLOUR_TOOL) or any(os.path.getmtime(COLOUR_TOOL) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(COLOUR_TOOL), exist_ok=True)
-        _compile(src, COLOUR_TOOL)
-    return COLOUR_TOOL
-
-
-PLY_TOOL = os.path.join(ROOT, "build", "ply_write_tool")
+    return _build("colour_io_tool", _test_src("colour_io_tool.cpp"), [DEPTH_IO_HPP, SOBFU_HPP, SOBFU_HIP_H], True, force)
 
 
 def build_ply_tool(force: bool = False) -> str:
     """tests/cpp/ply_write_tool.cpp: CPU-only driver of sobfu_amd::write_ply (runs without a GPU)."""
-    src = os.path.join(ROOT, "tests", "cpp", "ply_write_tool.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
-            os.path.join(HERE, "libsobfu_hip.so")]
-    if force or not os.path.exists(PLY_TOOL) or any(os.path.getmtime(PLY_TOOL) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(PLY_TOOL), exist_ok=True)
-        _compile(src, PLY_TOOL)
-    return PLY_TOOL
-
-
-VARIANT_TOOL = os.path.join(ROOT, "build", "variant_tool")
+    return _build("ply_write_tool", _test_src("ply_write_tool.cpp"), [SOBFU_HPP, SOBFU_HIP_H], True, force)
 
 
 def build_variant_tool(force: bool = False) -> str:
     """tests/cpp/variant_tool.cpp: CPU-only driver of the fused passes' instantiation choice (sobfu_amd/csrc/sobfu_variant.hpp, no HIP)."""
-    src = os.path.join(ROOT, "tests", "cpp", "variant_tool.cpp")
-    deps = [src, os.path.join(HERE, "csrc", "sobfu_variant.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h")]
-    if force or not os.path.exists(VARIANT_TOOL) or any(os.path.getmtime(VARIANT_TOOL) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(VARIANT_TOOL), exist_ok=True)
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", f"-I{os.path.join(HERE, 'csrc')}", f"-I{os.path.join(ROOT, 'include')}", src, "-o",
-                               VARIANT_TOOL])
-    return VARIANT_TOOL
+    return _build("variant_tool", _test_src("variant_tool.cpp"), [os.path.join(CSRC, "sobfu_variant.hpp"), SOBFU_HIP_H], False, force,
+                  ["-std=c++17", f"-I{CSRC}"])
 
 
-ICP_TOOL = os.path.join(ROOT, "build", "icp_shell_tool")
+def build_geometry_tool(force: bool = False, flags=()) -> str:
+    """tests/cpp/geometry_tool.cpp: CPU-only driver of the launch and tile geometry (sobfu_amd/csrc/sobfu_geometry.hpp and
+    sobfu_tile_layout.hpp, no HIP)."""
+    deps = [os.path.join(CSRC, h) for h in ("sobfu_geometry.hpp", "sobfu_tile_layout.hpp", "sobfu_variant.hpp")] + [SOBFU_HIP_H]
+    return _build("geometry_tool", _test_src("geometry_tool.cpp"), deps, False, force, ["-std=c++17", f"-I{CSRC}", *flags])
 
 
 def build_icp_tool(force: bool = False) -> str:
     """tests/cpp/icp_shell_tool.cpp: camera tracking through ProjectiveICP, Frame and the imgproc shells."""
-    src = os.path.join(ROOT, "tests", "cpp", "icp_shell_tool.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(HERE, "libsobfu_hip.so")]
-    if force or not os.path.exists(ICP_TOOL) or any(os.path.getmtime(ICP_TOOL) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(ICP_TOOL), exist_ok=True)
-        _compile(src, ICP_TOOL)
-    return ICP_TOOL
-
-
-MESH_WARP_TOOL = os.path.join(ROOT, "build", "mesh_warp_tool")
+    return _build("icp_shell_tool", _test_src("icp_shell_tool.cpp"), [SOBFU_HPP], True, force)
 
 
 def build_mesh_warp_tool(force: bool = False) -> str:
     """tests/cpp/mesh_warp_tool.cpp: the canonical mesh carried to live through SobFusion's shells (warp_mesh, fit_to_live)."""
-    src = os.path.join(ROOT, "tests", "cpp", "mesh_warp_tool.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_amd", "depth_io.hpp"),
-            os.path.join(HERE, "libsobfu_hip.so")]
-    if force or not os.path.exists(MESH_WARP_TOOL) or any(os.path.getmtime(MESH_WARP_TOOL) < os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(MESH_WARP_TOOL), exist_ok=True)
-        _compile(src, MESH_WARP_TOOL)
-    return MESH_WARP_TOOL
+    return _build("mesh_warp_tool", _test_src("mesh_warp_tool.cpp"), [SOBFU_HPP, DEPTH_IO_HPP], True, force)
 
 
 def build_host(force: bool = False) -> str:
-    build_app(force)
-    build_io_tool(force)
-    build_png_tool(force)
-    build_colour_tool(force)
-    build_ply_tool(force)
-    build_variant_tool(force)
-    build_icp_tool(force)
-    build_mesh_warp_tool(force)
-    src = os.path.join(ROOT, "tests", "cpp", "host_shell_tests.cpp")
-    deps = [src, os.path.join(ROOT, "include", "sobfu_amd", "sobfu.hpp"), os.path.join(ROOT, "include", "sobfu_hip.h"),
-            os.path.join(HERE, "libsobfu_hip.so")]
-    if not force and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
-        return OUT
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    _compile(src, OUT)
-    return OUT
+    for build in (build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
+                  build_icp_tool, build_mesh_warp_tool):
+        build(force)
+    return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, SOBFU_HIP_H], True, force)
 
 
 if __name__ == "__main__":

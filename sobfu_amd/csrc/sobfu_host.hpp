@@ -7,6 +7,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 
 #include "sobfu_hip.h"
 
@@ -45,6 +46,23 @@ inline void fill_pose(const float R[9], const float t[3], float* R_out, float* R
         if (Rt_out) Rt_out[i] = R[3 * (i % 3) + i / 3];
     }
     for (int i = 0; i < 3 && t_out; ++i) t_out[i] = t[i];
+}
+
+
+// The max-norm rows pass B folds max ||u||^2 into (bit patterns of non-negative floats): the norm a row stands for, rounded as the
+// device's gate rounds it (__fsqrt_rd)
+constexpr int kSlots = 256;
+inline float host_sqrt_rd(float s) {
+    float r = std::sqrt(s);
+    if (r > 0.f && (double) r * (double) r > (double) s) r = std::nextafterf(r, -INFINITY);
+    return r;
+}
+inline float slots_to_norm(const uint32_t* s) {
+    uint32_t m = 0;
+    for (int i = 0; i < kSlots; ++i) m = s[i] > m ? s[i] : m;
+    float f;
+    std::memcpy(&f, &m, 4);
+    return host_sqrt_rd(f);
 }
 
 }  // namespace sobfu_hip

@@ -5,17 +5,9 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "sobfu_variant.hpp"
+#include "sobfu_geometry.hpp"
 
 namespace sobfu_hip {
-// A box of cells [x0, x1) x [y0, y1) x [z0, z1) of the (local) array a fused pass produces; direct: a THIN box, evaluated one
-// lane per cell straight from the caches instead of by a z-march (the one-cell shells of a tile, halo messages).  Up to 6 boxes
-// per launch; empty boxes are skipped.
-struct LaunchBox {
-    int x0, x1, y0, y1, z0, z1;
-    bool direct;
-};
-constexpr int kMaxLaunchBoxes = 6;
 // A launch of one of the two fused passes: set the fields by name, the rest keep their defaults.  (X, Y, Z): extents of the field
 // arrays.  The gate: the launch returns at once when the max-norm row prev_slots (null: never gated) is <= max_update_norm.
 // warp: the single-GPU loop without the phi_n o psi stream (loop_warps_in_pass_a) -- pass A samples phi_n (passed as pnp) at psi
@@ -27,7 +19,7 @@ struct PassALaunch {
     float* nU        = nullptr;
     float w_reg      = 0.f;
     int X = 0, Y = 0, Z = 0;
-    LaunchBox boxes[kMaxLaunchBoxes] = {};
+    LaunchBox boxes[kMaxBoxes] = {};
     int n_boxes = 0;
     const uint32_t* prev_slots = nullptr;
     float max_update_norm      = 0.f;
@@ -47,7 +39,7 @@ struct PassBLaunch {
     int X = 0, Y = 0, Z = 0;
     int pX = 0, pY = 0, pZ = 0;  // extents of phi_n (the whole volume)
     int own[6] = {};             // the cells that enter the max-norm (x0, x1, y0, y1, z0, z1)
-    LaunchBox boxes[kMaxLaunchBoxes] = {};
+    LaunchBox boxes[kMaxBoxes] = {};
     int n_boxes = 0;
     const uint32_t* prev_slots = nullptr;
     float max_update_norm      = 0.f;
@@ -75,16 +67,6 @@ inline void set_whole_grid(PassBLaunch& l, int X, int Y, int Z) {
 }
 int launch_pass_a(const PassALaunch& l, hipStream_t stream);
 int launch_pass_b(const PassBLaunch& l, hipStream_t stream);
-// A box of a tile's pass A.  dst != null: a PUSH box -- the cells of one halo message, whose results go to
-// dst + 3 * ((x + ox) + px * ((y + oy) + py * (z + oz))): the neighbour's halo cells (peer-mapped) or a packed send buffer.
-// A MARCHING push box may be larger than its message and serve the owned block too (which then leaves those cells out): only rows
-// push_y0 <= y < push_y1 travel, and cells of planes local_z0 <= z < local_z1 are ALSO stored into this rank's own nabla_U.
-struct TileLaunchBox {
-    LaunchBox box;
-    float* dst;
-    int ox, oy, oz, px, py;
-    int push_y0, push_y1, local_z0, local_z1;
-};
 // Signalling state of the direct transport (device memory, one per tiled handle; filled by sobfu_hip_tiled_connect and read by
 // the tail of tile_potential_gradient_kernel).
 constexpr int kMaxSync = 64;

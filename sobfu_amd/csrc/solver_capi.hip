@@ -22,23 +22,10 @@
 
 namespace {
 
-constexpr int kSlots      = 256;
+using sobfu_hip::kSlots;
+using sobfu_hip::slots_to_norm;
 constexpr int kCheckEvery = 32;
 constexpr int kMaxRunAhead = 96;  // iterations the host may enqueue beyond the last max-norm row it has examined
-
-float host_sqrt_rd(float s) {  // __fsqrt_rd
-    float r = std::sqrt(s);
-    if (r > 0.f && (double) r * (double) r > (double) s) r = std::nextafterf(r, -INFINITY);
-    return r;
-}
-
-float slots_to_norm(const uint32_t* s) {
-    uint32_t m = 0;
-    for (int i = 0; i < kSlots; ++i) m = s[i] > m ? s[i] : m;
-    float f;
-    std::memcpy(&f, &m, 4);
-    return host_sqrt_rd(f);
-}
 
 }  // namespace
 

@@ -5,8 +5,6 @@
 // Part 2: fused two-pass iteration
 // ============================================================================================================
 
-constexpr int TX = 64;  // tile width in lanes: one wave per tile row (32-wide tiles measured slower: profiles/LABBOOK.md, round 5)
-
 // --- storage formats ------------------------------------------------------------------------------------------------
 // API format (COMPACT = false): the reference's layouts -- psi / nabla_U float4 (w == 0), TSDF volumes float2.
 // Compact format (COMPACT = true), private to the solver handle while it iterates: psi / nabla_U as packed 12-byte
@@ -146,23 +144,7 @@ SOBFU_DEV float gather_finish(const Gather8& g) {
 // With the XCD swizzle the linear id is first remapped so that each XCD (workgroup b runs on XCD b % 8 -- observed, used
 // for speed only) owns a contiguous run of tiles and serves neighbour-tile halos from its own L2.  PMC (256^3): fabric
 // bytes per launch drop 1.013 -> 0.821 GB for pass A and 1.406 -> 1.286 GB for pass B.
-constexpr int kMaxBoxes = 6;
-struct Box {
-    int x0, x1, y0, y1, z0, z1;  // cells [x0, x1) x [y0, y1) x [z0, z1)
-    int zc;                      // marching: planes per march (z-chunk); direct: wx, the lanes of a wave that run along x
-    int kind;                    // 0 marching, 1 direct
-    int wpg;                     // direct: waves of a workgroup that take cells (the others leave at once) -- see direct_wpg()
-    int rem;                     // marching: the first `rem` z-chunks march zc + 1 planes (an even split of the planes over a chosen NUMBER of chunks)
-    int pair;                    // marching, pass B: z-chunks march in alternating directions (even chunks top-down, odd ones bottom-up), so that
-                                 // two neighbours start at -- or arrive at -- their common boundary TOGETHER: the 6 planes either side of it,
-                                 // which both read, are fetched once where the two share an XCD (and its L2) instead of a march apart
-};
-struct BoxList {
-    int n;
-    int m0, m1;   // workgroups [m0, m1) belong to marching boxes, the rest to direct boxes
-    Box b[kMaxBoxes];
-    int first[kMaxBoxes + 1];  // first workgroup of box i; first[n] = workgroups in the launch
-};
+// (Box, BoxList and the host code that fills them: sobfu_geometry.hpp)
 struct TileGeom {
     int u0, v0, zb, ze;  // tile origin along x / y, planes [zb, ze) of this march
     int u_hi, v_hi;      // cells with x >= u_hi or y >= v_hi are outside the box (computed, not stored)

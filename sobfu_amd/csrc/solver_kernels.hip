@@ -11,8 +11,6 @@
 //           456 B/voxel.
 //
 // Arithmetic is op-for-op the reference's (see sobfu_device.hpp): results are bit-identical to the launcher-for-launcher kernels.
-#include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "sobfu_device.hpp"
@@ -41,155 +39,7 @@ constexpr int kMaxMsgs = 18;  // 6 face + 12 edge neighbours of a 3-D tile
 
 }  // namespace
 
-// Tile configuration of the fused passes (see DESIGN.md "Kernel tuning").
-// tile of a workgroup: 64 lanes x 8 waves, one row per wave (rows-per-thread 2 / 4 and 4 / 16 waves were measured in rounds 1 - 2:
-// profiles/LABBOOK.md; the kernels keep RPT / WY as template parameters, the launchers instantiate this one shape)
-constexpr int kRPT = 1, kWY = 8;
-static_assert(sobfu_hip::kMaxLaunchBoxes == kMaxBoxes, "a launch descriptor holds the boxes of one launch");
-
 namespace sobfu_hip {
-
-// z-chunk length of a fused pass.  A launch has tiles * ceil(nz / zc) workgroups; `capacity` of them are resident at
-// once on the chip (256 CUs x workgroups per CU allowed by VGPRs / LDS / waves).  Cost model: time ~ (1 + refill / zc)
-// / utilisation, where utilisation = groups / (ceil(groups / capacity) * capacity) penalises a ragged last wave of
-// workgroups (measured at 256^3, pass B: 768 groups = exactly 3 per CU: 166 us; 512 groups: 184 us; 1024: 195 us) and
-// refill = planes re-read when a march starts (2 for pass A, 6 for pass B).  Small grids end up with many short
-// marches, which is what the latency-bound regime wants (64^3: zc = 2 is 1.4x faster than zc = 8).
-static int env_zc(const char* env) {  // tuning override (SOBFU_ZC_A / SOBFU_ZC_B): planes per march, 0 = none
-    const char* e = getenv(env);
-    const int v   = e ? atoi(e) : 0;
-    return v > 0 ? v : 0;
-}
-int pick_zc(int X, int Y, int nz, int ty, int capacity, int refill, const char* env) {
-    if (const int v = env_zc(env)) return v < nz ? v : nz;
-    const long tiles = (long) ((X + TX - 1) / TX) * ((Y + ty - 1) / ty);
-    int best_zc = nz;
-    double best = 1e30;
-    for (int c = 1; c <= nz; ++c) {
-        const int zc = (nz + c - 1) / c;
-        if (zc < 2 && nz >= 2) break;
-        const long groups = tiles * ((nz + zc - 1) / zc);
-        const long waves  = (groups + capacity - 1) / capacity;
-        const double util = (double) groups / (double) (waves * capacity);
-        const double cost = (1.0 + (double) refill / zc) / util;
-        if (cost < best - 1e-9) { best = cost; best_zc = zc; }
-    }
-    return best_zc;
-}
-
-// direct boxes: lanes of a wave that run along x, and the workgroups (of WY waves) the box needs
-static int direct_wx(int ex) {
-    int wx = 1;
-    while (wx < ex && wx < 64) wx *= 2;
-    return wx;
-}
-// A wave of a box that is thin in x touches up to 64 / wx cache lines with EVERY load (its lanes sit in different rows), and the
-// address unit of a CU takes them one line per cycle: eight such waves in one workgroup -- on one CU -- queue up behind each
-// other (the one-column x shell of a 2 x 2 x 2 tile: 13.9 us as 32 full workgroups).  Such boxes get few working waves per
-// workgroup, i.e. many small workgroups that the dispatcher spreads over all CUs.
-// Only where the launch leaves the chip room (pass B of a tile: fewer workgroups than slots) -- in pass A, whose march fills every
-// slot, a thousand one-wave workgroups in front of it cost more than they save (`spread` = false: full workgroups).
-static int direct_wpg(int wx, bool spread) { return spread ? std::max(1, std::min(kWY, wx / 4)) : kWY; }
-static int direct_groups(const LaunchBox& s, int wx, bool spread) {
-    const int wyl = 64 / wx, wpg = direct_wpg(wx, spread);
-    const long waves = (long) ((s.x1 - s.x0 + wx - 1) / wx) * ((s.y1 - s.y0 + wyl - 1) / wyl) * (s.z1 - s.z0);
-    return (int) ((waves + wpg - 1) / wpg);
-}
-static double box_cells(const LaunchBox& s) {
-    return (s.x1 > s.x0 && s.y1 > s.y0 && s.z1 > s.z0) ? (double) (s.x1 - s.x0) * (s.y1 - s.y0) * (s.z1 - s.z0) : 0.0;
-}
-// geometry of one live box; returns its workgroups.  Marching boxes: zc_override > 0 fixes the planes per march; else, when the box's
-// xy tiles fit the share of the chip it gets (`even`: launches that are one resident round -- multi-GPU tiles, cache-resident grids),
-// the planes are split EVENLY over as many chunks as fill that share (chunk lengths differ by at most one plane: a launch of one
-// round lasts as long as its longest march); else the cost model picks a chunk length (pick_zc).
-static int finish_box(Box& b, const LaunchBox& s, int ty, int share, int refill, int zc_override, const char* env, bool spread, bool even = false) {
-    b.x0 = s.x0; b.x1 = s.x1; b.y0 = s.y0; b.y1 = s.y1; b.z0 = s.z0; b.z1 = s.z1;
-    b.kind = s.direct ? 1 : 0;
-    b.wpg = kWY;
-    b.rem = 0;
-    b.pair = 0;
-    if (s.direct) {
-        b.zc  = direct_wx(s.x1 - s.x0);
-        b.wpg = direct_wpg(b.zc, spread);
-        return direct_groups(s, b.zc, spread);
-    }
-    const int eu = s.x1 - s.x0, ev = s.y1 - s.y0, nz = s.z1 - s.z0;
-    const int tiles = ((eu + TX - 1) / TX) * ((ev + ty - 1) / ty);
-    int nch = 0;
-    if (zc_override <= 0 && env_zc(env) == 0 && even && tiles <= share) nch = std::max(share / tiles, 1);
-    if (nch > 0 && zc_override <= 0) {
-        nch   = std::min(nch, std::max(nz / 2, 1));  // a march of one plane is all prologue
-        b.zc  = nz / nch;
-        b.rem = nz % nch;
-        return tiles * nch;
-    }
-    b.zc = zc_override > 0 ? std::min(zc_override, nz) : pick_zc(eu, ev, nz, ty, share, refill, env);
-    return tiles * ((nz + b.zc - 1) / b.zc);
-}
-// Fills the launch geometry of a box list: z-chunk per marching box (cost model above, the chip's capacity shared between the
-// marching boxes; direct boxes are one short round trip and take no share) and the workgroup prefix -- marching boxes first.
-// Returns the workgroups.
-static int finish_boxes(BoxList& L, const LaunchBox* boxes, int n, int ty, int capacity, int refill, const char* env, bool even = false) {
-    L.n = 0;
-    int live = 0;
-    bool thin = false;
-    for (int i = 0; i < n; ++i) {
-        live += (box_cells(boxes[i]) > 0 && !boxes[i].direct) ? 1 : 0;
-        thin = thin || (box_cells(boxes[i]) > 0 && boxes[i].direct);
-    }
-    // an even split fills the marching share exactly -- then the thin boxes' workgroups would start only when a march ends, and end the
-    // launch: they keep a sixteenth of the slots (2 x 2 x 2 tile of 256^3: 15 chunks -> 480 + 288 workgroups, 43.0 us; 16 -> 512 + 288, 44.1)
-    if (even && thin) capacity -= capacity / 16;
-    int total = 0;
-    L.m0 = L.m1 = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        const bool direct_pass = pass == 1;  // marching boxes first
-        if (!direct_pass) L.m0 = total;
-        for (int i = 0; i < n && L.n < kMaxBoxes; ++i) {
-            if (box_cells(boxes[i]) == 0 || boxes[i].direct != direct_pass) continue;
-            // the chip's workgroup slots are shared equally between the marching boxes (the two plane ranges of an overlapped slab
-            // schedule): a thin range is latency-critical, so it gets as many short marches as the big one gets long ones
-            L.first[L.n] = total;
-            total += finish_box(L.b[L.n], boxes[i], ty, std::max(capacity / std::max(live, 1), 1), refill, 0, env, true, even);
-            ++L.n;
-        }
-        if (!direct_pass) L.m1 = total;
-    }
-    for (int k = L.n; k <= kMaxBoxes; ++k) L.first[k] = total;
-    return total;
-}
-
-// Pass A of a multi-GPU tile (see tile_potential_gradient_kernel): the launch geometry of its box list.  The boxes with a
-// destination (push boxes: direct, their result goes to `dst` only) are numbered first, then the others; returns the workgroups
-// (< 0: too many boxes).  resident: the tile's state stays in the Infinity Cache (GridTraits)
-static int fill_tile_boxes(TileBoxList& L, const TileLaunchBox* boxes, int n, bool resident) {
-    constexpr int TY = kRPT * kWY;
-    L.n = 0;
-    int live = 0, total = 0;
-    for (int i = 0; i < n; ++i) live += (box_cells(boxes[i].box) > 0 && !boxes[i].box.direct && boxes[i].dst == nullptr) ? 1 : 0;
-    for (int pass = 0; pass < 2; ++pass) {  // push boxes first
-        for (int i = 0; i < n; ++i) {
-            const TileLaunchBox& s = boxes[i];
-            if ((s.dst != nullptr) != (pass == 0) || box_cells(s.box) == 0) continue;
-            if (L.n >= kMaxTileBoxes) return -1;
-            TileBox& t = L.b[L.n];
-            L.first[L.n] = total;
-            // z-chunks: a marching push box (a face with wide rows) marches up to 8 planes; the owned block of a cache-resident
-            // tile is sized for TWO workgroups per CU -- the push boxes take slots too, and at that size 8-plane marches beat the 4-plane ones that
-            // filling all four slots per CU would give (2 x 2 x 2 tile of 256^3: pass A 19.8 -> 19.1 us, 1 x 2 x 4: 18.9 -> 17.2)
-            const int zc_box = (s.dst != nullptr && !s.box.direct) ? std::min(8, s.box.z1 - s.box.z0) : 0;
-            total += finish_box(t.b, s.box, TY, std::max(256 * (resident ? 2 : 4) * 8 / kWY / std::max(live, 1), 1), 2, zc_box,
-                                "SOBFU_ZC_A", false);
-            t.push.base = s.dst;
-            t.push.ox = s.ox; t.push.oy = s.oy; t.push.oz = s.oz; t.push.px = s.px; t.push.py = s.py;
-            t.push.y0 = s.push_y0; t.push.y1 = s.push_y1; t.push.lz0 = s.local_z0; t.push.lz1 = s.local_z1;
-            ++L.n;
-        }
-        if (pass == 0) L.n_push_wgs = total;
-    }
-    for (int k = L.n; k <= kMaxTileBoxes; ++k) L.first[k] = total;
-    return total;
-}
 
 // Calls launch(std::integral_constant<size_t, I>{}) for the row I of `table` that equals `v`, which instantiates the kernel of that
 // row: only the table's rows are ever instantiated.  false: `v` is no row of the table.
@@ -217,18 +67,14 @@ static int launch_tile_boxes(const TilePassAArgsP& a, int groups, const PassAVar
 }
 
 int launch_pass_a(const PassALaunch& L, hipStream_t stream) {
-    constexpr int TY = kRPT * kWY;
-    if (L.n_boxes > kMaxLaunchBoxes) return SOBFU_E_BADARG;
-    bool direct = false;
-    for (int i = 0; i < L.n_boxes; ++i) direct = direct || (L.boxes[i].direct && box_cells(L.boxes[i]) > 0);
+    if (L.n_boxes > kMaxBoxes) return SOBFU_E_BADARG;
+    const bool direct = has_direct_box(L.boxes, L.n_boxes);
     const GridTraits g = grid_traits(L.X, L.Y, L.Z, L.X, L.Y, L.Z, env_cache_cells());
     PassAVariant v;
     SOBFU_TRY(choose_pass_a(g, L.compact, L.warp, direct, &v));
     if (direct) {  // thin boxes: the tile kernel (no messages, no signalling, no gate) with a list of this call's own
-        TileLaunchBox tb[kMaxLaunchBoxes];
-        for (int i = 0; i < L.n_boxes; ++i) tb[i] = TileLaunchBox{L.boxes[i], nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         TileBoxList B{};
-        const int total = fill_tile_boxes(B, tb, L.n_boxes, g.resident);
+        const int total = plan_pass_a_thin(B, L.boxes, L.n_boxes, g.resident);
         if (total <= 0) return total < 0 ? SOBFU_E_BADARG : 0;
         // a stream-ordered device copy, freed behind the launch (hipMemcpyAsync from pageable memory has read B when it returns)
         TileBoxList* d = nullptr;
@@ -240,8 +86,7 @@ int launch_pass_a(const PassALaunch& L, hipStream_t stream) {
         return rc != 0 ? rc : (int) f;
     }
     PassAArgs a{{L.pnp, L.pg, L.psi, L.nU, {L.X, L.Y, L.Z}, L.w_reg, L.prev_slots, L.max_update_norm}, {}};
-    // <= 64 VGPR (the warping march included), 22 KB LDS: 4 workgroups of 8 waves per CU
-    const int groups = finish_boxes(a.boxes, L.boxes, L.n_boxes, TY, 256 * 4 * 8 / kWY, 2, "SOBFU_ZC_A");
+    const int groups = plan_pass_a(a.boxes, L.boxes, L.n_boxes);
     if (groups == 0) return 0;
     const dim3 grid((unsigned) groups), block(TX, kWY);
     const bool found = launch_row(kPassATable, v, [&](auto i) {
@@ -302,8 +147,7 @@ int launch_tile_flush(TileSync* sync, uint32_t seq, int wait, const uint32_t* ro
 }
 
 int launch_pass_b(const PassBLaunch& L, hipStream_t stream) {
-    constexpr int TY = kRPT * kWY;
-    if (L.n_boxes > kMaxLaunchBoxes) return SOBFU_E_BADARG;
+    if (L.n_boxes > kMaxBoxes) return SOBFU_E_BADARG;
     PassBArgs a{L.nU, L.psi, L.phi_n, L.pnp, (float4*) L.updates, L.slots, {L.X, L.Y, L.Z}, {}, L.alpha, {}, L.prev_slots, L.max_update_norm,
                 {L.pX, L.pY, L.pZ}, {L.own[0], L.own[1], L.own[2], L.own[3], L.own[4], L.own[5]}, L.prev_rows, L.psi_out ? L.psi_out : L.psi,
                 L.sys_acquire ? 1 : 0};
@@ -312,18 +156,8 @@ int launch_pass_b(const PassBLaunch& L, hipStream_t stream) {
     const PassBAsk ask{L.compact, L.updates != nullptr, L.sys_acquire, !L.warp};
     PassBMarch m;
     SOBFU_TRY(pass_b_march(g, ask, &m));
-    // workgroups a CU holds: <= 80 VGPR (launch bounds) and 32 - 48 KB LDS: 3 of 8 waves; the pipelined march (<= 128 VGPR): 2
-    // cache-resident launches are ONE resident round of workgroups, which lasts as long as its longest march: the planes are
-    // split evenly over as many z-chunks as fill the marching workgroups' share of the chip
-    const int groups = finish_boxes(a.boxes, L.boxes, L.n_boxes, TY, 256 * (m.pipe ? 2 : 3) * 8 / kWY, 6, "SOBFU_ZC_B", g.resident && m.pipe);
+    const int groups = plan_pass_b(a.boxes, L.boxes, L.n_boxes, g, m);
     if (groups == 0) return 0;  // an empty launch is no launch, whatever stage 2 would say of it
-    int zc_max = 0;
-    for (int i = 0; i < a.boxes.n; ++i) {
-        m.direct = m.direct || a.boxes.b[i].kind != 0;
-        if (a.boxes.b[i].kind == 0) zc_max = std::max(zc_max, a.boxes.b[i].zc + (a.boxes.b[i].rem > 0 ? 1 : 0));  // the first `rem` chunks march one plane more
-        if (a.boxes.b[i].kind == 0 && m.pipe && g.resident && SOBFU_PAIR_B) a.boxes.b[i].pair = 1;  // neighbouring z-chunks march towards / away from each other
-    }
-    m.long_marches = SOBFU_HLEAD > 0 && zc_max >= SOBFU_HLEAD_MIN_ZC;
     PassBVariant v;
     SOBFU_TRY(choose_pass_b(g, ask, m, &v));
     const dim3 grid((unsigned) groups), block(TX, kWY);

@@ -104,12 +104,6 @@ SOBFU_DEV float4 pass_a_direct_cell(const PassACore& a, int x, int y, int z) {
 }
 
 // the MARCHING path of pass A for the tile tg (a z-chunk of a 64 x TY tile)
-// where the cells of a PUSH box go (pass A of a multi-GPU tile: see tile_potential_gradient_kernel)
-struct PushDst {
-    float* base;             // null: the box is stored locally
-    int ox, oy, oz, px, py;  // cell (x, y, z) -> base + 3 * ((x + ox) + px * ((y + oy) + py * (z + oz)))
-    int y0, y1, lz0, lz1;    // marching push boxes: rows [y0, y1) travel; planes [lz0, lz1) are stored locally as well
-};
 SOBFU_DEV void st3_system(float* p, const float4& v);
 
 // NTL: streaming (nontemporal) hints, kNT or 0 -- for grids whose state exceeds the 256 MiB Infinity Cache; 0 for cache-resident
@@ -348,16 +342,7 @@ __global__ void __launch_bounds__(TX* WY, WARP ? 8 : 1) fused_potential_gradient
 // and pass B -- a separate launch, whose start invalidates the caches -- reads it.  nabla_U is
 // double-buffered by iteration parity, which orders a neighbour's stores of iteration k+1 behind this rank's reads of
 // iteration k without a second handshake (see tiled_capi.hip).
-constexpr int kMaxTileBoxes = 20;  // 18 messages + the owned block + one spare
-struct TileBox {
-    Box b;
-    PushDst push;
-};
-struct TileBoxList {
-    int n, n_push_wgs;  // workgroups [0, n_push_wgs) belong to push boxes
-    TileBox b[kMaxTileBoxes];
-    int first[kMaxTileBoxes + 1];
-};
+// (PushDst, TileBox, TileBoxList and the host code that fills them: sobfu_geometry.hpp)
 // ---- stores that leave the GPU ----------------------------------------------------------------------------------------------
 // What travels to a peer (message cells, row maxima, flags) is stored WRITE-THROUGH at system scope (sc0 sc1): it never sits
 // dirty in this GPU's write-back L2, so "everything I sent has arrived" is `s_waitcnt vmcnt(0)` -- the stores' acknowledgements --

@@ -24,15 +24,6 @@ struct PassBArgs {
     int sys_acquire;  // direct transport: halo cells and max-norm entries of this launch's inputs were stored by OTHER GPUs (see the kernel's entry)
 };
 
-#ifndef SOBFU_PAIR_B
-#define SOBFU_PAIR_B 1  // cache-resident launches of the pipelined pass B: z-chunks march in alternating directions (Box::pair)
-#endif
-#ifndef SOBFU_HLEAD
-#define SOBFU_HLEAD 3  // planes the halo requests of pass B run ahead on long marches (0: never; one plane ahead, straight from registers)
-#endif
-#ifndef SOBFU_HLEAD_MIN_ZC
-#define SOBFU_HLEAD_MIN_ZC 24  // shortest march (planes) that uses the halo lead
-#endif
 typedef float v2f __attribute__((ext_vector_type(2)));
 #ifndef SOBFU_MINW_B
 #define SOBFU_MINW_B 6  // waves/SIMD the register allocator must leave room for: <= 80 VGPR -> 3 workgroups of 8 waves per CU

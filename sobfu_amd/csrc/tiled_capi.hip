@@ -50,7 +50,7 @@
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
 #include "sobfu_launch.hpp"
-
+#include "sobfu_tile_layout.hpp"
 
 // The handful of RCCL (= NCCL API) types this file needs, declared here so that neither building nor loading the library
 // depends on an RCCL installation (values as in rccl.h; the entry points are resolved with dlsym at run time).
@@ -79,7 +79,9 @@ struct Rccl {
     bool ok() const { return handle != nullptr; }
 } g_rccl;
 
-constexpr int kHalo = 4, kSlots = 256;
+using sobfu_hip::kHalo;
+using sobfu_hip::kSlots;
+using sobfu_hip::TileLay;
 // iterations one solve may run on a handle whose max-norm rows other processes map (direct transport): the rows are part of the arena
 // the peers open once, so their number is fixed at creation (16 MiB)
 constexpr int kRowsIters = 16384;
@@ -160,85 +162,11 @@ void pool_give_back(void* p) {
         }                                                                                       \
     } while (0)
 
-float host_sqrt_rd(float s) {
-    float r = std::sqrt(s);
-    if (r > 0.f && (double) r * (double) r > (double) s) r = std::nextafterf(r, -INFINITY);
-    return r;
-}
-
-// The layout of ANY rank's tile (a rank also needs its neighbours': where their halo cells sit in their arrays).
-struct AxisLay {
-    int g0, g1, lo, hi, L, o0, o1, base;
-};
-struct MsgGeom {
-    int peer, dir[3];
-    int sb[6], rb[6];  // cells sent / halo cells received (local cells of THIS rank)
-    size_t cells;
-};
-struct TileLay {
-    int P[3], c[3];
-    AxisLay a[3];
-    std::vector<MsgGeom> msgs;
-    bool ok = true;
-};
-TileLay make_layout(const int dims[3], const int P[3], int rank) {
-    TileLay t;
-    const int c[3] = {rank % P[0], (rank / P[0]) % P[1], rank / (P[0] * P[1])};  // x fastest
-    for (int k = 0; k < 3; ++k) {
-        t.P[k] = P[k];
-        t.c[k] = c[k];
-        const int base = dims[k] / P[k], rem = dims[k] % P[k];  // the cells of an axis are split as evenly as possible
-        AxisLay& a = t.a[k];
-        a.g0   = c[k] * base + std::min(c[k], rem);
-        a.g1   = a.g0 + base + (c[k] < rem ? 1 : 0);
-        a.lo   = c[k] > 0 ? kHalo : 0;
-        a.hi   = c[k] < P[k] - 1 ? kHalo : 0;
-        a.L    = (a.g1 - a.g0) + a.lo + a.hi;
-        a.o0   = a.lo;
-        a.o1   = a.lo + (a.g1 - a.g0);
-        a.base = a.g0 - a.lo;
-        if (P[k] > 1 && base < kHalo) t.ok = false;  // a tile must own at least a halo's worth of cells per split axis
-    }
-    // halo messages: every face neighbour (one non-zero offset) and edge neighbour (two); corners are never read.  Along an
-    // axis with offset +1 the 4 owned cells next to that face are sent and the 4 halo cells beyond it received; along an
-    // axis with offset 0 the owned range (the same on both sides, as the neighbour shares this coordinate).
-    for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int dl[3] = {dx, dy, dz};
-                const int nnz = (dx != 0) + (dy != 0) + (dz != 0);
-                if (nnz < 1 || nnz > 2) continue;
-                bool inside = true;
-                for (int k = 0; k < 3; ++k) inside = inside && c[k] + dl[k] >= 0 && c[k] + dl[k] < P[k];
-                if (!inside) continue;
-                MsgGeom m;
-                m.cells = 1;
-                for (int k = 0; k < 3; ++k) {
-                    const AxisLay& a = t.a[k];
-                    m.dir[k] = dl[k];
-                    if (dl[k] > 0) { m.sb[2 * k] = a.o1 - kHalo; m.sb[2 * k + 1] = a.o1; m.rb[2 * k] = a.o1; m.rb[2 * k + 1] = a.o1 + kHalo; }
-                    else if (dl[k] < 0) { m.sb[2 * k] = a.o0; m.sb[2 * k + 1] = a.o0 + kHalo; m.rb[2 * k] = a.o0 - kHalo; m.rb[2 * k + 1] = a.o0; }
-                    else { m.sb[2 * k] = m.rb[2 * k] = a.o0; m.sb[2 * k + 1] = m.rb[2 * k + 1] = a.o1; }
-                    m.cells *= (size_t) (m.sb[2 * k + 1] - m.sb[2 * k]);
-                }
-                m.peer = (c[0] + dx) + P[0] * ((c[1] + dy) + P[1] * (c[2] + dz));
-                t.msgs.push_back(m);
-            }
-    // the z FACES go last: on the packed (RCCL / callback) transports of a 3-D tile they travel IN PLACE as whole padded planes of the
-    // array (see exchange_packed), so the messages that do use the packed buffers are a prefix of the list and of the buffers
-    std::stable_partition(t.msgs.begin(), t.msgs.end(), [](const MsgGeom& m) { return !(m.dir[0] == 0 && m.dir[1] == 0 && m.dir[2] != 0); });
-    return t;
-}
-
 }  // namespace
 
 struct sobfu_hip_tiled {
     int X, Y, Z, world, rank;
-    // tile grid P, this rank's tile coordinates c; per axis: owned global range [g0, g1), halo cells lo / hi, local extent L,
-    // owned local range [o0, o1), global coordinate `base` of local cell 0
-    int P[3], c[3], g0[3], g1[3], lo[3], hi[3], L[3], o0[3], o1[3], base[3];
-    bool slab;  // Px == Py == 1: on the RCCL transport halos are whole planes and travel in place (no pack / unpack)
-    int z0, z1, Lz, own_lo, own_hi, zbase;  // the z entries again, under the names the slab schedules use
+    TileLay lay;  // this rank's tile: owned cells, halo cells, local extents, the halo messages' cells (sobfu_tile_layout.hpp)
     sobfu_hip_solver_params p;
     float taps[7];
     ncclComm_t comm = nullptr;
@@ -257,15 +185,9 @@ struct sobfu_hip_tiled {
     uint32_t* slots = nullptr;
     int slots_iters = 0;
     size_t NL, NF;
-    // halo messages: one per face / edge neighbour, packed one after the other (same offsets on both sides)
-    std::vector<sobfu_hip_tiled_msg> msgs;
-    std::vector<MsgGeom> geom;
-    std::vector<int> sboxes, rboxes;  // 6 ints per message: the cells sent / the halo cells received
+    // the messages of one exchange: offsets into the packed buffers, the in-place z faces of a 3-D tile, n_packed
+    sobfu_hip::TileMsgs mx;
     float *sendbuf = nullptr, *recvbuf = nullptr;
-    // packed transports of a 3-D tile: the first n_packed messages travel through the buffers, the z faces behind them in place
-    // (zmsgs: offsets into the nabla_U array itself -- 4 whole padded planes out of the owned rim, 4 into the halo)
-    int n_packed = 0;
-    std::vector<sobfu_hip_tiled_msg> zmsgs;
     uint32_t* scatter_table = nullptr;  // device: destination cell of every cell of the packed receive buffer (the loop's scatter, precomputed)
     unsigned scatter_cells = 0;
     // direct transport (sobfu_hip_tiled_connect): push destinations in the peers, signalling state
@@ -312,70 +234,23 @@ double deadline_seconds() {
 // (re)builds pass A's box lists and their launch plans: one push box per message, then the owned block.  Destinations: the peers'
 // halo cells when connected (dst[half][i] != null), else the packed send buffer.  On failure the handle keeps the plans it had.
 int build_a_boxes(sobfu_hip_tiled* t, float* const* dst0, float* const* dst1, const TileLay* peers) {
-    // The y and z FACES are pushed by short marches whose cells the owned block would compute a second time.  Instead such a box
-    // stands in for the owned block on its cells (it stores them at home too) and the owned block shrinks: by the 4 rim planes
-    // along z, by a whole 8-row tile along y (the face box then marches 8 rows, of which the 4 rim rows travel).  Where face
-    // boxes meet, the z box is the one that stores at home.  The x face (4 cells of a 64-lane row: lane per cell) and the edge
-    // strips stay push-only: shrinking the owned block by 4 columns would not save it a single workgroup.  Measured (one box, A/B):
-    // 1 x 1 x 8 slabs of 256^3 43.1 -> 41.6 us per iteration; 2 x 2 x 2 and 1 x 2 x 4 tiles unchanged (43.4 / 44.7).
-    const int ny_nb = (t->lo[1] ? 1 : 0) + (t->hi[1] ? 1 : 0), nz_nb = (t->lo[2] ? 1 : 0) + (t->hi[2] ? 1 : 0);
-    const bool wide = (t->o1[0] - t->o0[0]) >= 64;  // rows wide enough for the faces to be MARCHED (thin rows: lane per cell, push-only)
-    // packed (RCCL / callback) transports of a 3-D tile: the z faces leave IN PLACE, straight out of the owned block's rim planes -- no
-    // push box evaluates them and the owned block keeps those planes
-    const bool z_inplace = dst0 == nullptr && dst1 == nullptr && !t->slab && !t->zmsgs.empty();
-    const bool z_home = !z_inplace && wide && nz_nb > 0 && (t->o1[2] - t->o0[2]) > kHalo * nz_nb;
-    const bool y_home = wide && ny_nb > 0 && (t->o1[1] - t->o0[1]) > 8 * ny_nb;
-    const int iz0 = t->o0[2] + ((z_home && t->lo[2]) ? kHalo : 0), iz1 = t->o1[2] - ((z_home && t->hi[2]) ? kHalo : 0);  // planes the z boxes leave
-    const int iy0 = t->o0[1] + ((y_home && t->lo[1]) ? 8 : 0), iy1 = t->o1[1] - ((y_home && t->hi[1]) ? 8 : 0);
+    const sobfu_hip::PushBoxes pb = sobfu_hip::push_boxes(t->lay, t->mx, t->sendbuf, dst0, dst1, peers, t->debug_skip);
     sobfu_hip::TilePassAPlan *all[2] = {nullptr, nullptr}, *push[2] = {nullptr, nullptr}, *own_only = nullptr;
     int rc = 0;
     auto plan = [&](sobfu_hip::TilePassAPlan** out, const std::vector<sobfu_hip::TileLaunchBox>& v) {
-        if (rc == 0) rc = sobfu_hip::tile_pass_a_plan_create(out, v.data(), (int) v.size(), t->L[0], t->L[1], t->L[2]);
+        if (rc == 0) rc = sobfu_hip::tile_pass_a_plan_create(out, v.data(), (int) v.size(), t->lay.a[0].L, t->lay.a[1].L, t->lay.a[2].L);
     };
     for (int h = 0; h < 2; ++h) {
-        std::vector<sobfu_hip::TileLaunchBox> v;
-        for (size_t i = 0; i < t->geom.size(); ++i) {
-            const MsgGeom& m = t->geom[i];
-            sobfu_hip::TileLaunchBox b{};
-            // wide rows (y / z faces): a short march costs a fifth of the loads of a lane-per-cell evaluation (1 x 1 x 8 slabs: pass A
-            // 26.6 -> 18.4 us); thin in x: direct
-            const bool march = (m.sb[1] - m.sb[0]) >= 64;
-            b.box = sobfu_hip::LaunchBox{m.sb[0], m.sb[1], m.sb[2], m.sb[3], m.sb[4], m.sb[5], !march};
-            b.push_y0 = m.sb[2]; b.push_y1 = m.sb[3];
-            const bool face_z = march && m.dir[0] == 0 && m.dir[1] == 0 && m.dir[2] != 0, face_y = march && m.dir[0] == 0 && m.dir[2] == 0 && m.dir[1] != 0;
-            if (face_z && z_home) { b.local_z0 = m.sb[4]; b.local_z1 = m.sb[5]; }
-            if (face_y && y_home) {
-                if (m.dir[1] > 0) b.box.y0 = t->o1[1] - 8; else b.box.y1 = t->o0[1] + 8;
-                b.local_z0 = iz0; b.local_z1 = iz1;
-            }
-            if (z_inplace && m.dir[0] == 0 && m.dir[1] == 0 && m.dir[2] != 0) continue;
-            if ((!march && (t->debug_skip & 128)) || (march && (t->debug_skip & 256))) continue;  // timing experiments: without the thin / the marched push boxes
-            if (march && (t->debug_skip & 512)) b.push_y1 = b.push_y0;  // timing experiments: the marched boxes keep their cells at home only
-            float* const* dst = h ? dst1 : dst0;
-            if (dst && dst[i]) {  // the matching message of the peer: direction -dir; its receive box is where these cells live there
-                const TileLay& pl = peers[i];
-                const MsgGeom* pm = nullptr;
-                for (const MsgGeom& g : pl.msgs)
-                    if (g.dir[0] == -m.dir[0] && g.dir[1] == -m.dir[1] && g.dir[2] == -m.dir[2]) pm = &g;
-                b.dst = dst[i];
-                b.ox = pm->rb[0] - m.sb[0]; b.oy = pm->rb[2] - m.sb[2]; b.oz = pm->rb[4] - m.sb[4];
-                b.px = pl.a[0].L; b.py = pl.a[1].L;
-            } else {
-                b.dst = t->sendbuf + t->msgs[i].send_off;
-                b.ox = -m.sb[0]; b.oy = -m.sb[2]; b.oz = -m.sb[4];
-                b.px = m.sb[1] - m.sb[0]; b.py = m.sb[3] - m.sb[2];
-            }
-            v.push_back(b);
-        }
+        std::vector<sobfu_hip::TileLaunchBox> v = pb.push[h];
         plan(&push[h], v);
         sobfu_hip::TileLaunchBox own{};
-        own.box = sobfu_hip::LaunchBox{t->o0[0], t->o1[0], iy0, iy1, iz0, iz1, false};
+        own.box = pb.own;
         v.push_back(own);
         plan(&all[h], v);
     }
     // the same launch without messages (a world of one; timing experiments): the whole owned block
     sobfu_hip::TileLaunchBox whole{};
-    whole.box = sobfu_hip::LaunchBox{t->o0[0], t->o1[0], t->o0[1], t->o1[1], t->o0[2], t->o1[2], false};
+    whole.box = pb.whole;
     plan(&own_only, {whole});
     if (rc == 0) {
         std::swap(all, t->a_plan);
@@ -474,14 +349,8 @@ int sobfu_hip_tiled_create3(sobfu_hip_tiled** out, int X, int Y, int Z, int Px, 
     auto* t = new sobfu_hip_tiled();
     t->X = X; t->Y = Y; t->Z = Z; t->world = Px * Py * Pz; t->rank = rank;
     const int dims[3] = {X, Y, Z}, P[3] = {Px, Py, Pz};
-    const TileLay lay = make_layout(dims, P, rank);
-    int rc = lay.ok ? 0 : SOBFU_E_UNSUPPORTED;
-    for (int a = 0; a < 3; ++a) {
-        t->P[a] = P[a]; t->c[a] = lay.c[a];
-        t->g0[a] = lay.a[a].g0; t->g1[a] = lay.a[a].g1; t->lo[a] = lay.a[a].lo; t->hi[a] = lay.a[a].hi; t->L[a] = lay.a[a].L;
-        t->o0[a] = lay.a[a].o0; t->o1[a] = lay.a[a].o1; t->base[a] = lay.a[a].base;
-    }
-    t->slab = Px == 1 && Py == 1;
+    t->lay = sobfu_hip::make_layout(dims, P, rank);
+    int rc = t->lay.ok ? 0 : SOBFU_E_UNSUPPORTED;
     // bring-up / timing settings of this handle, read once ("environment")
     const char* dp = std::getenv("SOBFU_TILED_DRY_PACKED");
     t->dry_packed = dp && dp[0] == '1';
@@ -489,46 +358,21 @@ int sobfu_hip_tiled_create3(sobfu_hip_tiled** out, int X, int Y, int Z, int Px, 
     t->force_comm = fc && fc[0] == '1';
     const char* ds = std::getenv("SOBFU_TILED_DEBUG_SKIP");
     t->debug_skip = ds ? std::atoi(ds) : 0;
-    t->z0 = t->g0[2]; t->z1 = t->g1[2]; t->Lz = t->L[2]; t->own_lo = t->o0[2]; t->own_hi = t->o1[2]; t->zbase = t->base[2];
-    t->NL = (size_t) t->L[0] * t->L[1] * t->L[2];
+    t->NL = t->lay.cells();
     t->NF = (size_t) X * Y * Z;
     t->p  = *params;
     float h[16];
     if (rc == 0) rc = sobfu_hip_sobolev_filter(params->s, params->lambda, h);
     for (int i = 0; i < 7; ++i) t->taps[i] = h[i];
     if (rc == 0) {
-        size_t off = 0;
-        t->geom = lay.msgs;
-        for (const MsgGeom& g : lay.msgs) {
-            sobfu_hip_tiled_msg m;
-            m.peer     = g.peer;
-            m.send_off = m.recv_off = off;
-            m.count    = g.cells * 3;
-            off += m.count;
-            t->msgs.push_back(m);
-            t->sboxes.insert(t->sboxes.end(), g.sb, g.sb + 6);
-            t->rboxes.insert(t->rboxes.end(), g.rb, g.rb + 6);
-            const bool zface = g.dir[0] == 0 && g.dir[1] == 0 && g.dir[2] != 0;
-            if (zface && !t->slab) {  // the neighbour across a z face shares this tile's x / y layout: whole planes of the array match
-                const size_t plane_f = (size_t) t->L[0] * t->L[1] * 3;
-                t->zmsgs.push_back(sobfu_hip_tiled_msg{g.peer, plane_f * (size_t) g.sb[4], plane_f * (size_t) g.rb[4], plane_f * (size_t) kHalo});
-            } else if (!zface) {
-                t->n_packed += 1;  // (z faces are last in the list)
-            }
-        }
-        if (t->slab) t->n_packed = (int) t->msgs.size();  // (slabs never take the packed path; keep the count meaningful)
+        t->mx = sobfu_hip::make_messages(t->lay);
+        const size_t off = t->mx.floats;
         if (off > 0) {
             rc = (int) hipMalloc((void**) &t->sendbuf, off * sizeof(float));
             if (rc == 0) rc = (int) hipMalloc((void**) &t->recvbuf, off * sizeof(float));
         }
-        if (rc == 0 && !t->slab && t->n_packed > 0) {  // where every cell of the packed receive buffer goes (x fastest inside a message box)
-            std::vector<uint32_t> tab;
-            for (int i = 0; i < t->n_packed; ++i) {
-                const int* b = t->rboxes.data() + 6 * i;
-                for (int z = b[4]; z < b[5]; ++z)
-                    for (int y = b[2]; y < b[3]; ++y)
-                        for (int x = b[0]; x < b[1]; ++x) tab.push_back((uint32_t) ((size_t) x + (size_t) t->L[0] * ((size_t) y + (size_t) t->L[1] * (size_t) z)));
-            }
+        if (rc == 0 && !t->lay.slab() && t->mx.n_packed > 0) {  // where every cell of the packed receive buffer goes
+            const std::vector<uint32_t> tab = sobfu_hip::scatter_table(t->lay, t->mx.n_packed);
             t->scatter_cells = (unsigned) tab.size();
             rc = (int) hipMalloc((void**) &t->scatter_table, tab.size() * sizeof(uint32_t));
             if (rc == 0) rc = (int) hipMemcpy(t->scatter_table, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -658,7 +502,7 @@ int sobfu_hip_tiled_connect(sobfu_hip_tiled* t, int n_peers, const int* peer_ran
     // a launch in the middle of a solve whose pass A has already pushed into the peers.
     sobfu_hip::PassBMarch m;
     const sobfu_hip::PassBAsk connected{true, false, true, true};
-    if (sobfu_hip::pass_b_march(sobfu_hip::grid_traits(t->L[0], t->L[1], t->L[2], t->X, t->Y, t->Z, 0), connected, &m) != 0) return SOBFU_E_UNSUPPORTED;
+    if (sobfu_hip::pass_b_march(sobfu_hip::grid_traits(t->lay.a[0].L, t->lay.a[1].L, t->lay.a[2].L, t->X, t->Y, t->Z, 0), connected, &m) != 0) return SOBFU_E_UNSUPPORTED;
     if (t->grows_own) {  // a longer solve on the unconnected handle moved the rows to a private array: back to the exported ones
         SOBFU_HIP_TRY(hipFree(t->grows_own));
         if (t->slots) SOBFU_HIP_TRY(hipFree(t->slots));
@@ -674,14 +518,14 @@ int sobfu_hip_tiled_connect(sobfu_hip_tiled* t, int n_peers, const int* peer_ran
         return nullptr;
     };
     // push destinations: every message needs its peer
-    std::vector<float*> d0(t->geom.size()), d1(t->geom.size());
+    std::vector<float*> d0(t->lay.msgs.size()), d1(t->lay.msgs.size());
     std::vector<TileLay> pl;
-    for (size_t i = 0; i < t->geom.size(); ++i) {
-        const sobfu_hip_tiled_exports* e = find(t->geom[i].peer);
+    for (size_t i = 0; i < t->lay.msgs.size(); ++i) {
+        const sobfu_hip_tiled_exports* e = find(t->lay.msgs[i].peer);
         if (!e || !e->arena || !e->flags) return SOBFU_E_BADARG;
         d0[i] = (float*) ((char*) e->arena + e->nabla_u_off[0]);
         d1[i] = (float*) ((char*) e->arena + e->nabla_u_off[1]);
-        pl.push_back(make_layout(dims, t->P, t->geom[i].peer));
+        pl.push_back(sobfu_hip::make_layout(dims, t->lay.P, t->lay.msgs[i].peer));
     }
     // sync set: EVERY other rank -- the halo neighbours for the nabla_U cells, the rest because the max-norm rows become global by
     // every rank storing its row maximum at every other rank (world <= 64: a few 4-byte stores per iteration)
@@ -835,41 +679,43 @@ int sobfu_hip_tiled_get_profile(sobfu_hip_tiled* t, float ms[3], int* samples, i
 
 int sobfu_hip_tiled_layout(const sobfu_hip_tiled* t, int* z0, int* z1, int* lo, int* hi, int* Lz, int* zbase) {
     SOBFU_CHECK_ARGS(t);
-    if (z0) *z0 = t->z0;
-    if (z1) *z1 = t->z1;
-    if (lo) *lo = t->lo[2];
-    if (hi) *hi = t->hi[2];
-    if (Lz) *Lz = t->Lz;
-    if (zbase) *zbase = t->zbase;
+    const sobfu_hip::AxisLay& z = t->lay.a[2];
+    if (z0) *z0 = z.g0;
+    if (z1) *z1 = z.g1;
+    if (lo) *lo = z.lo;
+    if (hi) *hi = z.hi;
+    if (Lz) *Lz = z.L;
+    if (zbase) *zbase = z.base;
     return 0;
 }
 
 int sobfu_hip_tiled_layout3(const sobfu_hip_tiled* t, int out[24]) {
     SOBFU_CHECK_ARGS(t && out);
     for (int a = 0; a < 3; ++a) {
-        out[a] = t->P[a]; out[3 + a] = t->c[a]; out[6 + a] = t->g0[a]; out[9 + a] = t->g1[a]; out[12 + a] = t->lo[a];
-        out[15 + a] = t->hi[a]; out[18 + a] = t->L[a]; out[21 + a] = t->base[a];
+        const sobfu_hip::AxisLay& l = t->lay.a[a];
+        out[a] = t->lay.P[a]; out[3 + a] = t->lay.c[a]; out[6 + a] = l.g0; out[9 + a] = l.g1; out[12 + a] = l.lo;
+        out[15 + a] = l.hi; out[18 + a] = l.L; out[21 + a] = l.base;
     }
     return 0;
 }
 
 int sobfu_hip_tiled_messages(const sobfu_hip_tiled* t, sobfu_hip_tiled_msg* msgs, int* send_boxes, int* recv_boxes, int max_msgs) {
     if (!t) return SOBFU_E_BADARG;
-    const int n = (int) t->msgs.size();
+    const int n = (int) t->mx.msgs.size();
     for (int i = 0; i < n && i < max_msgs; ++i) {
-        if (msgs) msgs[i] = t->msgs[i];
-        if (send_boxes) std::memcpy(send_boxes + 6 * i, t->sboxes.data() + 6 * i, 6 * sizeof(int));
-        if (recv_boxes) std::memcpy(recv_boxes + 6 * i, t->rboxes.data() + 6 * i, 6 * sizeof(int));
+        if (msgs) msgs[i] = t->mx.msgs[i];
+        if (send_boxes) std::memcpy(send_boxes + 6 * i, t->lay.msgs[i].sb, 6 * sizeof(int));
+        if (recv_boxes) std::memcpy(recv_boxes + 6 * i, t->lay.msgs[i].rb, 6 * sizeof(int));
     }
     return n;  // number of messages of an exchange
 }
 
 int sobfu_hip_tiled_messages_inplace(const sobfu_hip_tiled* t, sobfu_hip_tiled_msg* msgs, int max_msgs, int* n_packed) {
     if (!t) return SOBFU_E_BADARG;
-    if (n_packed) *n_packed = t->n_packed;
-    const int n = (int) t->zmsgs.size();
+    if (n_packed) *n_packed = t->mx.n_packed;
+    const int n = (int) t->mx.zmsgs.size();
     for (int i = 0; i < n && i < max_msgs; ++i)
-        if (msgs) msgs[i] = t->zmsgs[i];
+        if (msgs) msgs[i] = t->mx.zmsgs[i];
     return n;
 }
 
@@ -902,8 +748,8 @@ static int exchange_planes(sobfu_hip_tiled* t, float* field3, int planes, hipStr
     const size_t plane_f = (size_t) t->X * t->Y * 3, cnt = plane_f * planes;
     sobfu_hip_tiled_msg m[2];
     int n = 0;
-    if (t->rank > 0) m[n++] = {t->rank - 1, plane_f * t->own_lo, plane_f * (t->own_lo - planes), cnt};
-    if (t->rank < t->world - 1) m[n++] = {t->rank + 1, plane_f * (t->own_hi - planes), plane_f * t->own_hi, cnt};
+    if (t->rank > 0) m[n++] = {t->rank - 1, plane_f * t->lay.a[2].o0, plane_f * (t->lay.a[2].o0 - planes), cnt};
+    if (t->rank < t->world - 1) m[n++] = {t->rank + 1, plane_f * (t->lay.a[2].o1 - planes), plane_f * t->lay.a[2].o1, cnt};
     return transfer(t, field3, field3, m, n, stream);
 }
 
@@ -914,11 +760,11 @@ static int exchange_planes(sobfu_hip_tiled* t, float* field3, int planes, hipStr
 // (stale) halo content: exactly the cells of the xz / yz EDGE STRIPS, which the scatter -- behind the transfer on the same stream --
 // overwrites with the diagonal neighbours' cells; the corner regions beyond are never read (every stencil is axis-aligned).
 static int exchange_packed(sobfu_hip_tiled* t, float* field3, hipStream_t stream) {
-    const int n = t->n_packed, nz = (int) t->zmsgs.size();
+    const int n = t->mx.n_packed, nz = (int) t->mx.zmsgs.size();
     if (n + nz == 0) return 0;
-    SOBFU_TRY(transfer(t, t->sendbuf, t->recvbuf, t->msgs.data(), n, stream, field3, field3, t->zmsgs.data(), nz));
+    SOBFU_TRY(transfer(t, t->sendbuf, t->recvbuf, t->mx.msgs.data(), n, stream, field3, field3, t->mx.zmsgs.data(), nz));
     if (t->scatter_table) return sobfu_hip::launch_msg_scatter_table(field3, t->recvbuf, t->scatter_table, t->scatter_cells, stream);
-    return sobfu_hip::launch_msg_copy(false, field3, t->recvbuf, t->L[0], t->L[1], t->L[2], t->rboxes.data(), n, stream);
+    return sobfu_hip::launch_msg_copy(false, field3, t->recvbuf, t->lay.a[0].L, t->lay.a[1].L, t->lay.a[2].L, sobfu_hip::flat_boxes(t->lay, n, true).data(), n, stream);
 }
 
 static int allreduce_max(sobfu_hip_tiled* t, uint32_t* buf, size_t n, hipStream_t stream, bool own_comm = false) {
@@ -930,11 +776,11 @@ static int allreduce_max(sobfu_hip_tiled* t, uint32_t* buf, size_t n, hipStream_
 // Debug / bring-up: one halo exchange of a caller-provided 12-byte tile field exactly as the loop's RCCL / callback transports do
 // it (z-slabs: `planes` planes in place; 3-D tiles: pack, transfer, scatter).
 int sobfu_hip_tiled_exchange(sobfu_hip_tiled* t, float* d_field3, int planes, void* stream) {
-    SOBFU_CHECK_ARGS(t && d_field3 && planes > 0 && planes <= kHalo && (t->slab || planes == kHalo));
-    if (t->slab) return exchange_planes(t, d_field3, planes, (hipStream_t) stream);
-    const int n = t->n_packed;  // (the z faces travel in place: nothing to pack)
-    if (n + (int) t->zmsgs.size() == 0) return 0;
-    SOBFU_TRY(sobfu_hip::launch_msg_copy(true, d_field3, t->sendbuf, t->L[0], t->L[1], t->L[2], t->sboxes.data(), n, (hipStream_t) stream));
+    SOBFU_CHECK_ARGS(t && d_field3 && planes > 0 && planes <= kHalo && (t->lay.slab() || planes == kHalo));
+    if (t->lay.slab()) return exchange_planes(t, d_field3, planes, (hipStream_t) stream);
+    const int n = t->mx.n_packed;  // (the z faces travel in place: nothing to pack)
+    if (n + (int) t->mx.zmsgs.size() == 0) return 0;
+    SOBFU_TRY(sobfu_hip::launch_msg_copy(true, d_field3, t->sendbuf, t->lay.a[0].L, t->lay.a[1].L, t->lay.a[2].L, sobfu_hip::flat_boxes(t->lay, n, false).data(), n, (hipStream_t) stream));
     return exchange_packed(t, d_field3, (hipStream_t) stream);
 }
 
@@ -971,14 +817,14 @@ int sobfu_hip_tiled_allreduce_max_u32(sobfu_hip_tiled* t, uint32_t* d_buf, size_
 // a bare dry handle (no communicator, no transport plugged in) times the direct schedule -- or, with SOBFU_TILED_DRY_PACKED=1 at
 // create, the launches of the RCCL / callback transports (pass A packing into the send buffer, the scatter kernel, pass B)
 static bool uses_sync(const sobfu_hip_tiled* t) { return t->direct || (!t->comm && !t->xfn && !t->dry_packed); }
-static bool tile_path(const sobfu_hip_tiled* t) { return !t->slab || uses_sync(t); }
+static bool tile_path(const sobfu_hip_tiled* t) { return !t->lay.slab() || uses_sync(t); }
 
 static int tiled_begin(sobfu_hip_tiled* t, const float* d_phi_global_local, const float* d_phi_n_full, float* d_phi_n_psi_local,
                        float* d_psi_local, int max_iters, hipStream_t st) {
     sobfu_hip_tiled::Session& q = t->q;
     if (q.active) return SOBFU_E_BADARG;
     if (t->dead) return SOBFU_E_TIMEOUT;
-    const int X = t->X, Y = t->Y, Z = t->Z, Lx = t->L[0], Ly = t->L[1], Lz = t->L[2];
+    const int X = t->X, Y = t->Y, Z = t->Z, Lx = t->lay.a[0].L, Ly = t->lay.a[1].L, Lz = t->lay.a[2].L;
     float* P[2] = {t->c_psi, t->c_psi2};
     float* F[2] = {t->c_f, t->c_f2};
     if (max_iters > t->slots_iters) {
@@ -1032,7 +878,7 @@ static int first_iteration_watchdog(sobfu_hip_tiled* t, hipStream_t st) {
     }
     std::fprintf(stderr, "sobfu_hip: rank %d: the first tiled iteration has not completed after %.0f s -- waiting for the halo exchange "
                          "(grouped ncclSend/ncclRecv with ranks", t->rank, limit);
-    for (const sobfu_hip_tiled_msg& m : t->msgs) std::fprintf(stderr, " %d", m.peer);
+    for (const sobfu_hip_tiled_msg& m : t->mx.msgs) std::fprintf(stderr, " %d", m.peer);
     std::fprintf(stderr, ")%s; aborting the communicator(s)\n", t->p.max_update_norm >= 0.f ? " or the max-norm all-reduce" : "");
     abort_comms(t);
     return SOBFU_E_TIMEOUT;
@@ -1043,7 +889,7 @@ static int tiled_step_impl(sobfu_hip_tiled* t, int n_steps, hipStream_t st, int 
     sobfu_hip_tiled::Session& q = t->q;
     if (!q.active || n_steps < 0 || q.launched + n_steps > q.cap) return SOBFU_E_BADARG;
     if (t->dead) return SOBFU_E_TIMEOUT;
-    const int X = t->X, Y = t->Y, Z = t->Z, Lx = t->L[0], Ly = t->L[1], Lz = t->L[2];
+    const int X = t->X, Y = t->Y, Z = t->Z, Lx = t->lay.a[0].L, Ly = t->lay.a[1].L, Lz = t->lay.a[2].L;
     const sobfu_hip_solver_params& p = t->p;
     float* P[2] = {t->c_psi, t->c_psi2};
     float* F[2] = {t->c_f, t->c_f2};
@@ -1051,11 +897,10 @@ static int tiled_step_impl(sobfu_hip_tiled* t, int n_steps, hipStream_t st, int 
     // (SOBFU_TILED_FORCE_COMM=1 at create runs the communication choreography -- streams, events, empty exchange group, world-1
     // all-reduce -- on a single rank too: bring-up / test hook for 1-GPU machines)
     const bool can_converge = p.max_update_norm >= 0.f, multi = t->world > 1 || t->force_comm;
-    const int lo = t->own_lo, hi = t->own_hi, H = kHalo;
-    const int a_lo = t->lo[2] ? std::min(lo + H, hi) : lo, a_hi = t->hi[2] ? std::max(hi - H, a_lo) : hi;
-    const int b_lo = t->lo[2] ? std::min(lo + 3, hi) : lo, b_hi = t->hi[2] ? std::max(hi - 3, b_lo) : hi;
-    const int b_first = t->lo[2] ? lo - 1 : lo, b_last = t->hi[2] ? hi + 1 : hi;
-    const int ax0 = t->o0[0], ax1 = t->o1[0], ay0 = t->o0[1], ay1 = t->o1[1];
+    const sobfu_hip::AxisLay &lx = t->lay.a[0], &ly = t->lay.a[1], &lz = t->lay.a[2];
+    const int lo = lz.o0, hi = lz.o1, H = kHalo;
+    const auto [a_lo, a_hi, b_lo, b_hi, b_first, b_last] = sobfu_hip::plane_ranges(t->lay);
+    const int ax0 = lx.o0, ax1 = lx.o1, ay0 = ly.o0, ay1 = ly.o1;
     const int own[6] = {ax0, ax1, ay0, ay1, lo, hi};
     const bool tiles = tile_path(t), sync = uses_sync(t);
     // timing experiments only (results are wrong): bit 0 no push boxes, bit 1 no thin shells, bit 2 no pass A, bit 3 no pass B,
@@ -1067,7 +912,7 @@ static int tiled_step_impl(sobfu_hip_tiled* t, int n_steps, hipStream_t st, int 
     // the slab is so thin that the 3.1 MB face messages cannot hide behind B_int alone (N >= 4 at 256^3, if a face takes the ~65 us that ~60 GB/s per xGMI direction implies)
     // the schedule (results do not depend on it): sobfu_hip_tiled_set_schedule (autotuner, tests) > heuristic
     const bool want_split = t->schedule == 1 ? true : (t->schedule == 2 ? false : (hi - lo) <= kSplitAMaxPlanes);
-    const bool split_a = (t->lo[2] || t->hi[2]) && a_hi > a_lo && want_split;
+    const bool split_a = (lz.lo || lz.hi) && a_hi > a_lo && want_split;
     const bool serial = t->schedule == 3;  // z-slab path only
     // Where the all-reduce of a max-norm row runs on the RCCL / callback transports (the late gate gives row j until pass B of
     // iteration j+2): in line behind pass B (serial / tile path), on the comm stream behind the next exchange (overlapped slab
@@ -1105,10 +950,10 @@ static int tiled_step_impl(sobfu_hip_tiled* t, int n_steps, hipStream_t st, int 
             for (int i = 0; i < 6; ++i) L.own[i] = own[i];
             L.boxes[0] = {ax0, ax1, ay0, ay1, za, (dbg & 16) ? za : zb, false};
             L.boxes[1] = {ax0, ax1, ay0, ay1, za2, zb2, false};
-            L.boxes[2] = {ax0, ax1, ay0 - 1, (ysh && t->lo[1]) ? ay0 : ay0 - 1, lo, hi, true};
-            L.boxes[3] = {ax0, ax1, ay1, (ysh && t->hi[1]) ? ay1 + 1 : ay1, lo, hi, true};
-            L.boxes[4] = {ax0 - 1, (xsh && t->lo[0]) ? ax0 : ax0 - 1, ay0, ay1, lo, hi, true};
-            L.boxes[5] = {ax1, (xsh && t->hi[0]) ? ax1 + 1 : ax1, ay0, ay1, lo, hi, true};
+            L.boxes[2] = {ax0, ax1, ay0 - 1, (ysh && ly.lo) ? ay0 : ay0 - 1, lo, hi, true};
+            L.boxes[3] = {ax0, ax1, ay1, (ysh && ly.hi) ? ay1 + 1 : ay1, lo, hi, true};
+            L.boxes[4] = {ax0 - 1, (xsh && lx.lo) ? ax0 : ax0 - 1, ay0, ay1, lo, hi, true};
+            L.boxes[5] = {ax1, (xsh && lx.hi) ? ax1 + 1 : ax1, ay0, ay1, lo, hi, true};
             L.n_boxes  = 6;
             L.prev_slots = prev; L.max_update_norm = p.max_update_norm; L.prev_rows = it > 3 ? 2 : 1;
             L.compact     = true;
@@ -1289,11 +1134,7 @@ static int tiled_end(sobfu_hip_tiled* t, sobfu_hip_solver_report* report, float*
     }
     int done = n_iters;
     for (int k = 0; k < n_iters; ++k) {
-        uint32_t m = 0;
-        for (int i = 0; i < kSlots; ++i) m = std::max(m, hs[(size_t) k * kSlots + i]);
-        float f;
-        std::memcpy(&f, &m, 4);
-        const float v = host_sqrt_rd(f);
+        const float v = sobfu_hip::slots_to_norm(hs.data() + (size_t) k * kSlots);
         if (per_iter_max_norm) per_iter_max_norm[k] = v;
         r.last_max_update_norm = v;
         if (can_converge && v <= p.max_update_norm) {  // solver.cu:183 -- iteration k+2 ran speculatively, later ones not at all
@@ -1306,7 +1147,7 @@ static int tiled_end(sobfu_hip_tiled* t, sobfu_hip_solver_report* report, float*
     // leave the compact format from the half that holds the state after `done` iterations: psi.xyz back,
     // phi_n o psi = apply(phi_n, psi) (the state of solver.cu:168)
     SOBFU_TRY(sobfu_hip::launch_unpack_vec(P[done & 1], q.psi, t->NL, st));
-    SOBFU_TRY(sobfu_hip_tile3_apply(q.pn, t->X, t->Y, t->Z, q.pnp, q.psi, t->L[0], t->L[1], t->L[2], st));
+    SOBFU_TRY(sobfu_hip_tile3_apply(q.pn, t->X, t->Y, t->Z, q.pnp, q.psi, t->lay.a[0].L, t->lay.a[1].L, t->lay.a[2].L, st));
     SOBFU_HIP_TRY(hipStreamSynchronize(st));
     q.active = false;
     if (report) *report = r;
