@@ -26,6 +26,15 @@
 // writes DIR/tracked_<n>.ply: the kept mesh carried to frame n by that frame's psi, so vertex i and the faces are the same in every file.
 // --fit-stats prints one line per solved frame: phi_n sampled at the canonical mesh's vertices warped to live (and unwarped), in millimetres.
 //
+// Reconstruction error against ground-truth meshes (opt-in; sobfu_amd/csrc/mesh_distance_kernels.hip): exact vertex-to-surface
+// distances both ways, a = the model, b = the ground truth, one printed line per evaluation with every field of compare_meshes at %.9g, in
+// metres.  --evaluate GT.ply: after the last frame, the indexed mesh of phi_global against GT ("evaluate canonical <frame>: ...").
+// --evaluate-live PATTERN (printf-style, one %d or %0Nd: the frame number): on every solved frame, phi_global's mesh carried through psi
+// against that frame's ground truth ("evaluate live <frame>: ...").  The ground truth is in the frame of the meshes written here (x, -y, -z);
+// --evaluate-pose FILE (16 numbers, row-major 4 x 4) is applied to it first.  --evaluate-max-dist METRES (default 5 x the truncation distance):
+// vertices farther than that have no match.  --error-mesh DIR writes the evaluated mesh as DIR/error_canonical_<frame>.ply /
+// DIR/error_live_<frame>.ply with vertices coloured by error: blue (0) to red (max-dist), grey where there is no match.
+//
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
 //                  [--warp-mesh] [--track-mesh K] [--fit-stats]
@@ -158,10 +167,24 @@ struct Screenshots {
     }
 };
 
+// PATTERN of --evaluate-live with the frame number in place of its one %d / %0Nd; empty: not such a pattern
+static std::string frame_path(const std::string& pattern, int n) {
+    const size_t at = pattern.find('%');
+    if (at == std::string::npos || pattern.find('%', at + 1) != std::string::npos) return "";
+    size_t e = at + 1;
+    while (e < pattern.size() && pattern[e] >= '0' && pattern[e] <= '9') ++e;
+    if (e >= pattern.size() || pattern[e] != 'd' || e - at > 4) return "";
+    std::string digits = std::to_string(n);
+    const int width = e > at + 1 ? std::atoi(pattern.substr(at + 1, e - at - 1).c_str()) : 0;
+    if (pattern[at + 1] == '0' || width > 0)
+        while ((int) digits.size() < width) digits.insert(digits.begin(), pattern[at + 1] == '0' ? '0' : ' ');
+    return pattern.substr(0, at) + digits + pattern.substr(e + 1);
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -176,6 +199,8 @@ int main(int argc, char** argv) {
     bool textured = false, warp_mesh = false, fit_stats = false;
     int track_mesh = -1;  // the frame after which the tracked mesh is cut; -1: off
     std::string dump, mesh_dir, data_dir, mesh_format = "vtk", poses_path;
+    std::string eval_gt, eval_live, eval_pose, error_dir;
+    float eval_max_dist = -1.f;  // < 0: 5 x the truncation distance
     Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
     std::vector<std::string> files;
@@ -200,6 +225,11 @@ int main(int argc, char** argv) {
         else if (a == "--warp-mesh") warp_mesh = true;
         else if (a == "--track-mesh" && i + 1 < argc) track_mesh = std::atoi(argv[++i]);
         else if (a == "--fit-stats") fit_stats = true;
+        else if (a == "--evaluate" && i + 1 < argc) eval_gt = argv[++i];
+        else if (a == "--evaluate-live" && i + 1 < argc) eval_live = argv[++i];
+        else if (a == "--evaluate-max-dist" && i + 1 < argc) eval_max_dist = std::strtof(argv[++i], nullptr);
+        else if (a == "--evaluate-pose" && i + 1 < argc) eval_pose = argv[++i];
+        else if (a == "--error-mesh" && i + 1 < argc) error_dir = argv[++i];
         else files.push_back(a);
     }
     if (mesh_format != "vtk" && mesh_format != "ply") {
@@ -218,6 +248,45 @@ int main(int argc, char** argv) {
         p.tsdf_trunc_dist = tv * p.voxel_sizes()[0];
         p.eta = ev * p.voxel_sizes()[0];
     }
+    // ground truth of --evaluate / --evaluate-live: read, posed, compared; one printed line, one optional error mesh
+    float gt_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    if (!eval_pose.empty()) {
+        FILE* f = std::fopen(eval_pose.c_str(), "r");
+        int got = 0;
+        while (f && got < 16 && std::fscanf(f, "%f", &gt_pose[got]) == 1) ++got;
+        if (f) std::fclose(f);
+        if (got != 16) {
+            std::printf("--evaluate-pose %s: expected 16 numbers\n", eval_pose.c_str());
+            return 2;
+        }
+    }
+    if (!eval_live.empty() && frame_path(eval_live, 0).empty()) {
+        std::printf("--evaluate-live needs a pattern with one %%d or %%0Nd, not %s\n", eval_live.c_str());
+        return 2;
+    }
+    if (eval_max_dist < 0.f) eval_max_dist = 5.f * p.tsdf_trunc_dist;
+    auto evaluate = [&](SobFusion& fusion, const std::string& gt_path, bool live, int n) {
+        sobfu_amd::IndexedMesh gt, model;
+        std::string why;
+        if (!sobfu_amd::read_ply(gt_path, gt, &why)) {
+            std::printf("cannot read ground truth: %s\n", why.c_str());
+            return false;
+        }
+        if (!eval_pose.empty()) sobfu_amd::transform_points(gt.vertices, gt_pose);
+        sobfu_amd::MeshComparison r;
+        std::vector<float> d;
+        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why) : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why))) {
+            std::printf("cannot evaluate against %s: %s\n", gt_path.c_str(), why.c_str());
+            return false;
+        }
+        std::printf("evaluate %s %d: %s\n", live ? "live" : "canonical", n, sobfu_amd::format_comparison(r).c_str());
+        if (!error_dir.empty() && !model.empty()) {
+            sobfu_amd::error_colours(d, eval_max_dist, model.colours);
+            const std::string path = error_dir + (live ? "/error_live_" : "/error_canonical_") + std::to_string(n) + ".ply";
+            if (!sobfu_amd::write_ply(path, model)) std::printf("cannot write %s\n", path.c_str());
+        }
+        return true;
+    };
     std::vector<std::string> colour_files, mask_files;
     if (!data_dir.empty()) {  // demo.cpp:177-197, with a colour-less dataset allowed
         if (!files.empty() || synthetic > 0) {
@@ -327,6 +396,8 @@ int main(int argc, char** argv) {
                             1e3 * f.mean_abs, 1e3 * f.rms, 1e3 * f.max, 1e3 * before.rms);
             }
         }
+        if (solved_frame && !eval_live.empty() && !evaluate(fusion, frame_path(eval_live, n), true, n)) return 2;
+        if (n == nframes - 1 && !eval_gt.empty() && !evaluate(fusion, eval_gt, false, n)) return 2;
         if (track_mesh >= 0 && n == track_mesh) tracked = fusion.get_phi_global_indexed_mesh();
         if (track_mesh >= 0 && n >= track_mesh && solved_frame) save_ply("tracked", fusion.warp_to_live(tracked));
         if (!shots.dir.empty()) {

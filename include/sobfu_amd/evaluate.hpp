@@ -1,0 +1,350 @@
+// Reconstruction error against a ground-truth mesh (no reference counterpart; kernels and rules: sobfu_amd/csrc/mesh_distance_kernels.hip,
+// DESIGN.md 4.9): a PLY reader, the triangle grid over the C ABI, the two-way vertex-to-surface comparison and its statistics.  Part of
+// sobfu.hpp, which includes it after IndexedMesh, DeviceArray and sobfuSafeCall: not a header to include on its own.  The Python twins are
+// sobfu_amd/mesh_io.py (read_ply) and sobfu_amd/evaluate.py (compare_meshes).
+#pragma once
+
+namespace sobfu_amd {
+
+// ---- read_ply: the rules and refusals of sobfu_amd.mesh_io.read_ply -------------------------------------------------------------------
+// ASCII or binary little-endian PLY 1.0 -> vertices (w = 1), normals (w = 1; empty when the file has none), faces, colours (empty when
+// the file has none).  Vertex properties in any order, unknown scalar properties skipped; face lists with any integer count and index
+// types.  false + *why for: polygons other than triangles, big-endian files, element counts the file is too short for, vertex indices
+// out of range, a header it cannot parse.
+namespace ply_detail {
+struct Prop {
+    std::string name;
+    int type = -1, count_type = -1;  // indices into kTypes; count_type >= 0: a list
+};
+struct Element {
+    std::string name;
+    size_t count = 0;
+    std::vector<Prop> props;
+};
+struct Type {
+    const char *a, *b;
+    int size;
+    char kind;  // i, u, f
+};
+static const Type kTypes[8] = {{"char", "int8", 1, 'i'},   {"uchar", "uint8", 1, 'u'}, {"short", "int16", 2, 'i'},  {"ushort", "uint16", 2, 'u'},
+                               {"int", "int32", 4, 'i'},   {"uint", "uint32", 4, 'u'}, {"float", "float32", 4, 'f'}, {"double", "float64", 8, 'f'}};
+inline int type_of(const std::string& s) {
+    for (int i = 0; i < 8; ++i)
+        if (s == kTypes[i].a || s == kTypes[i].b) return i;
+    return -1;
+}
+// one little-endian scalar at p (the caller has checked the bounds)
+inline double scalar_at(const unsigned char* p, int type) {
+    switch (type) {
+        case 0: { signed char v; std::memcpy(&v, p, 1); return v; }
+        case 1: return *p;
+        case 2: { short v; std::memcpy(&v, p, 2); return v; }
+        case 3: { unsigned short v; std::memcpy(&v, p, 2); return v; }
+        case 4: { int v; std::memcpy(&v, p, 4); return v; }
+        case 5: { unsigned v; std::memcpy(&v, p, 4); return v; }
+        case 6: { float v; std::memcpy(&v, p, 4); return v; }
+        default: { double v; std::memcpy(&v, p, 8); return v; }
+    }
+}
+inline std::vector<std::string> words(const std::string& line) {
+    std::vector<std::string> w;
+    std::istringstream is(line);
+    for (std::string s; is >> s;) w.push_back(s);
+    return w;
+}
+inline bool all_digits(const std::string& s) { return !s.empty() && s.find_first_not_of("0123456789") == std::string::npos && s.size() <= 18; }
+}  // namespace ply_detail
+
+inline bool read_ply(const std::string& path, IndexedMesh& m, std::string* why = nullptr) {
+    using namespace ply_detail;
+    auto fail = [&](const std::string& msg) {
+        if (why) *why = path + ": " + msg;
+        return false;
+    };
+    m = IndexedMesh();
+    std::vector<unsigned char> buf;
+    {
+        FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) return fail("cannot open");
+        unsigned char chunk[65536];
+        for (size_t n; (n = std::fread(chunk, 1, sizeof chunk, f)) > 0;) buf.insert(buf.end(), chunk, chunk + n);
+        std::fclose(f);
+    }
+    const std::string text(buf.begin(), buf.end());
+    if (text.compare(0, 4, "ply\n") != 0 && text.compare(0, 4, "ply\r") != 0) return fail("not a PLY file");
+    const size_t end = text.find("end_header"), nl = end == std::string::npos ? end : text.find('\n', end);
+    if (nl == std::string::npos) return fail("the PLY header has no end_header line");
+    std::string fmt;
+    std::vector<Element> elements;
+    {
+        std::istringstream hs(text.substr(0, end));
+        std::string line;
+        std::getline(hs, line);  // "ply"
+        while (std::getline(hs, line)) {
+            const std::vector<std::string> w = words(line);
+            if (w.empty() || w[0] == "comment" || w[0] == "obj_info") continue;
+            if (w[0] == "format" && w.size() == 3) {
+                if (w[1] == "binary_big_endian") return fail("big-endian PLY files are not supported");
+                if ((w[1] != "ascii" && w[1] != "binary_little_endian") || w[2] != "1.0") return fail("unknown PLY format");
+                fmt = w[1];
+            } else if (w[0] == "element" && w.size() == 3 && all_digits(w[2])) {
+                Element e;
+                e.name = w[1], e.count = (size_t) std::strtoull(w[2].c_str(), nullptr, 10);
+                elements.push_back(e);
+            } else if (w[0] == "property" && !elements.empty() && w.size() == 3 && type_of(w[1]) >= 0) {
+                Prop p;
+                p.name = w[2], p.type = type_of(w[1]);
+                elements.back().props.push_back(p);
+            } else if (w[0] == "property" && !elements.empty() && w.size() == 5 && w[1] == "list" && type_of(w[2]) >= 0 && type_of(w[3]) >= 0) {
+                Prop p;
+                p.name = w[4], p.count_type = type_of(w[2]), p.type = type_of(w[3]);
+                elements.back().props.push_back(p);
+            } else {
+                return fail("cannot read the PLY header line '" + line + "'");
+            }
+        }
+    }
+    if (fmt.empty()) return fail("the PLY header has no format line");
+    const bool ascii = fmt == "ascii";
+    size_t off = nl + 1;
+    std::vector<std::string> tokens;
+    size_t tok = 0;
+    if (ascii) tokens = words(text.substr(off));
+    bool have_vertex = false, have_normals = false, have_colours = false;
+    for (const Element& e : elements) {
+        size_t lists = 0;
+        for (const Prop& p : e.props) lists += p.count_type >= 0;
+        if (lists && (e.name != "face" || e.props.size() != 1)) return fail("element " + e.name + " has list properties this reader does not handle");
+        const std::string too_short = "element " + e.name + " declares " + std::to_string(e.count) + " entries, more than the file holds";
+        if (!lists) {  // fixed-size records
+            const size_t np = e.props.size();
+            size_t rec = 0;
+            for (const Prop& p : e.props) rec += (size_t) kTypes[p.type].size;
+            if (ascii ? (np && e.count > (tokens.size() - tok) / np) : (rec && e.count > (buf.size() - off) / rec)) return fail(too_short);
+            const bool vertex = e.name == "vertex";
+            int ix[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};  // x y z nx ny nz red green blue -> property index
+            static const char* kNames[9] = {"x", "y", "z", "nx", "ny", "nz", "red", "green", "blue"};
+            for (size_t j = 0; vertex && j < np; ++j)
+                for (int k = 0; k < 9; ++k)
+                    if (e.props[j].name == kNames[k]) ix[k] = (int) j;
+            if (vertex) {
+                if (ix[0] < 0 || ix[1] < 0 || ix[2] < 0) return fail("the vertex element has no x, y, z");
+                have_vertex = true, have_normals = ix[3] >= 0 && ix[4] >= 0 && ix[5] >= 0, have_colours = ix[6] >= 0 && ix[7] >= 0 && ix[8] >= 0;
+                m.vertices.resize(e.count);
+                if (have_normals) m.normals.resize(e.count);
+                if (have_colours) m.colours.resize(e.count);
+            }
+            std::vector<double> row(np);
+            for (size_t i = 0; i < e.count; ++i) {
+                for (size_t j = 0; j < np; ++j) {
+                    if (ascii) {
+                        char* stop = nullptr;
+                        row[j] = std::strtod(tokens[tok].c_str(), &stop);
+                        if (stop == tokens[tok].c_str() || *stop) return fail("element " + e.name + " holds something that is not a number");
+                        ++tok;
+                    } else {
+                        row[j] = scalar_at(buf.data() + off, e.props[j].type);
+                        off += (size_t) kTypes[e.props[j].type].size;
+                    }
+                }
+                if (!vertex) continue;
+                m.vertices[i] = make_float4((float) row[ix[0]], (float) row[ix[1]], (float) row[ix[2]], 1.f);
+                if (have_normals) m.normals[i] = make_float4((float) row[ix[3]], (float) row[ix[4]], (float) row[ix[5]], 1.f);
+                if (have_colours) {
+                    kfusion::RGB c;
+                    c.bgra = 0;
+                    c.r = (unsigned char) row[ix[6]], c.g = (unsigned char) row[ix[7]], c.b = (unsigned char) row[ix[8]];
+                    m.colours[i] = c;
+                }
+            }
+            continue;
+        }
+        if (!have_vertex) return fail("the face element comes before the vertex element");
+        const Prop& p = e.props[0];
+        if (kTypes[p.count_type].kind == 'f' || kTypes[p.type].kind == 'f') return fail("the face list must have integer counts and indices");
+        const size_t cs = (size_t) kTypes[p.count_type].size, is = (size_t) kTypes[p.type].size, V = m.vertices.size();
+        if (ascii ? e.count > (tokens.size() - tok) / 4 : e.count > (buf.size() - off) / (cs + 3 * is)) {
+            // a short file, unless its first polygon already says why the sizes do not add up
+            if (!ascii && e.count && buf.size() - off >= cs && scalar_at(buf.data() + off, p.count_type) != 3.0)
+                return fail("only triangles are supported, found a polygon of another size");
+            return fail(too_short);
+        }
+        m.faces.resize(3 * e.count);
+        for (size_t i = 0; i < e.count; ++i) {
+            double v[4];
+            for (int j = 0; j < 4; ++j) {
+                if (ascii) {
+                    char* stop = nullptr;
+                    v[j] = (double) std::strtoll(tokens[tok].c_str(), &stop, 10);
+                    if (stop == tokens[tok].c_str() || *stop) return fail("the face element holds something that is not an integer");
+                    ++tok;
+                } else {
+                    v[j] = scalar_at(buf.data() + off, j ? p.type : p.count_type);
+                    off += j ? is : cs;
+                }
+                if (j == 0 && v[0] != 3.0) return fail("only triangles are supported, found a polygon of another size");
+            }
+            for (int j = 1; j < 4; ++j) {
+                if (v[j] < 0 || v[j] >= (double) V) return fail("a face refers to a vertex outside [0, " + std::to_string(V) + ")");
+                m.faces[3 * i + (size_t) j - 1] = (int) v[j];
+            }
+        }
+    }
+    if (!have_vertex) return fail("no vertex element");
+    return true;
+}
+
+// ---- TriangleGrid: the grid of sobfu_hip_mesh_grid_build over a mesh kept on the device ---------------------------------------------
+class TriangleGrid {
+public:
+    // false (+ *why): a face index out of range or a non-finite corner -- there is no grid to query then
+    bool build(const std::vector<float4>& vertices, const std::vector<int>& faces, float cell = 0.f, std::string* why = nullptr) {
+        built_ = false;
+        nv_ = (int) vertices.size(), nt_ = (int) (faces.size() / 3);
+        float bbox[6] = {0, 0, 0, 0, 0, 0};
+        bool any = false;
+        for (const float4& v : vertices) {
+            if (!(std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z)) || nt_ == 0) continue;
+            const float c[3] = {v.x, v.y, v.z};
+            for (int i = 0; i < 3; ++i) {
+                bbox[i]     = any ? std::min(bbox[i], c[i]) : c[i];
+                bbox[3 + i] = any ? std::max(bbox[3 + i], c[i]) : c[i];
+            }
+            any = true;
+        }
+        sobfuSafeCall(sobfu_hip_mesh_grid_plan(bbox, nt_, cell, origin_, &h_, dims_));
+        vertices_.release(), faces_.release();
+        if (nv_) vertices_.upload(vertices);
+        if (nt_) faces_.upload(faces.data(), 3 * (size_t) nt_);
+        int max_refs = 8 * nt_ + 1024, refs = 0;
+        for (;;) {
+            workspace_.create(sobfu_hip_mesh_grid_workspace_bytes(dims_, max_refs));
+            const int rc = sobfu_hip_mesh_grid_build(nv_ ? (const float*) vertices_.ptr() : nullptr, nv_, nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_,
+                                                     workspace_.ptr(), workspace_.size(), max_refs, &refs, nullptr);
+            if (rc == SOBFU_E_UNSUPPORTED && refs > max_refs) {
+                max_refs = refs;
+                continue;
+            }
+            if (rc == SOBFU_E_BADARG) {
+                if (why) *why = "the mesh has a face index out of range or a non-finite corner";
+                return false;
+            }
+            sobfuSafeCall(rc);
+            break;
+        }
+        references_ = refs;
+        return built_ = true;
+    }
+    // distances (+Inf: farther than max_dist), and optionally the nearest triangles and closest points, of `points`
+    void query(const std::vector<float4>& points, std::vector<float>& dist, float max_dist = 0.f, std::vector<int>* tri = nullptr,
+               std::vector<float4>* closest = nullptr, int mode = SOBFU_MESH_DISTANCE_AUTO, int ring_cap = 0) {
+        if (!built_) kfusion::cuda::error("TriangleGrid::query without a built grid", __FILE__, __LINE__);
+        const size_t n = points.size();
+        dist.assign(n, 0.f);
+        if (tri) tri->assign(n, -1);
+        if (closest) closest->assign(n, make_float4(0.f, 0.f, 0.f, 0.f));
+        if (n == 0) return;
+        kfusion::cuda::DeviceArray<float4> dp, dc;
+        kfusion::cuda::DeviceArray<float> dd(n);
+        kfusion::cuda::DeviceArray<int> dt(n), du(n);
+        dp.upload(points);
+        if (closest) dc.create(n);
+        sobfuSafeCall(sobfu_hip_mesh_distance(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
+                                              nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dp.ptr(), (int) n, max_dist, mode, ring_cap,
+                                              dd.ptr(), dt.ptr(), closest ? (float*) dc.ptr() : nullptr, du.ptr(), nullptr));
+        dd.download(dist);
+        if (tri) dt.download(*tri);
+        if (closest) dc.download(*closest);
+    }
+    int references() const { return references_; }
+    const int* dims() const { return dims_; }
+    float cell() const { return h_; }
+
+private:
+    kfusion::cuda::DeviceArray<float4> vertices_;
+    kfusion::cuda::DeviceArray<int> faces_;
+    kfusion::cuda::DeviceArray<unsigned char> workspace_;
+    float origin_[3] = {0, 0, 0}, h_ = 0.f;
+    int dims_[3] = {1, 1, 1}, nv_ = 0, nt_ = 0, references_ = 0;
+    bool built_ = false;
+};
+
+// ---- compare_meshes: float64 statistics over the finite distances, as sobfu_amd.evaluate.distance_stats ------------------------------
+struct DistanceStats {
+    size_t n = 0, within = 0;
+    double mean = 0, rms = 0, median = 0, max = 0;
+};
+struct MeshComparison {
+    DistanceStats a_to_b, b_to_a;
+    double chamfer = 0, hausdorff = 0;  // the mean of the two means; the larger of the two maxima
+};
+inline DistanceStats distance_stats(const std::vector<float>& dist) {
+    DistanceStats s;
+    s.n = dist.size();
+    std::vector<double> f;
+    for (float d : dist)
+        if (std::isfinite(d)) f.push_back((double) d);
+    if (f.empty()) return s;
+    double s1 = 0, s2 = 0;
+    for (double d : f) s1 += d, s2 += d * d, s.max = std::max(s.max, d);
+    s.within = f.size();
+    s.mean = s1 / (double) f.size(), s.rms = std::sqrt(s2 / (double) f.size());
+    std::sort(f.begin(), f.end());
+    s.median = f.size() % 2 ? f[f.size() / 2] : 0.5 * (f[f.size() / 2 - 1] + f[f.size() / 2]);
+    return s;
+}
+// a = the model, b = the ground truth, by convention; vertex-to-surface both ways.  false: one of the meshes is refused (TriangleGrid::build)
+inline bool compare_meshes(const IndexedMesh& a, const IndexedMesh& b, float max_dist, MeshComparison& out, std::vector<float>* d_ab = nullptr,
+                           std::vector<float>* d_ba = nullptr, std::string* why = nullptr) {
+    TriangleGrid ga, gb;
+    if (!gb.build(b.vertices, b.faces, 0.f, why) || !ga.build(a.vertices, a.faces, 0.f, why)) return false;
+    std::vector<float> ab, ba;
+    gb.query(a.vertices, ab, max_dist);
+    ga.query(b.vertices, ba, max_dist);
+    out.a_to_b = distance_stats(ab), out.b_to_a = distance_stats(ba);
+    out.chamfer = 0.5 * (out.a_to_b.mean + out.b_to_a.mean), out.hausdorff = std::max(out.a_to_b.max, out.b_to_a.max);
+    if (d_ab) d_ab->swap(ab);
+    if (d_ba) d_ba->swap(ba);
+    return true;
+}
+// one line, every field at %.9g (sobfu_amd.evaluate.format_result); digits: another precision (17 round-trips a double)
+inline std::string format_comparison(const MeshComparison& r, int digits = 9) {
+    char line[1536];
+    const DistanceStats &x = r.a_to_b, &y = r.b_to_a;
+    std::snprintf(line, sizeof line,
+                  "a_to_b.n=%zu a_to_b.within=%zu a_to_b.mean=%.*g a_to_b.rms=%.*g a_to_b.median=%.*g a_to_b.max=%.*g "
+                  "b_to_a.n=%zu b_to_a.within=%zu b_to_a.mean=%.*g b_to_a.rms=%.*g b_to_a.median=%.*g b_to_a.max=%.*g chamfer=%.*g hausdorff=%.*g",
+                  x.n, x.within, digits, x.mean, digits, x.rms, digits, x.median, digits, x.max, y.n, y.within, digits, y.mean, digits, y.rms, digits,
+                  y.median, digits, y.max, digits, r.chamfer, digits, r.hausdorff);
+    return line;
+}
+// (n, 4) points through a row-major 4 x 4 transform in float32: ((m0 x + m1 y) + m2 z) + t per row, w = 1 (sobfu_amd.fusion.transform_points)
+inline void transform_points(std::vector<float4>& points, const float pose[16]) {
+    for (float4& p : points) {
+        float o[3];
+        for (int i = 0; i < 3; ++i) {
+            const volatile float xy = pose[4 * i] * p.x + pose[4 * i + 1] * p.y;  // volatile: no contraction into an fma, whatever the flags
+            const volatile float xyz = xy + pose[4 * i + 2] * p.z;
+            o[i] = xyz + pose[4 * i + 3];
+        }
+        p = make_float4(o[0], o[1], o[2], 1.f);
+    }
+}
+// Vertex colours by error: a fixed ramp from blue (0) to red (max_dist and beyond), r = round(255 t), b = round(255 (1 - t)), g = 0 with
+// t = clamp(d / max_dist, 0, 1) in double; grey (128, 128, 128) where there is no match
+inline void error_colours(const std::vector<float>& dist, float max_dist, std::vector<kfusion::RGB>& colours) {
+    colours.resize(dist.size());
+    for (size_t i = 0; i < dist.size(); ++i) {
+        kfusion::RGB c;
+        c.bgra = 0;
+        if (!std::isfinite(dist[i]) || !(max_dist > 0.f)) {
+            c.r = c.g = c.b = 128;
+        } else {
+            const double t = std::min(1.0, std::max(0.0, (double) dist[i] / (double) max_dist));
+            c.r = (unsigned char) (255.0 * t + 0.5), c.g = 0, c.b = (unsigned char) (255.0 * (1.0 - t) + 0.5);
+        }
+        colours[i] = c;
+    }
+}
+
+}  // namespace sobfu_amd

@@ -1304,6 +1304,9 @@ inline MeshFit mesh_fit(const IndexedMesh& m, const kfusion::cuda::TsdfVolume& v
 }
 }  // namespace sobfu_amd
 
+// ---- reconstruction error against a ground-truth mesh: read_ply, TriangleGrid, compare_meshes (rules: DESIGN.md 4.9) ----------------------
+#include "evaluate.hpp"
+
 // SobFusion (include/sobfu/sob_fusion.hpp, src/sobfu/sob_fusion.cpp:71-145) -- per-frame driver: bilateral filter ->
 // depth truncation -> dists; frame 0 builds phi_global and allocates everything; frame n builds phi_n, fuses it
 // directly while n < START_FRAME, otherwise estimates psi (warm-started) and fuses phi_n o psi.
@@ -1411,6 +1414,24 @@ public:
     sobfu_amd::MeshFit fit_to_live(const sobfu_amd::IndexedMesh& m, std::vector<float>* samples = nullptr) {
         if (!phi_n) kfusion::cuda::error("fit_to_live needs a second frame", __FILE__, __LINE__);
         return sobfu_amd::mesh_fit(m, *phi_n, params, samples);
+    }
+    // The reconstruction against a ground-truth mesh given in the frame of the meshes written here (marching-cubes vertices, (x, -y, -z)):
+    // exact vertex-to-surface distances both ways, in metres (a = the model, b = the ground truth).  evaluate_canonical: the indexed mesh
+    // of phi_global; evaluate_live: that mesh carried through psi.  Reads the volumes only.  model / d_model (optional): the evaluated
+    // mesh and its vertices' distances.  false (+ *why): the ground truth is refused (an index out of range, a non-finite corner)
+    bool evaluate_canonical(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
+                            std::vector<float>* d_model = nullptr, std::string* why = nullptr) {
+        sobfu_amd::IndexedMesh m = get_phi_global_indexed_mesh();
+        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why);
+        if (model) *model = std::move(m);
+        return ok;
+    }
+    bool evaluate_live(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
+                       std::vector<float>* d_model = nullptr, std::string* why = nullptr) {
+        sobfu_amd::IndexedMesh m = get_phi_global_warped_indexed_mesh();
+        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why);
+        if (model) *model = std::move(m);
+        return ok;
     }
     static sobfu_amd::TriangleMesh convert_to_mesh(const kfusion::cuda::DeviceArray<kfusion::cuda::Point>& triangles) {
         sobfu_amd::TriangleMesh m;

@@ -575,6 +575,38 @@ int sobfu_hip_tiled_exchange(sobfu_hip_tiled* t, float* d_field3, int planes, vo
 int sobfu_hip_tiled_self_sendrecv(sobfu_hip_tiled* t, const float* d_src, float* d_dst, size_t n, void* stream);
 int sobfu_hip_tiled_allreduce_max_u32(sobfu_hip_tiled* t, uint32_t* d_buf, size_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mesh distance  (no counterpart in the reference; sobfu_amd/csrc/mesh_distance_kernels.hip)
+ * Exact Euclidean distances from points to an indexed triangle mesh: vertices as n_vertices dense float4 (x, y, z, w; w ignored, 16-byte
+ * aligned like the other point lists), faces as n_triangles x 3 int32.  Per point: dist = the distance to the nearest triangle (fp32 rule:
+ * sobfu_amd/csrc/sobfu_mesh_distance.hpp), tri = the lowest triangle index at that distance, closest = that triangle's closest point
+ * (x, y, z, 1).  The answer is the same bit for bit whichever mode finds it and from run to run.
+ * ---------------------------------------------------------------------------------------------------- */
+/* Host only: the uniform grid over a mesh whose box is bbox = {min x, y, z, max x, y, z} -> origin, cell edge h and dims (<= 128 each;
+ * dims * h covers the box).  cell = 0: cells along the longest extent = clamp(ceil(sqrt(n_triangles) / 4), 1, 128); cell > 0: that edge
+ * (enlarged where it would need more than 128 cells).  SOBFU_E_BADARG: a non-finite or inverted box, a negative count or cell. */
+int sobfu_hip_mesh_grid_plan(const float bbox[6], int n_triangles, float cell, float origin[3], float* h, int dims[3]);
+/* Bytes of the caller-kept workspace of a grid with room for max_refs triangle references (0: invalid dims). */
+size_t sobfu_hip_mesh_grid_workspace_bytes(const int dims[3], int max_refs);
+/* Builds the grid into d_workspace (16-byte aligned): count, scan, fill.  SYNCHRONISES the stream once, after the count: *h_refs = the
+ * references the mesh needs.  SOBFU_E_UNSUPPORTED with *h_refs > max_refs: build again with a workspace of that size.  SOBFU_E_BADARG
+ * (after the synchronisation) for a face index outside [0, n_vertices) or a non-finite corner; a workspace whose build did not return 0
+ * is not marked as built and every query through it answers (+Inf, -1). */
+int sobfu_hip_mesh_grid_build(const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles, const float origin[3], float h,
+                              const int dims[3], void* d_workspace, size_t workspace_bytes, int max_refs, int* h_refs, void* stream);
+#define SOBFU_MESH_DISTANCE_AUTO 0  /* the grid; brute force for meshes of at most 64 triangles */
+#define SOBFU_MESH_DISTANCE_GRID 1
+#define SOBFU_MESH_DISTANCE_BRUTE 2 /* every point against every triangle */
+/* n points (dense float4) against the mesh and plan the workspace was built with (the same arrays, unchanged).  max_dist <= 0 or +Inf:
+ * unlimited; else a point farther than max_dist gets dist = +Inf, tri = -1, closest = (0, 0, 0, 0).  ring_cap: shells of cells a point
+ * may walk before it is finished by brute force (0 = default, 8).  d_closest may be NULL; d_unresolved: n ints of scratch (may be NULL
+ * for SOBFU_MESH_DISTANCE_BRUTE).  No triangles: every point gets (+Inf, -1).  n = 0 succeeds and launches nothing.  Asynchronous. */
+int sobfu_hip_mesh_distance(void* d_workspace, size_t workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                            int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, float max_dist,
+                            int mode, int ring_cap, float* d_dist, int* d_tri, float* d_closest, int* d_unresolved, void* stream);
+/* How many points of the last sobfu_hip_mesh_distance through this workspace hit the ring cap (synchronises the stream). */
+int sobfu_hip_mesh_distance_unresolved(const void* d_workspace, int* h_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ LIB = os.path.join(HERE, "libsobfu_hip.so")
 SOBFU_HPP = os.path.join(INC, "sobfu_amd", "sobfu.hpp")
 DEPTH_IO_HPP = os.path.join(INC, "sobfu_amd", "depth_io.hpp")
 SOBFU_HIP_H = os.path.join(INC, "sobfu_hip.h")
+EVALUATE_HPP = os.path.join(INC, "sobfu_amd", "evaluate.hpp")  # part of sobfu.hpp
 
 
 def _test_src(name: str) -> str:
@@ -25,7 +26,7 @@ def _test_src(name: str) -> str:
 
 def _build(out: str, src: str, deps, linked: bool, force: bool = False, flags=()) -> str:
     """g++ `src` into build/`out` when it is missing or older than `src` / `deps`.  linked: against libsobfu_hip.so and the HIP
-    runtime (the library is then a dependency too); else a stand-alone program with `flags`."""
+    runtime (the library is then a dependency too; `flags` are added); else a stand-alone program with `flags`."""
     out = os.path.join(ROOT, "build", out)
     deps = [src, *deps] + ([LIB] if linked else [])
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
@@ -34,7 +35,7 @@ def _build(out: str, src: str, deps, linked: bool, force: bool = False, flags=()
     if linked:
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__",
                                f"-I{ROCM}/include", f"-I{INC}", src, "-o", out, f"-L{HERE}", "-lsobfu_hip",
-                               f"-L{ROCM}/lib", "-lamdhip64", "-lz", f"-Wl,-rpath,{HERE}", f"-Wl,-rpath,{ROCM}/lib", "-Wl,-rpath,$ORIGIN/../sobfu_amd"])
+                               f"-L{ROCM}/lib", "-lamdhip64", "-lz", f"-Wl,-rpath,{HERE}", f"-Wl,-rpath,{ROCM}/lib", "-Wl,-rpath,$ORIGIN/../sobfu_amd", *flags])
     else:
         subprocess.check_call(["g++", "-O2", "-Wall", f"-I{INC}", src, "-o", out, *flags])
     return out
@@ -42,7 +43,7 @@ def _build(out: str, src: str, deps, linked: bool, force: bool = False, flags=()
 
 def build_app(force: bool = False) -> str:
     """apps/sobfu_headless.cpp: the headless frame-loop app over the shells."""
-    return _build("sobfu_headless", os.path.join(ROOT, "apps", "sobfu_headless.cpp"), [SOBFU_HPP, DEPTH_IO_HPP], True, force)
+    return _build("sobfu_headless", os.path.join(ROOT, "apps", "sobfu_headless.cpp"), [SOBFU_HPP, EVALUATE_HPP, DEPTH_IO_HPP], True, force)
 
 
 def build_io_tool(force: bool = False) -> str:
@@ -88,11 +89,18 @@ def build_mesh_warp_tool(force: bool = False) -> str:
     return _build("mesh_warp_tool", _test_src("mesh_warp_tool.cpp"), [SOBFU_HPP, DEPTH_IO_HPP], True, force)
 
 
+def build_mesh_eval_tool(force: bool = False) -> str:
+    """tests/cpp/mesh_eval_tool.cpp: read_ply, the point-triangle rule on the CPU (-ffp-contract=off, as the kernels are built) and
+    compare_meshes (include/sobfu_amd/evaluate.hpp, sobfu_amd/csrc/sobfu_mesh_distance.hpp)."""
+    deps = [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H, os.path.join(CSRC, "sobfu_mesh_distance.hpp")]
+    return _build("mesh_eval_tool", _test_src("mesh_eval_tool.cpp"), deps, True, force, [f"-I{CSRC}", "-ffp-contract=off"])
+
+
 def build_host(force: bool = False) -> str:
     for build in (build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
-                  build_icp_tool, build_mesh_warp_tool):
+                  build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool):
         build(force)
-    return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, SOBFU_HIP_H], True, force)
+    return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H], True, force)
 
 
 if __name__ == "__main__":

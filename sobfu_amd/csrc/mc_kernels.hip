@@ -17,6 +17,7 @@
 #include "sobfu_device.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
+#include "sobfu_scan.hpp"
 
 using namespace sobfu_hip;
 
@@ -51,31 +52,6 @@ SOBFU_DEV int cube_index(const float2* __restrict__ vol, const Dims& d, int x, i
     return cube;
 }
 
-constexpr int kBlock = 256, kItems = 8, kChunk = kBlock * kItems;  // cells per workgroup
-
-// block-wide exclusive prefix of one int per lane; returns the prefix, *total = block sum (valid in every lane)
-SOBFU_DEV int block_exclusive(int v, int* total, int* s_wave /* kBlock / 64 + 1 */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int n = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += n;
-    }
-    __syncthreads();  // s_wave may still be read from the previous call
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        int t = s_wave[w];
-        if (w < wave) base += t;
-        sum += t;
-    }
-    *total = sum;
-    return base + incl - v;
-}
-
 // pass 1: vertex count of every cell (uint8 scratch) + per-workgroup number of active cells
 __global__ void __launch_bounds__(kBlock) classify_kernel(const float2* __restrict__ vol, Dims d, uint8_t* __restrict__ nv_out,
                                                           int* __restrict__ block_cnt) {
@@ -102,33 +78,6 @@ __global__ void __launch_bounds__(kBlock) classify_kernel(const float2* __restri
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
 }
 
-// pass 2: exclusive scan of n ints by ONE workgroup (n = number of workgroups of pass 1 / pass 3: a few thousand)
-SOBFU_DEV void scan_blocks(int* __restrict__ v, int n, int* __restrict__ total_out) {
-    __shared__ int s_wave[17];
-    __shared__ int s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int b = 0; b < n; b += 1024) {
-        const int i = b + threadIdx.x, x = i < n ? v[i] : 0;
-        int incl = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int base = s_carry;
-        for (int w = 0; w < wave; ++w) base += s_wave[w];
-        if (i < n) v[i] = base + incl - x;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = base + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = s_carry;
-}
-__global__ void __launch_bounds__(1024) scan_blocks_kernel(int* __restrict__ v, int n, int* __restrict__ total_out) { scan_blocks(v, n, total_out); }
 // the indexed path's three per-workgroup arrays (consecutive, n ints each; totals consecutive): one workgroup per array
 __global__ void __launch_bounds__(1024) scan_blocks3_kernel(int* __restrict__ v, int n, int* __restrict__ totals) {
     scan_blocks(v + (size_t) blockIdx.x * n, n, totals + blockIdx.x);
@@ -150,33 +99,6 @@ __global__ void __launch_bounds__(kBlock) compact_kernel(const uint8_t* __restri
             voxel_idx[pos] = (int) i;
             voxel_nv[pos]  = nv;
         }
-        run += total;
-    }
-}
-
-// generic int exclusive scan, same three passes: sums of kChunk-element blocks, scan of the sums, local scan + offset
-__global__ void __launch_bounds__(kBlock) chunk_sum_kernel(const int* __restrict__ in, int n, int* __restrict__ block_sum) {
-    __shared__ int s_wave[kBlock / 64 + 1];
-    int s = 0;
-    for (int it = 0; it < kItems; ++it) {
-        const size_t i = (size_t) blockIdx.x * kChunk + (size_t) it * kBlock + threadIdx.x;
-        s += i < (size_t) n ? in[i] : 0;
-    }
-    int total;
-    block_exclusive(s, &total, s_wave);
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(kBlock) chunk_scan_kernel(const int* __restrict__ in, int n, const int* __restrict__ block_off,
-                                                            int* __restrict__ out) {
-    __shared__ int s_wave[kBlock / 64 + 1];
-    int run = block_off[blockIdx.x];
-#pragma unroll 1
-    for (int it = 0; it < kItems; ++it) {
-        const size_t i = (size_t) blockIdx.x * kChunk + (size_t) it * kBlock + threadIdx.x;
-        const int x = i < (size_t) n ? in[i] : 0;
-        int total;
-        const int pos = run + block_exclusive(x, &total, s_wave);
-        if (i < (size_t) n) out[i] = pos;
         run += total;
     }
 }
@@ -240,11 +162,6 @@ __global__ void __launch_bounds__(256) triangles_kernel(const float2* __restrict
             out_n[first + i + k] = n;
         }
     }
-}
-
-int scan_in_place_sums(int* d_sums, int nb, int* d_total, hipStream_t st) {
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, d_sums, nb, d_total);
-    return (int) hipGetLastError();
 }
 
 // ---- indexed (welded) meshes: one vertex per cut grid edge, shared by every triangle that uses it ----------------------------------

@@ -32,6 +32,16 @@ def affine_inv(a):
     return r
 
 
+def transform_points(points, pose):
+    """(n, 4) float32 points through a 4 x 4 transform, in float32: ((m0 x + m1 y) + m2 z) + t per row; w = 1 (the order of
+    sobfu_amd::transform_points in include/sobfu_amd/evaluate.hpp)"""
+    p, m = np.asarray(points, np.float32), np.asarray(pose, np.float32).reshape(4, 4)
+    out = np.ones((len(p), 4), np.float32)
+    for i in range(3):
+        out[:, i] = ((m[i, 0] * p[:, 0] + m[i, 1] * p[:, 1]) + m[i, 2] * p[:, 2]) + m[i, 3]
+    return out
+
+
 class SobFusion:
     """params: a dict as sobfu_amd.params.read_ini returns (dims, vs, trunc, eta, max_weight, intr, R, t, start_frame, bilateral,
     trunc_depth, max_iter, max_update_norm, s, lam, alpha, w_reg; track_camera and the icp_* settings for camera tracking)."""
@@ -179,6 +189,30 @@ class SobFusion:
         if d.size == 0:
             return dict(valid=0, mean_abs=0.0, rms=0.0, max=0.0)
         return dict(valid=int(d.size), mean_abs=float(d.mean()), rms=float(np.sqrt((d * d).mean())), max=float(d.max()))
+
+    def evaluate(self, gt_vertices, gt_faces, which="canonical", max_dist=None, pose=None, return_meshes=False):
+        """The reconstruction against a ground-truth mesh (vertices (V, 4), faces (F, 3)) in the frame of the meshes the app writes
+        (marching-cubes vertices, (x, -y, -z)): exact vertex-to-surface distances both ways (sobfu_amd.evaluate.compare_meshes; a = the
+        model, b = the ground truth), in metres.  which: "canonical" meshes phi_global (ops.marching_cubes_indexed at the volume pose),
+        "live" carries that mesh through psi (warp_to_live).  pose: a 4 x 4 transform applied to the ground truth first (float32, row by
+        row: (r0 x + r1 y) + r2 z + t).  Reads the volumes only.  return_meshes: -> (dict, model vertices, model faces, gt vertices)."""
+        import torch
+
+        from . import evaluate as E
+
+        if which not in ("canonical", "live"):
+            raise ValueError(f"which is 'canonical' or 'live', not {which!r}")
+        if self.phi_global is None:
+            raise RuntimeError("phi_global does not exist before the first frame")
+        P = self.P
+        v, _, f = self.ops.marching_cubes_indexed(self.phi_global, P["size"], P["R"], P["t"])
+        if which == "live":
+            v = self.warp_to_live(v)
+        gv = E.device_tensor(gt_vertices, torch.float32)
+        if pose is not None:
+            gv = E.device_tensor(transform_points(gv.cpu().numpy(), pose), torch.float32)
+        r = E.compare_meshes(v, f, gv, gt_faces, max_dist)
+        return (r, v, f, gv) if return_meshes else r
 
     def close(self):
         if self.solver is not None:

@@ -626,6 +626,87 @@ def sample_tsdf(vol, voxel_size, R, t, points, mc_vertices=False, out=None):
     return out
 
 
+# ---- exact point-to-mesh distances (sobfu_amd/csrc/mesh_distance_kernels.hip) ------------------------------------------------------------
+_MESH_MODES = {"auto": 0, "grid": 1, "brute": 2}
+
+
+def mesh_grid_plan(bbox, n_triangles, cell=None):
+    """The uniform grid over a mesh with this bounding box (min x, y, z, max x, y, z) -> origin (3,) float32, h, dims (3,) (host only)"""
+    origin, h, dims = _F3(), C.c_float(0), (C.c_int * 3)()
+    check(_lib.lib().sobfu_hip_mesh_grid_plan((C.c_float * 6)(*[float(v) for v in bbox]), C.c_int(int(n_triangles)), _f(cell or 0.0), origin,
+                                              C.byref(h), dims), "mesh_grid_plan")
+    return np.array(list(origin), np.float32), float(h.value), np.array(list(dims), np.int32)
+
+
+class TriangleGrid:
+    """A uniform grid over an indexed triangle mesh -- vertices (V, 4) float32, faces (F, 3) int32, GPU tensors that must stay unchanged
+    while the grid is used -- for exact nearest-triangle queries.  cell: the cell edge (None: the plan's default).  Owns the workspace.
+    A face index out of range or a non-finite corner raises HipError (SOBFU_E_BADARG) here: there is no grid to query then."""
+
+    def __init__(self, vertices, faces, cell=None):
+        L = _lib.lib()
+        L.sobfu_hip_mesh_grid_workspace_bytes.restype = C.c_size_t
+        _point_list(vertices, "vertices")
+        if not (faces.dim() == 2 and faces.shape[1] == 3):
+            raise ValueError(f"expected (F, 3) int32 faces, got {tuple(faces.shape)}")
+        self.vertices, self.faces = vertices, faces
+        self.n_vertices, self.n_triangles = int(vertices.shape[0]), int(faces.shape[0])
+        xyz = vertices[:, :3]
+        xyz = xyz[torch.isfinite(xyz).all(1)]  # a non-finite vertex is the build's to refuse when a face uses it
+        if xyz.shape[0] and self.n_triangles:
+            bbox = torch.cat([xyz.amin(0), xyz.amax(0)]).cpu().numpy()
+        else:
+            bbox = np.zeros(6, np.float32)
+        self.origin, self.h, dims = mesh_grid_plan(bbox, self.n_triangles, cell)
+        self.dims = tuple(int(d) for d in dims)
+        self._plan = (_F3(*[float(v) for v in self.origin]), _f(self.h), (C.c_int * 3)(*[int(d) for d in self.dims]))
+        self.unresolved_buffer = None
+        refs, max_refs = C.c_int(0), 8 * self.n_triangles + 1024
+        while True:
+            nbytes = int(L.sobfu_hip_mesh_grid_workspace_bytes(self._plan[2], C.c_int(max_refs)))
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=vertices.device)
+            rc = L.sobfu_hip_mesh_grid_build(*self._mesh(), *self._plan, *_ws(self.workspace), C.c_int(max_refs), C.byref(refs), _stream())
+            if rc == -3 and refs.value > max_refs:  # SOBFU_E_UNSUPPORTED: the references need more room
+                max_refs = refs.value
+                continue
+            check(rc, "mesh_grid_build")
+            break
+        self.references = refs.value
+
+    def _mesh(self):
+        return (_ptr(self.vertices) if self.n_vertices else None, C.c_int(self.n_vertices),
+                _ptr(self.faces, torch.int32) if self.n_triangles else None, C.c_int(self.n_triangles))
+
+    def query(self, points, max_dist=None, closest=False, mode="auto", ring_cap=None):
+        """(n, 4) float32 points -> dist (n,) float32, tri (n,) int32 [, closest (n, 4) float32]: the distance to the nearest triangle, the
+        lowest triangle index at that distance and its closest point (x, y, z, 1).  max_dist: farther points get (+Inf, -1, zeros).
+        mode "auto" | "grid" | "brute" and ring_cap (shells walked before a point goes to brute force) never change the answer."""
+        if mode not in _MESH_MODES:
+            raise ValueError(f"unknown mode {mode!r}")
+        n = int(points.shape[0])
+        dist = torch.empty(n, dtype=torch.float32, device=points.device)
+        tri = torch.empty(n, dtype=torch.int32, device=points.device)
+        cl = torch.empty((n, 4), dtype=torch.float32, device=points.device) if closest else None
+        if n:
+            self.unresolved_buffer = torch.empty(n, dtype=torch.int32, device=points.device)
+            check(_lib.lib().sobfu_hip_mesh_distance(*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(points, "points"), C.c_int(n),
+                                                     _f(0.0 if max_dist is None else max_dist), C.c_int(_MESH_MODES[mode]), C.c_int(int(ring_cap or 0)),
+                                                     _ptr(dist), _ptr(tri, torch.int32), None if cl is None else _ptr(cl),
+                                                     _ptr(self.unresolved_buffer, torch.int32), _stream()), "mesh_distance")
+        return (dist, tri, cl) if closest else (dist, tri)
+
+    def unresolved(self):
+        """how many points of the last query hit the ring cap and were finished by brute force (synchronises)"""
+        n = C.c_int(0)
+        check(_lib.lib().sobfu_hip_mesh_distance_unresolved(_ws(self.workspace)[0], C.byref(n), _stream()), "mesh_distance_unresolved")
+        return n.value
+
+
+def mesh_distance(points, vertices, faces, max_dist=None, closest=False, mode="auto", ring_cap=None, cell=None):
+    """TriangleGrid(vertices, faces, cell).query(points, ...) in one call"""
+    return TriangleGrid(vertices, faces, cell).query(points, max_dist, closest, mode, ring_cap)
+
+
 # ---- camera tracking (sobfu_amd/csrc/icp_kernels.hip): projective ICP and its image pyramids -------------------------------------
 class IcpLevel(C.Structure):
     """sobfu_hip_icp_level"""
