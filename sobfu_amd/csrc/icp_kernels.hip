@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(256) resize_depth_normals_kernel(const uint16_
     const int d10 = row_ptr(ds, dsstep, ys + 1)[xs], d11 = row_ptr(ds, dsstep, ys + 1)[xs + 1];
     uint16_t d = 0;
     float4 n = nan4();
-    if (d00 * d01 != 0 && d10 * d11 != 0) {
+    if (d00 != 0 && d01 != 0 && d10 != 0 && d11 != 0) {  // not d00 * d01: the product of two depths >= 46341 overflows int
         d = (uint16_t) ((d00 + d01 + d10 + d11) / 4);
         n = avg4(row_ptr(ns, nsstep, ys)[xs], row_ptr(ns, nsstep, ys)[xs + 1], row_ptr(ns, nsstep, ys + 1)[xs], row_ptr(ns, nsstep, ys + 1)[xs + 1]);
     }

@@ -750,21 +750,26 @@ def normals_mask_depth(depth, intr, normals=None):
     return normals
 
 
-def resize_depth_normals(depth, normals):
-    """resizeDepthNormals: half resolution of (depth, normals)"""
+def resize_depth_normals(depth, normals, depth_out=None, normals_out=None):
+    """resizeDepthNormals: half resolution of (depth, normals); `depth_out` / `normals_out` may be given to write into existing buffers"""
     rows, cols = depth.shape
-    d = torch.empty((rows // 2, cols // 2), dtype=depth.dtype, device=depth.device)
-    n = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=depth.device)
+    d = torch.empty((rows // 2, cols // 2), dtype=depth.dtype, device=depth.device) if depth_out is None else depth_out
+    n = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=depth.device) if normals_out is None else normals_out
+    if tuple(d.shape) != (rows // 2, cols // 2) or tuple(n.shape) != (rows // 2, cols // 2, 4):
+        raise ValueError(f"the outputs of a ({rows}, {cols}) image must be ({rows // 2}, {cols // 2}) and ({rows // 2}, {cols // 2}, 4)")
     check(_lib.lib().sobfu_hip_resize_depth_normals(*_depth_image(depth), *_image_ptr(normals, torch.float32, 4), C.c_int(rows), C.c_int(cols),
                                                     *_depth_image(d), *_image_ptr(n, torch.float32, 4), _stream()), "resize_depth_normals")
     return d, n
 
 
-def resize_points_normals(points, normals):
-    """resizePointsNormals: half resolution of (points, normals); an output pixel is valid iff its four source pixels are"""
+def resize_points_normals(points, normals, points_out=None, normals_out=None):
+    """resizePointsNormals: half resolution of (points, normals); an output pixel is valid iff its four source pixels are.
+    `points_out` / `normals_out` may be given to write into existing buffers"""
     rows, cols = points.shape[:2]
-    p = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=points.device)
-    n = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=points.device)
+    p = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=points.device) if points_out is None else points_out
+    n = torch.empty((rows // 2, cols // 2, 4), dtype=torch.float32, device=points.device) if normals_out is None else normals_out
+    if tuple(p.shape) != (rows // 2, cols // 2, 4) or tuple(n.shape) != (rows // 2, cols // 2, 4):
+        raise ValueError(f"the outputs of a ({rows}, {cols}) image must be ({rows // 2}, {cols // 2}, 4)")
     check(_lib.lib().sobfu_hip_resize_points_normals(*_image_ptr(points, torch.float32, 4), *_image_ptr(normals, torch.float32, 4), C.c_int(rows),
                                                      C.c_int(cols), *_image_ptr(p, torch.float32, 4), *_image_ptr(n, torch.float32, 4), _stream()),
           "resize_points_normals")
@@ -834,16 +839,22 @@ def icp_estimate(intr, curr, ncurr, prev, nprev, dist_thres=0.1, angle_thres=np.
 
 def icp_step(level_index, intr, curr, ncurr, prev, nprev, aff, dist_thres=0.1, angle_thres=np.deg2rad(20.0), codes=False, workspace=None):
     """One correspondence + reduction pass of pyramid level `level_index` (base intrinsics intr) at the 4 x 4 pose `aff` ->
-    (A 6 x 6, b (6,), inlier count, rms residual, code map (rows, cols) uint8 or None), float64 numpy"""
+    (A 6 x 6, b (6,), inlier count, rms residual, code map (rows, cols) uint8 or None), float64 numpy.  `codes` may also be a
+    (rows, cols) uint8 tensor on the GPU with contiguous rows (any row stride) to write the code map into."""
     lvl, depth = _icp_level(curr, ncurr, prev, nprev)
     dev = curr.device
     aff_d = torch.as_tensor(np.asarray(aff, np.float32).reshape(16), device=dev)
     ws = torch.empty(int(_lib.lib().sobfu_hip_icp_workspace_bytes()), dtype=torch.uint8, device=dev) if workspace is None else workspace
     sums = torch.empty(29, dtype=torch.float64, device=dev)
-    cm = torch.empty(tuple(curr.shape[:2]), dtype=torch.uint8, device=dev) if codes else None
+    if isinstance(codes, torch.Tensor):
+        cm = codes
+        if not (cm.is_cuda and cm.dtype == torch.uint8 and tuple(cm.shape) == tuple(curr.shape[:2]) and cm.stride(1) == 1):
+            raise ValueError("the code map must be a (rows, cols) uint8 tensor on the GPU with contiguous rows")
+    else:
+        cm = torch.empty(tuple(curr.shape[:2]), dtype=torch.uint8, device=dev) if codes else None
     check(_lib.lib().sobfu_hip_icp_step(C.byref(lvl), C.c_int(int(level_index)), C.c_int(1 if depth else 0), _f(intr[0]), _f(intr[1]), _f(intr[2]),
                                         _f(intr[3]), _f(dist_thres), _f(angle_thres), _ptr(aff_d), _ptr(ws, torch.uint8), C.c_size_t(ws.numel()),
-                                        _ptr(sums, torch.float64), None if cm is None else _ptr(cm, torch.uint8),
+                                        _ptr(sums, torch.float64), None if cm is None else C.c_void_p(cm.data_ptr()),
                                         C.c_int(0 if cm is None else cm.stride(0)), _stream()), "icp_step")
     s = sums.cpu().numpy()
     A = np.zeros((6, 6))

@@ -167,9 +167,10 @@ def resize_points_normals(points, normals):
 
 
 # ---- ICP ------------------------------------------------------------------------------------------------------------------------
-def correspond(level, intr, curr, ncurr, prev, nprev, aff, dist, angle):
+def correspond(level, intr, curr, ncurr, prev, nprev, aff, dist, angle, unmasked=False):
     """-> (codes (rows, cols) uint8, rows (rows, cols, 7) float32 (zero where code != 0), margins (rows, cols): the smallest relative
-    distance of a decision of the pixel from its threshold)"""
+    distance of a decision of the pixel from its threshold); with unmasked also the rows of every pixel, whatever its code (the row a
+    pixel would contribute were it an inlier; not finite where the pixel or its target is invalid)"""
     depth = np.asarray(curr).ndim == 2
     li = level_intr(intr, level)
     fx, fy, cx, cy = li[:4]
@@ -228,8 +229,9 @@ def correspond(level, intr, curr, ncurr, prev, nprev, aff, dist, angle):
         margin = np.where(live, np.minimum(margin, np.abs(cosv - mc)), margin)
         r = (nd[0] * (d[0] - s[0]) + nd[1] * (d[1] - s[1])) + nd[2] * (d[2] - s[2])
         row = np.stack([s[1] * nd[2] - s[2] * nd[1], s[2] * nd[0] - s[0] * nd[2], s[0] * nd[1] - s[1] * nd[0], nd[0], nd[1], nd[2], r], -1)
+    every = row.astype(np.float32)
     row = np.where((codes == 0)[..., None], row, 0).astype(np.float32)
-    return codes, row, margin
+    return (codes, row, margin, every) if unmasked else (codes, row, margin)
 
 
 def sums(row, codes):

@@ -199,7 +199,15 @@ def run_world_direct(dims, grid, psi0, pg, pn, n_iters, thr, stepped, solves=1, 
     tiled.NativeTiledSolver.connect_local(solvers)
     torch.cuda.synchronize()
     pn_d = torch.from_numpy(pn).cuda()
-    streams = [torch.cuda.Stream() for _ in range(world)]
+    if stepped:
+        streams = [torch.cuda.Stream() for _ in range(world)]
+    else:
+        # in-kernel waits live: a rank whose kernels sit behind a waiting peer's in the same hardware queue never raises its flag, and
+        # the peer runs into its deadline.  The runtime deals a process's few hardware queues to the streams of one priority by use
+        # count, so two of them can share a queue (it depends on what the process did before); it pools the queues by priority, so
+        # streams of different priorities never share one.
+        assert world == 2
+        streams = [torch.cuda.Stream(priority=0), torch.cuda.Stream(priority=-1)]
     state = []
     for r, s in enumerate(solvers):
         L = s.layout
