@@ -8,6 +8,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
+#include <type_traits>
 
 #include "sobfu_hip.h"
 
@@ -29,6 +31,39 @@
     } while (0)
 
 namespace sobfu_hip {
+
+// What a C-ABI handle holds, as members that release it themselves: unique_ptr with stateless deleters (an empty member releases
+// nothing; a handle's members go in the reverse order of their declaration).  hipEvent_t / hipStream_t are pointer types already.
+struct DeviceFree {
+    void operator()(void* p) const { (void) hipFree(p); }
+};
+struct PinnedFree {
+    void operator()(void* p) const { (void) hipHostFree(p); }
+};
+struct EventDestroy {
+    void operator()(hipEvent_t e) const { (void) hipEventDestroy(e); }
+};
+struct StreamDestroy {
+    void operator()(hipStream_t s) const { (void) hipStreamDestroy(s); }
+};
+template <class T> using DevicePtr = std::unique_ptr<T, DeviceFree>;
+template <class T> using PinnedPtr = std::unique_ptr<T, PinnedFree>;
+using EventPtr  = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
+using StreamPtr = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
+// hipMalloc into an owner: what it held is released FIRST, so a failed allocation leaves it empty
+template <class T> inline hipError_t device_alloc(DevicePtr<T>& out, size_t bytes) {
+    out.reset();
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) out.reset(static_cast<T*>(p));
+    return e;
+}
+inline hipError_t event_create(EventPtr& out, unsigned flags) {
+    hipEvent_t e = nullptr;
+    const hipError_t rc = hipEventCreateWithFlags(&e, flags);
+    if (rc == hipSuccess) out.reset(e);
+    return rc;
+}
 
 // the pointer and the row size of its pitched image (bytes; 0 for a dense array) are multiples of `to`
 inline bool aligned(const void* p, long long step, int to) { return ((uintptr_t) p % (uintptr_t) to) == 0 && step % to == 0; }

@@ -16,6 +16,21 @@ namespace sobfu_hip {
 
 constexpr int kHalo = 4;
 
+// The bits of SOBFU_TILED_DEBUG_SKIP (read once, when a handle is created): pieces of an iteration left out, for timing experiments
+// only -- the results are wrong.  The first seven are read by the loop (tiled_capi.hip), the last three by push_boxes below.
+enum DebugSkip : int {
+    kSkipPushBoxes    = 1,    // pass A of the tile path launches the whole owned block alone, without its push boxes
+    kSkipShells       = 2,    // pass B of the tile path without its thin x / y shells
+    kSkipPassA        = 4,    // no pass A (tile path)
+    kSkipPassB        = 8,    // no pass B (tile path)
+    kSkipOwnedB       = 16,   // pass B without the owned block
+    kSkipYShells      = 32,   // pass B without the y shells
+    kSkipXShells      = 64,   // pass B without the x shells
+    kSkipThinPush     = 128,  // no thin push boxes (x faces, edges, corners)
+    kSkipMarchedPush  = 256,  // no marched push boxes (y / z faces)
+    kMarchedHomeOnly  = 512,  // the marched push boxes store at home only
+};
+
 // The layout of ANY rank's tile (a rank also needs its neighbours': where their halo cells sit in their arrays).
 // tile grid P, the rank's tile coordinates c; per axis: owned global range [g0, g1), halo cells lo / hi, local extent L,
 // owned local range [o0, o1), global coordinate `base` of local cell 0
@@ -193,8 +208,8 @@ inline PushBoxes push_boxes(const TileLay& lay, const TileMsgs& mm, float* sendb
                 b.local_z0 = iz0; b.local_z1 = iz1;
             }
             if (z_inplace && m.dir[0] == 0 && m.dir[1] == 0 && m.dir[2] != 0) continue;
-            if ((!march && (debug_skip & 128)) || (march && (debug_skip & 256))) continue;  // timing experiments: without the thin / the marched push boxes
-            if (march && (debug_skip & 512)) b.push_y1 = b.push_y0;  // timing experiments: the marched boxes keep their cells at home only
+            if ((!march && (debug_skip & kSkipThinPush)) || (march && (debug_skip & kSkipMarchedPush))) continue;
+            if (march && (debug_skip & kMarchedHomeOnly)) b.push_y1 = b.push_y0;
             float* const* dst = h ? dst1 : dst0;
             if (dst && dst[i]) {  // the matching message of the peer: direction -dir; its receive box is where these cells live there
                 const TileLay& pl = peers[i];

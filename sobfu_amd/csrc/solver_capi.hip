@@ -22,6 +22,8 @@
 
 namespace {
 
+using sobfu_hip::DevicePtr;
+using sobfu_hip::EventPtr;
 using sobfu_hip::kSlots;
 using sobfu_hip::slots_to_norm;
 constexpr int kCheckEvery = 32;
@@ -34,21 +36,21 @@ struct sobfu_hip_solver {
     size_t N = 0;
     sobfu_hip_solver_params p{};
     float taps[7]{};
-    // device workspace
-    float* nabla_U     = nullptr;  // 16 B/voxel
-    float* updates     = nullptr;  // 16 B/voxel, allocated on first need (verbosity > 0 or keep_updates)
+    // device workspace (the members release what they hold)
+    DevicePtr<float> nabla_U;  // 16 B/voxel
+    DevicePtr<float> updates;  // 16 B/voxel, allocated on first need (verbosity > 0 or keep_updates)
     // compact iteration state (12-byte psi, 4-byte tsdf-only phi_global / phi_n / phi_n o psi), allocated on first
     // quiet solve; nabla_U doubles as the 12-byte nabla_U buffer
-    float* c_psi = nullptr;  // 12 B/voxel
-    float* c_f   = nullptr;  //  4 B/voxel  (phi_n o psi).tsdf
-    float* c_g   = nullptr;  //  4 B/voxel  phi_global.tsdf
-    float* c_n   = nullptr;  //  4 B/voxel  phi_n.tsdf
+    DevicePtr<float> c_psi;  // 12 B/voxel
+    DevicePtr<float> c_f;    //  4 B/voxel  (phi_n o psi).tsdf
+    DevicePtr<float> c_g;    //  4 B/voxel  phi_global.tsdf
+    DevicePtr<float> c_n;    //  4 B/voxel  phi_n.tsdf
     bool compact = true;
-    uint32_t* slots    = nullptr;  // (slots_iters + 1) x 256
-    uint32_t* h_rows   = nullptr;  // pinned mirror of the slot rows for the non-blocking convergence poll
+    DevicePtr<uint32_t> slots;                  // (slots_iters + 1) x 256
+    sobfu_hip::PinnedPtr<uint32_t> h_rows;      // pinned mirror of the slot rows for the non-blocking convergence poll
     int h_rows_iters   = 0;
-    hipEvent_t ev_chk  = nullptr;
-    void* red_scratch  = nullptr;  // 65536 x 8 B block partials
+    EventPtr ev_chk;
+    DevicePtr<void> red_scratch;  // 65536 x 8 B block partials
     int slots_iters    = 0;
     bool keep_updates  = false;
     sobfu_hip_log_fn log_fn = nullptr;
@@ -57,7 +59,7 @@ struct sobfu_hip_solver {
     size_t bytes            = 0;
     // optional per-kernel timing (HIP events on the solver's stream around the launches of every prof_stride-th iteration)
     int prof_stride = 0;
-    std::vector<hipEvent_t> events;
+    std::vector<EventPtr> events;
     double ms_a = 0, ms_b = 0;
     int prof_launches = 0, prof_pending = 0;
     // an open quiet solve (session_begin .. session_end)
@@ -97,12 +99,9 @@ std::string fmt_g(float v) {  // std::cout default float formatting (%g, precisi
 
 int ensure_slots(sobfu_hip_solver* s, int iters) {
     if (iters <= s->slots_iters) return 0;
-    if (s->slots) {
-        SOBFU_HIP_TRY(hipFree(s->slots));
-        s->bytes -= (size_t) (s->slots_iters + 1) * kSlots * 4;
-    }
-    s->slots = nullptr;
-    SOBFU_HIP_TRY(hipMalloc((void**) &s->slots, (size_t) (iters + 1) * kSlots * 4));
+    if (s->slots) s->bytes -= (size_t) (s->slots_iters + 1) * kSlots * 4;
+    s->slots_iters = 0;
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->slots, (size_t) (iters + 1) * kSlots * 4));
     s->slots_iters = iters;
     s->bytes += (size_t) (iters + 1) * kSlots * 4;
     return 0;
@@ -111,28 +110,30 @@ int ensure_slots(sobfu_hip_solver* s, int iters) {
 // pinned host mirror + event for the convergence poll (rows are copied asynchronously; the host never drains the stream
 // just to look at them)
 int ensure_poll(sobfu_hip_solver* s, int iters) {
-    if (!s->ev_chk) SOBFU_HIP_TRY(hipEventCreateWithFlags(&s->ev_chk, hipEventDisableTiming));
+    if (!s->ev_chk) SOBFU_HIP_TRY(sobfu_hip::event_create(s->ev_chk, hipEventDisableTiming));
     if (iters <= s->h_rows_iters) return 0;
-    if (s->h_rows) SOBFU_HIP_TRY(hipHostFree(s->h_rows));
-    s->h_rows = nullptr;
-    SOBFU_HIP_TRY(hipHostMalloc((void**) &s->h_rows, (size_t) iters * kSlots * 4, hipHostMallocDefault));
+    s->h_rows.reset();
+    s->h_rows_iters = 0;
+    void* h = nullptr;
+    SOBFU_HIP_TRY(hipHostMalloc(&h, (size_t) iters * kSlots * 4, hipHostMallocDefault));
+    s->h_rows.reset((uint32_t*) h);
     s->h_rows_iters = iters;
     return 0;
 }
 
 int ensure_compact(sobfu_hip_solver* s) {
     if (s->c_psi) return 0;
-    SOBFU_HIP_TRY(hipMalloc((void**) &s->c_psi, s->N * 12));
-    SOBFU_HIP_TRY(hipMalloc((void**) &s->c_f, s->N * 4));
-    SOBFU_HIP_TRY(hipMalloc((void**) &s->c_g, s->N * 4));
-    SOBFU_HIP_TRY(hipMalloc((void**) &s->c_n, s->N * 4));
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->c_psi, s->N * 12));
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->c_f, s->N * 4));
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->c_g, s->N * 4));
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->c_n, s->N * 4));
     s->bytes += s->N * 24;
     return 0;
 }
 
 int ensure_updates(sobfu_hip_solver* s) {
     if (s->updates) return 0;
-    SOBFU_HIP_TRY(hipMalloc((void**) &s->updates, s->N * 16));
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->updates, s->N * 16));
     s->bytes += s->N * 16;
     return 0;
 }
@@ -151,9 +152,9 @@ int set_params(sobfu_hip_solver* s, const sobfu_hip_solver_params* p) {
 
 int ensure_events(sobfu_hip_solver* s, size_t n) {
     while (s->events.size() < n) {
-        hipEvent_t e;
-        SOBFU_HIP_TRY(hipEventCreate(&e));
-        s->events.push_back(e);
+        EventPtr e;
+        SOBFU_HIP_TRY(sobfu_hip::event_create(e, hipEventDefault));
+        s->events.push_back(std::move(e));
     }
     return 0;
 }
@@ -176,18 +177,18 @@ int session_begin_impl(sobfu_hip_solver* s, const float* pg, const float* pn, fl
     if (!q.compact) SOBFU_TRY(sobfu_hip_apply(pn, pnp, psi, X, Y, Z, st));  // solver.cu:106
     if (cap <= 0) return 0;
     SOBFU_TRY(ensure_slots(s, cap));
-    SOBFU_HIP_TRY(hipMemsetAsync(s->slots, 0, (size_t) (cap + 1) * kSlots * 4, st));
+    SOBFU_HIP_TRY(hipMemsetAsync(s->slots.get(), 0, (size_t) (cap + 1) * kSlots * 4, st));
     if (s->keep_updates) {
         SOBFU_TRY(ensure_updates(s));
-        q.upd = s->updates;
+        q.upd = s->updates.get();
     }
     // compact mode: iterate on private 12-byte psi / nabla_U and tsdf-only TSDF copies; the API buffers are rebuilt by
     // session_end (psi.xyz written back, phi_n o psi = apply(phi_n, psi) once) -- same values as iterating in place
     q.it_pnp = pnp; q.it_pg = pg; q.it_pn = pn; q.it_psi = psi; q.it_out = pnp;
     if (q.compact) {
         SOBFU_TRY(ensure_compact(s));
-        SOBFU_TRY(sobfu_hip::launch_compact_enter(psi, pg, pn, s->c_psi, s->c_g, s->c_n, s->c_f, X, Y, Z, st));  // incl. solver.cu:106
-        q.it_pnp = s->c_f; q.it_pg = s->c_g; q.it_pn = s->c_n; q.it_psi = s->c_psi; q.it_out = s->c_f;
+        SOBFU_TRY(sobfu_hip::launch_compact_enter(psi, pg, pn, s->c_psi.get(), s->c_g.get(), s->c_n.get(), s->c_f.get(), X, Y, Z, st));  // incl. solver.cu:106
+        q.it_pnp = s->c_f.get(); q.it_pg = s->c_g.get(); q.it_pn = s->c_n.get(); q.it_psi = s->c_psi.get(); q.it_out = s->c_f.get();
         // quiet solves of big grids: pass A warps phi_n itself and pass B stores no phi_n o psi (c_f is then not kept current, so
         // the verbose loop, whose energies read it, and solves that keep `updates` stay on the F stream; session_end rebuilds the
         // caller's phi_n o psi from psi either way)
@@ -210,7 +211,7 @@ int session_begin(sobfu_hip_solver* s, const float* pg, const float* pn, float* 
 void session_examine(sobfu_hip_solver* s, int upto, float* per_iter) {
     sobfu_hip_solver::Session& q = s->q;
     for (int k = q.checked; k < upto && !q.converged; ++k) {
-        const float v = slots_to_norm(s->h_rows + (size_t) k * kSlots);
+        const float v = slots_to_norm(s->h_rows.get() + (size_t) k * kSlots);
         if (per_iter) per_iter[k] = v;
         q.last_norm = v;
         q.done = k + 1;
@@ -228,31 +229,31 @@ int session_enqueue(sobfu_hip_solver* s, int n, bool poll, float* per_iter, hipS
     const int last = q.launched + n;
     sobfu_hip::PassALaunch A;
     sobfu_hip::set_whole_grid(A, X, Y, Z);
-    A.pnp = q.warp ? q.it_pn : q.it_pnp; A.pg = q.it_pg; A.psi = q.it_psi; A.nU = s->nabla_U; A.w_reg = p.w_reg;
+    A.pnp = q.warp ? q.it_pn : q.it_pnp; A.pg = q.it_pg; A.psi = q.it_psi; A.nU = s->nabla_U.get(); A.w_reg = p.w_reg;
     A.max_update_norm = p.max_update_norm;
     A.compact = q.compact;
     A.warp    = q.warp;
     sobfu_hip::PassBLaunch B;
     sobfu_hip::set_whole_grid(B, X, Y, Z);
-    B.nU = s->nabla_U; B.psi = q.it_psi; B.phi_n = q.it_pn; B.pnp = q.it_out; B.updates = q.upd; B.taps = s->taps; B.alpha = p.alpha;
+    B.nU = s->nabla_U.get(); B.psi = q.it_psi; B.phi_n = q.it_pn; B.pnp = q.it_out; B.updates = q.upd; B.taps = s->taps; B.alpha = p.alpha;
     B.max_update_norm = p.max_update_norm;
     B.compact = q.compact;
     B.warp    = q.warp;
     for (int it = q.launched + 1; it <= last && !q.converged; ++it) {
-        const uint32_t* prev = (it > 1) ? s->slots + (size_t) (it - 1) * kSlots : nullptr;
-        uint32_t* cur        = s->slots + (size_t) it * kSlots;
+        const uint32_t* prev = (it > 1) ? s->slots.get() + (size_t) (it - 1) * kSlots : nullptr;
+        uint32_t* cur        = s->slots.get() + (size_t) it * kSlots;
         // timing events (sobfu_hip_solver_set_profiling): an event between two kernels costs a few us of drained pipeline, so
         // a profiled run is not the run whose wall time is quoted
         const bool ev = s->prof_stride > 0 && (it % s->prof_stride == 0) && (size_t) 3 * (s->prof_pending + 1) <= s->events.size();
         const int e0  = 3 * s->prof_pending;
-        if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0], st));
+        if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0].get(), st));
         A.prev_slots = B.prev_slots = prev;
         B.slots = cur;
         SOBFU_TRY(sobfu_hip::launch_pass_a(A, st));
-        if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 1], st));
+        if (ev) SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 1].get(), st));
         SOBFU_TRY(sobfu_hip::launch_pass_b(B, st));
         if (ev) {
-            SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 2], st));
+            SOBFU_HIP_TRY(hipEventRecord(s->events[e0 + 2].get(), st));
             s->prof_pending += 1;
         }
         q.launched = it;
@@ -262,15 +263,15 @@ int session_enqueue(sobfu_hip_solver* s, int n, bool poll, float* per_iter, hipS
             // at most kMaxRunAhead iterations past the last row it has seen (launches after the break are no-ops,
             // but each still costs a few us)
             if (!q.in_flight && (it % kCheckEvery == 0 || it == last)) {
-                SOBFU_HIP_TRY(hipMemcpyAsync(s->h_rows + (size_t) q.checked * kSlots, s->slots + (size_t) (q.checked + 1) * kSlots,
+                SOBFU_HIP_TRY(hipMemcpyAsync(s->h_rows.get() + (size_t) q.checked * kSlots, s->slots.get() + (size_t) (q.checked + 1) * kSlots,
                                              (size_t) (it - q.checked) * kSlots * 4, hipMemcpyDeviceToHost, st));
-                SOBFU_HIP_TRY(hipEventRecord(s->ev_chk, st));
+                SOBFU_HIP_TRY(hipEventRecord(s->ev_chk.get(), st));
                 q.in_flight = true;
                 q.fl_to     = it;
             }
             if (q.in_flight) {
                 const bool must_wait = it - q.checked >= kMaxRunAhead;
-                hipError_t e = must_wait ? hipEventSynchronize(s->ev_chk) : hipEventQuery(s->ev_chk);
+                hipError_t e = must_wait ? hipEventSynchronize(s->ev_chk.get()) : hipEventQuery(s->ev_chk.get());
                 if (e == hipSuccess) {
                     session_examine(s, q.fl_to, per_iter);
                     q.in_flight = false;
@@ -290,19 +291,19 @@ int session_drain(sobfu_hip_solver* s, float* per_iter, hipStream_t st) {
     if (q.launched == 0) return 0;
     if (s->p.max_update_norm >= 0.f) {
         if (q.in_flight) {
-            SOBFU_HIP_TRY(hipEventSynchronize(s->ev_chk));
+            SOBFU_HIP_TRY(hipEventSynchronize(s->ev_chk.get()));
             session_examine(s, q.fl_to, per_iter);
             q.in_flight = false;
         }
         if (!q.converged && q.checked < q.launched) {  // rows launched after the last copy was issued
-            SOBFU_HIP_TRY(hipMemcpyAsync(s->h_rows + (size_t) q.checked * kSlots, s->slots + (size_t) (q.checked + 1) * kSlots,
+            SOBFU_HIP_TRY(hipMemcpyAsync(s->h_rows.get() + (size_t) q.checked * kSlots, s->slots.get() + (size_t) (q.checked + 1) * kSlots,
                                          (size_t) (q.launched - q.checked) * kSlots * 4, hipMemcpyDeviceToHost, st));
             SOBFU_HIP_TRY(hipStreamSynchronize(st));
             session_examine(s, q.launched, per_iter);
         }
     } else {
         std::vector<uint32_t> hs((size_t) q.launched * kSlots);
-        SOBFU_HIP_TRY(hipMemcpyAsync(hs.data(), s->slots + kSlots, hs.size() * 4, hipMemcpyDeviceToHost, st));
+        SOBFU_HIP_TRY(hipMemcpyAsync(hs.data(), s->slots.get() + kSlots, hs.size() * 4, hipMemcpyDeviceToHost, st));
         SOBFU_HIP_TRY(hipStreamSynchronize(st));
         for (int k = 0; k < q.launched; ++k) {
             const float v = slots_to_norm(hs.data() + (size_t) k * kSlots);
@@ -324,7 +325,7 @@ int session_end(sobfu_hip_solver* s, sobfu_hip_solver_report* rep, float* per_it
     SOBFU_TRY(session_drain(s, per_iter, st));
     // `done` iterations actually executed (later launches were no-ops): psi.xyz back + phi_n o psi = apply(phi_n, psi), the
     // state solver.cu:168 leaves behind, in one pass
-    if (q.compact) SOBFU_TRY(sobfu_hip::launch_compact_leave(s->c_psi, q.pn, q.psi, q.pnp, s->X, s->Y, s->Z, st));
+    if (q.compact) SOBFU_TRY(sobfu_hip::launch_compact_leave(s->c_psi.get(), q.pn, q.psi, q.pnp, s->X, s->Y, s->Z, st));
     // the lines the reference prints at verbosity 0 (solver.cu:115-117,184,189), emitted after the fact
     for (int it = 1; it <= q.done && !q.inline_log; ++it)
         if (it == 1 || it % 50 == 0) s->log("iter. no. " + std::to_string(it));
@@ -354,7 +355,7 @@ int run_verbose(sobfu_hip_solver* s, const float* pg, const float* pn, float* pn
     SOBFU_TRY(ensure_updates(s));
     SOBFU_TRY(session_begin(s, pg, pn, pnp, psi, max_iter, st));
     sobfu_hip_solver::Session& q = s->q;
-    q.upd = s->updates;  // the quiet runs store `updates` too: a break inside one leaves that iteration's (reductor.cpp:26)
+    q.upd = s->updates.get();  // the quiet runs store `updates` too: a break inside one leaves that iteration's (reductor.cpp:26)
     q.inline_log = p.verbosity <= 2;  // without reporting iterations session_end prints the `iter. no.` lines
     float e_data = NAN, e_reg = NAN, arg = NAN;
     auto fail = [&](int rc) {
@@ -369,11 +370,11 @@ int run_verbose(sobfu_hip_solver* s, const float* pg, const float* pn, float* pn
     // a reporting iteration: ungated, and its pass B stores `updates`
     sobfu_hip::PassALaunch A;
     sobfu_hip::set_whole_grid(A, X, Y, Z);
-    A.pnp = q.it_pnp; A.pg = q.it_pg; A.psi = q.it_psi; A.nU = s->nabla_U; A.w_reg = p.w_reg;
+    A.pnp = q.it_pnp; A.pg = q.it_pg; A.psi = q.it_psi; A.nU = s->nabla_U.get(); A.w_reg = p.w_reg;
     A.compact = q.compact;
     sobfu_hip::PassBLaunch B;
     sobfu_hip::set_whole_grid(B, X, Y, Z);
-    B.nU = s->nabla_U; B.psi = q.it_psi; B.phi_n = q.it_pn; B.pnp = q.it_out; B.updates = s->updates; B.taps = s->taps; B.alpha = p.alpha;
+    B.nU = s->nabla_U.get(); B.psi = q.it_psi; B.phi_n = q.it_pn; B.pnp = q.it_out; B.updates = s->updates.get(); B.taps = s->taps; B.alpha = p.alpha;
     B.compact = q.compact;
     for (int it = 1; it <= max_iter && !q.converged;) {
         if (!reports(it)) {  // a run of quiet iterations it .. to
@@ -386,20 +387,20 @@ int run_verbose(sobfu_hip_solver* s, const float* pg, const float* pn, float* pn
         }
         if (it == 1 || it % 50 == 0) s->log("iter. no. " + std::to_string(it));
         if (q.compact) {  // solver.cu:132-142 (J of the displacement is rebuilt in registers, not stored)
-            SOBFU_VTRY(sobfu_hip::data_energy_tsdf(q.it_pg, q.it_pnp, (int) s->N, s->red_scratch, &e_data, st));
-            SOBFU_VTRY(sobfu_hip::reg_energy_from_psi3(q.it_psi, X, Y, Z, s->red_scratch, &e_reg, st));
+            SOBFU_VTRY(sobfu_hip::data_energy_tsdf(q.it_pg, q.it_pnp, (int) s->N, s->red_scratch.get(), &e_data, st));
+            SOBFU_VTRY(sobfu_hip::reg_energy_from_psi3(q.it_psi, X, Y, Z, s->red_scratch.get(), &e_reg, st));
         } else {
-            SOBFU_VTRY(sobfu_hip_data_energy(pg, pnp, (int) s->N, s->red_scratch, &e_data, st));
-            SOBFU_VTRY(sobfu_hip_reg_energy_sobolev_from_psi(psi, X, Y, Z, s->red_scratch, &e_reg, st));
+            SOBFU_VTRY(sobfu_hip_data_energy(pg, pnp, (int) s->N, s->red_scratch.get(), &e_data, st));
+            SOBFU_VTRY(sobfu_hip_reg_energy_sobolev_from_psi(psi, X, Y, Z, s->red_scratch.get(), &e_reg, st));
         }
         const float e = e_data + p.w_reg * e_reg;
         s->log("data energy + w_reg * reg energy = " + fmt_g(e_data) + " + " + fmt_g(p.w_reg) + " * " + fmt_g(e_reg) + " = " + fmt_g(e));
-        uint32_t* cur = s->slots + (size_t) it * kSlots;  // the row the next quiet iteration's gate reads
+        uint32_t* cur = s->slots.get() + (size_t) it * kSlots;  // the row the next quiet iteration's gate reads
         B.slots = cur;
         SOBFU_VTRY(sobfu_hip::launch_pass_a(A, st));
         SOBFU_VTRY(sobfu_hip::launch_pass_b(B, st));
         float mx[2];
-        SOBFU_VTRY(sobfu_hip_max_update_norm(s->updates, (int) s->N, s->red_scratch, mx, st));  // solver.cu:172 (synchronises)
+        SOBFU_VTRY(sobfu_hip_max_update_norm(s->updates.get(), (int) s->N, s->red_scratch.get(), mx, st));  // solver.cu:172 (synchronises)
         if (per_iter) per_iter[it - 1] = mx[0];
         arg = mx[1];
         q.launched = q.checked = q.done = it;
@@ -488,41 +489,25 @@ int sobfu_hip_sobolev_filter(int s, float lambda, float* h) {
 int sobfu_hip_solver_create(sobfu_hip_solver** out, int X, int Y, int Z, const sobfu_hip_solver_params* params) {
     SOBFU_CHECK_ARGS(out && params && X > 1 && Y > 1 && Z > 1);
     if ((size_t) X * Y * Z > (size_t) 0x7fffffff) return SOBFU_E_UNSUPPORTED;  // int32 linear indices, like the reference
-    auto* s = new sobfu_hip_solver();
+    std::unique_ptr<sobfu_hip_solver> s(new sobfu_hip_solver());  // an early return releases whatever has been built
     s->X = X; s->Y = Y; s->Z = Z;
     s->N = (size_t) X * Y * Z;
     if (const char* e = getenv("SOBFU_COMPACT")) s->compact = atoi(e) != 0;  // tuning override
-    int rc = set_params(s, params);
-    if (rc == 0) rc = (int) hipMalloc((void**) &s->nabla_U, s->N * 16);
-    if (rc == 0) rc = (int) hipMalloc(&s->red_scratch, 65536 * 8);
-    if (rc == 0) {
-        s->bytes = s->N * 16 + 65536 * 8;
-        rc = ensure_slots(s, params->max_iter > 0 ? params->max_iter : 1);
-    }
+    SOBFU_TRY(set_params(s.get(), params));
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->nabla_U, s->N * 16));
+    SOBFU_HIP_TRY(sobfu_hip::device_alloc(s->red_scratch, 65536 * 8));
+    s->bytes = s->N * 16 + 65536 * 8;
+    SOBFU_TRY(ensure_slots(s.get(), params->max_iter > 0 ? params->max_iter : 1));
     // the quiet path's compact state is part of the workspace from the start (like the reference's constructor, which
     // allocates everything up front): the first solve of a sequence pays no allocation
-    if (rc == 0 && s->compact) rc = ensure_compact(s);
-    if (rc == 0 && params->verbosity > 0) rc = ensure_updates(s);
-    if (rc != 0) {
-        sobfu_hip_solver_destroy(s);
-        return rc;
-    }
-    *out = s;
+    if (s->compact) SOBFU_TRY(ensure_compact(s.get()));
+    if (params->verbosity > 0) SOBFU_TRY(ensure_updates(s.get()));
+    *out = s.release();
     return 0;
 }
 
 int sobfu_hip_solver_destroy(sobfu_hip_solver* s) {
-    if (!s) return 0;
-    if (s->nabla_U) (void) hipFree(s->nabla_U);
-    if (s->updates) (void) hipFree(s->updates);
-    if (s->slots) (void) hipFree(s->slots);
-    if (s->red_scratch) (void) hipFree(s->red_scratch);
-    if (s->h_rows) (void) hipHostFree(s->h_rows);
-    if (s->ev_chk) (void) hipEventDestroy(s->ev_chk);
-    for (float* q : {s->c_psi, s->c_f, s->c_g, s->c_n})
-        if (q) (void) hipFree(q);
-    for (hipEvent_t e : s->events) (void) hipEventDestroy(e);
-    delete s;
+    if (s) delete s;
     return 0;
 }
 
@@ -536,7 +521,7 @@ size_t sobfu_hip_solver_workspace_bytes(const sobfu_hip_solver* s) { return s ? 
 float* sobfu_hip_solver_updates(sobfu_hip_solver* s) {
     if (!s) return nullptr;
     if (ensure_updates(s) != 0) return nullptr;
-    return s->updates;
+    return s->updates.get();
 }
 
 int sobfu_hip_solver_keep_updates(sobfu_hip_solver* s, int keep) {
@@ -571,8 +556,8 @@ int sobfu_hip_solver_get_profile(sobfu_hip_solver* s, float* ms_pass_a, float* m
     SOBFU_CHECK_ARGS(s);
     for (int it = 1; it <= s->prof_pending; ++it) {  // events recorded since the last call (the caller has synchronised)
         float a = 0, b = 0;
-        SOBFU_HIP_TRY(hipEventElapsedTime(&a, s->events[3 * (it - 1)], s->events[3 * (it - 1) + 1]));
-        SOBFU_HIP_TRY(hipEventElapsedTime(&b, s->events[3 * (it - 1) + 1], s->events[3 * (it - 1) + 2]));
+        SOBFU_HIP_TRY(hipEventElapsedTime(&a, s->events[3 * (it - 1)].get(), s->events[3 * (it - 1) + 1].get()));
+        SOBFU_HIP_TRY(hipEventElapsedTime(&b, s->events[3 * (it - 1) + 1].get(), s->events[3 * (it - 1) + 2].get()));
         s->ms_a += a;
         s->ms_b += b;
         s->prof_launches += 1;

@@ -179,13 +179,14 @@ def test_transport_sees_what_the_queries_announce():
         s.close()
 
 
-def run_world_direct(dims, grid, psi0, pg, pn, n_iters, thr, stepped, solves=1, kw=None, keep_halo_lines_hot=False):
+def run_world_direct(dims, grid, psi0, pg, pn, n_iters, thr, stepped, solves=1, kw=None, keep_halo_lines_hot=False, solvers=None, close=True):
     """N ranks on the DIRECT transport in one process.  stepped: one host thread drives all ranks phase by phase (pass A incl.
     the pushes | pass B | ... | end-of-solve handshake) with the in-kernel waits off -- any number of ranks; else one thread
     per rank runs the real loop, in-kernel waits live (few ranks: every rank's stream needs a hardware queue of its own).
     keep_halo_lines_hot (stepped): right before every pass A -- whose push boxes store into the OTHER ranks' nabla_U halo cells -- a
     copy kernel reads every rank's nabla_U arena, so that the lines those stores are about to change sit in the reader's caches when
-    the stores happen: pass B must still see the new cells (on connected handles it reads nabla_U and the max-norm rows at system scope)."""
+    the stores happen: pass B must still see the new cells (on connected handles it reads nabla_U and the max-norm rows at system scope).
+    solvers: connected handles of the caller's (default: fresh ones, connected here); close=False leaves them open."""
     import ctypes as C
 
     import torch
@@ -194,9 +195,10 @@ def run_world_direct(dims, grid, psi0, pg, pn, n_iters, thr, stepped, solves=1, 
 
     grid = as_grid(grid)
     world = grid[0] * grid[1] * grid[2]
-    kw = kw or dict(alpha=0.05, w_reg=0.4)
-    solvers = [tiled.NativeTiledSolver(dims, max_update_norm=thr, dry=(world, r), grid=grid, **kw) for r in range(world)]
-    tiled.NativeTiledSolver.connect_local(solvers)
+    if solvers is None:
+        kw = kw or dict(alpha=0.05, w_reg=0.4)
+        solvers = [tiled.NativeTiledSolver(dims, max_update_norm=thr, dry=(world, r), grid=grid, **kw) for r in range(world)]
+        tiled.NativeTiledSolver.connect_local(solvers)
     torch.cuda.synchronize()
     pn_d = torch.from_numpy(pn).cuda()
     if stepped:
@@ -261,7 +263,7 @@ def run_world_direct(dims, grid, psi0, pg, pn, n_iters, thr, stepped, solves=1, 
         assert all(s.status()[0] for s in solvers)
     res = [(out[r][0], out[r][1], solvers[r].layout.owned(state[r][1]).cpu().numpy(), solvers[r].layout.owned(state[r][2]).cpu().numpy()) for r in range(world)]
     full = (assemble(solvers, [o[2] for o in res]), assemble(solvers, [o[3] for o in res]))
-    for s in solvers:
+    for s in solvers if close else ():
         s.close()
     return res, full
 
@@ -309,6 +311,71 @@ def test_native_loop_direct_transport(dims, grid, stepped):
             assert np.array_equal(np.asarray(hist, np.float32).view(np.uint32), hist_e.view(np.uint32))
         assert np.array_equal(psi_t[..., :3].view(np.uint32), psi_e[..., :3].view(np.uint32))
         assert np.array_equal(pnp_t.view(np.uint32), pnp_e.view(np.uint32))
+
+
+def test_max_norm_rows_outgrow_the_exported_ones_and_return():
+    """The exported max-norm rows hold 16 384 iterations.  An UNCONNECTED handle that runs one more moves to private rows (and stays
+    there for a shorter solve); connecting it moves the rows back into the arena the peers map, after which a longer solve is refused
+    and the handle goes on working.  The smallest tiles the layout allows; bit for bit against the single-GPU solve."""
+    import torch
+
+    import oracle
+    from sobfu_amd import ops, tiled
+
+    dims, long = (8, 8, 8), 16385
+    rng = np.random.default_rng(17)
+    pg = np.stack([rng.uniform(-1, 1, dims), rng.integers(0, 3, dims)], -1).astype(np.float32)
+    pn = np.stack([rng.uniform(-1, 1, dims), rng.integers(0, 3, dims)], -1).astype(np.float32)
+    psi0 = oracle.new_field(dims)
+    oracle.init_identity(psi0)
+    psi0[..., :3] += rng.uniform(-0.7, 0.7, psi0[..., :3].shape).astype(np.float32)
+    pg_d, pn_d = torch.from_numpy(pg).cuda(), torch.from_numpy(pn).cuda()
+    kw = dict(alpha=0.05, w_reg=0.4)
+
+    # a world of one: past the exported rows, then a short solve on the private ones
+    ref = ops.Solver(dims, max_iter=long, max_update_norm=-1.0, **kw)
+    one = tiled.NativeTiledSolver(dims, max_update_norm=-1.0, dry=(1, 0), grid=(1, 1, 1), **kw)
+    assert one.max_iterations() > long
+    psi_r, pnp_r = torch.from_numpy(psi0.copy()).cuda(), ops.new_volume(dims)
+    psi_t, pnp_t = torch.from_numpy(psi0.copy()).cuda(), one.new_local(2)
+    for n in (long, 6):
+        rep, hist_r = ref.iterate(pg_d, pn_d, pnp_r, psi_r, n)
+        done, hist_t = one.iterate(pg_d, pn_d, pnp_t, psi_t, n)
+        torch.cuda.synchronize()
+        assert done == rep.iterations == n
+        assert np.array_equal(np.asarray(hist_t, np.float32).view(np.uint32), np.asarray(hist_r[:n], np.float32).view(np.uint32))
+        assert torch.equal(psi_t[..., :3].contiguous().view(torch.int32), psi_r[..., :3].contiguous().view(torch.int32))
+    ref.close()
+    one.close()
+
+    # a world of two: each rank outgrows the exported rows alone (no halo arrives: nothing to compare), then they connect
+    thr, grid = 1e-10, (1, 1, 2)
+    ref = ops.Solver(dims, max_iter=6, max_update_norm=thr, **kw)
+    psi_r, pnp_r = torch.from_numpy(psi0.copy()).cuda(), ops.new_volume(dims)
+    rep, hist_r = ref.iterate(pg_d, pn_d, pnp_r, psi_r, 6)
+    ref.close()
+    hist_r = np.asarray(hist_r[:rep.iterations], np.float32)
+    solvers = [tiled.NativeTiledSolver(dims, max_update_norm=thr, dry=(2, r), grid=grid, **kw) for r in range(2)]
+    for s in solvers:
+        L = s.layout
+        s.iterate(torch.from_numpy(np.ascontiguousarray(L.take(pg))).cuda(), pn_d, s.new_local(2), torch.from_numpy(np.ascontiguousarray(L.take(psi0))).cuda(), long)
+        torch.cuda.synchronize()
+    tiled.NativeTiledSolver.connect_local(solvers)
+
+    def solve_and_compare(close):
+        out, (psi_t, pnp_t) = run_world_direct(dims, grid, psi0, pg, pn, 6, thr, True, solvers=solvers, close=close)
+        for done, hist, _, _ in out:
+            assert done == rep.iterations
+            assert np.array_equal(np.asarray(hist, np.float32).view(np.uint32), hist_r.view(np.uint32))
+        assert np.array_equal(psi_t[..., :3].view(np.uint32), psi_r.cpu().numpy()[..., :3].view(np.uint32))
+        assert np.array_equal(pnp_t.view(np.uint32), pnp_r.cpu().numpy().view(np.uint32))
+
+    solve_and_compare(close=False)
+    assert all(s.max_iterations() == 16384 for s in solvers)
+    s = solvers[0]
+    with pytest.raises(RuntimeError, match="unsupported"):
+        s.begin(s.new_local(2), pn_d, s.new_local(2), s.identity_psi(), long)
+    solve_and_compare(close=True)
 
 
 @pytest.mark.parametrize("dims,grid", [((40, 24, 36), (2, 2, 2)), ((64, 64, 64), (2, 2, 2)), ((40, 24, 36), (1, 1, 3))])

@@ -57,7 +57,7 @@ def tile_a(dims, boxes):
 
 
 def tile_b_boxes(lay, za, zb, za2=0, zb2=0, shells=True):
-    """the six boxes of the tiled loop's pass B launch (tiled_step_impl): two plane ranges of the owned block, the y and x shells"""
+    """the six boxes of the tiled loop's pass B launch (pass_b in tiled_capi.hip): two plane ranges of the owned block, the y and x shells"""
     ax0, ax1, ay0, ay1, lo, hi = lay.own_box()
     return [box(ax0, ax1, ay0, ay1, za, zb), box(ax0, ax1, ay0, ay1, za2, zb2),
             box(ax0, ax1, ay0 - 1, ay0 if shells and lay.lo3[1] else ay0 - 1, lo, hi, 1), box(ax0, ax1, ay1, ay1 + 1 if shells and lay.hi3[1] else ay1, lo, hi, 1),
