@@ -34,6 +34,11 @@
 // --evaluate-pose FILE (16 numbers, row-major 4 x 4) is applied to it first.  --evaluate-max-dist METRES (default 5 x the truncation distance):
 // vertices farther than that have no match.  --error-mesh DIR writes the evaluated mesh as DIR/error_canonical_<frame>.ply /
 // DIR/error_live_<frame>.ply with vertices coloured by error: blue (0) to red (max-dist), grey where there is no match.
+// --evaluate-align [ITERS] (default 30) refines the pose of --evaluate-pose (or the identity) before each canonical --evaluate, by
+// point-to-plane ICP of the model's vertices against the ground truth (a start within ICP's basin is the caller's to give),
+// and prints "align: status=... iterations=... inliers=... rms=... pose=<16 numbers at %.9g>"; --evaluate-align-dof 3|6 (default 6; 3:
+// translation only, for symmetric objects); --evaluate-pose-out FILE writes the refined pose as --evaluate-pose reads it.  --evaluate-live
+// uses the pose as given: aligning every live frame would hide the tracking error that evaluation measures.
 //
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
@@ -184,7 +189,7 @@ static std::string frame_path(const std::string& pattern, int n) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -199,7 +204,8 @@ int main(int argc, char** argv) {
     bool textured = false, warp_mesh = false, fit_stats = false;
     int track_mesh = -1;  // the frame after which the tracked mesh is cut; -1: off
     std::string dump, mesh_dir, data_dir, mesh_format = "vtk", poses_path;
-    std::string eval_gt, eval_live, eval_pose, error_dir;
+    std::string eval_gt, eval_live, eval_pose, error_dir, eval_pose_out;
+    int eval_align = -1, eval_align_dof = 6;  // --evaluate-align: the iterations; -1: off
     float eval_max_dist = -1.f;  // < 0: 5 x the truncation distance
     Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
@@ -229,11 +235,26 @@ int main(int argc, char** argv) {
         else if (a == "--evaluate-live" && i + 1 < argc) eval_live = argv[++i];
         else if (a == "--evaluate-max-dist" && i + 1 < argc) eval_max_dist = std::strtof(argv[++i], nullptr);
         else if (a == "--evaluate-pose" && i + 1 < argc) eval_pose = argv[++i];
+        else if (a == "--evaluate-align") {
+            eval_align = 30;
+            if (i + 1 < argc && argv[i + 1][0] != '\0' && std::string(argv[i + 1]).find_first_not_of("0123456789") == std::string::npos)
+                eval_align = std::atoi(argv[++i]);
+        }
+        else if (a == "--evaluate-align-dof" && i + 1 < argc) eval_align_dof = std::atoi(argv[++i]);
+        else if (a == "--evaluate-pose-out" && i + 1 < argc) eval_pose_out = argv[++i];
         else if (a == "--error-mesh" && i + 1 < argc) error_dir = argv[++i];
         else files.push_back(a);
     }
     if (mesh_format != "vtk" && mesh_format != "ply") {
         std::printf("--mesh-format is vtk or ply, not %s\n", mesh_format.c_str());
+        return 2;
+    }
+    if (eval_align_dof != 3 && eval_align_dof != 6) {
+        std::printf("--evaluate-align-dof is 3 or 6, not %d\n", eval_align_dof);
+        return 2;
+    }
+    if (eval_align > 1000 || (eval_align >= 0 && eval_gt.empty()) || (!eval_pose_out.empty() && eval_align < 0)) {
+        std::printf("--evaluate-align takes at most 1000 iterations and needs --evaluate GT.ply; --evaluate-pose-out needs --evaluate-align\n");
         return 2;
     }
     if ((warp_mesh || track_mesh >= 0) && mesh_dir.empty()) {
@@ -272,12 +293,29 @@ int main(int argc, char** argv) {
             std::printf("cannot read ground truth: %s\n", why.c_str());
             return false;
         }
-        if (!eval_pose.empty()) sobfu_amd::transform_points(gt.vertices, gt_pose);
+        const bool align = !live && eval_align >= 0;  // the live evaluation uses the pose as given
+        if (!eval_pose.empty() && !align) sobfu_amd::transform_points(gt.vertices, gt_pose);
         sobfu_amd::MeshComparison r;
         std::vector<float> d;
-        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why) : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why))) {
+        sobfu_amd::AlignRequest request;
+        std::copy(gt_pose, gt_pose + 16, request.pose);
+        request.iters = eval_align, request.dof = eval_align_dof;
+        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why)
+                   : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr))) {
             std::printf("cannot evaluate against %s: %s\n", gt_path.c_str(), why.c_str());
             return false;
+        }
+        if (align) {
+            std::printf("align: %s\n", sobfu_amd::format_alignment(request.info, request.pose).c_str());
+            if (!eval_pose_out.empty()) {
+                FILE* f = std::fopen(eval_pose_out.c_str(), "w");
+                if (!f) {
+                    std::printf("cannot write %s\n", eval_pose_out.c_str());
+                    return false;
+                }
+                for (int k = 0; k < 16; ++k) std::fprintf(f, k % 4 == 3 ? "%.9g\n" : "%.9g ", (double) request.pose[k]);
+                std::fclose(f);
+            }
         }
         std::printf("evaluate %s %d: %s\n", live ? "live" : "canonical", n, sobfu_amd::format_comparison(r).c_str());
         if (!error_dir.empty() && !model.empty()) {

@@ -1,8 +1,11 @@
 // Reconstruction error against a ground-truth mesh (no reference counterpart; kernels and rules: sobfu_amd/csrc/mesh_distance_kernels.hip,
 // DESIGN.md 4.9): a PLY reader, the triangle grid over the C ABI, the two-way vertex-to-surface comparison and its statistics.  Part of
 // sobfu.hpp, which includes it after IndexedMesh, DeviceArray and sobfuSafeCall: not a header to include on its own.  The Python twins are
-// sobfu_amd/mesh_io.py (read_ply) and sobfu_amd/evaluate.py (compare_meshes).
+// sobfu_amd/mesh_io.py (read_ply) and sobfu_amd/evaluate.py (compare_meshes, align_meshes).  Automatic rigid alignment of the ground truth
+// (sobfu_amd/csrc/mesh_align_kernels.hip): TriangleGrid::align, align_meshes, format_alignment.
 #pragma once
+
+#include "../../sobfu_amd/csrc/sobfu_rigid.hpp"  // the rigid inverse, the same lines as the kernels'
 
 namespace sobfu_amd {
 
@@ -194,6 +197,14 @@ inline bool read_ply(const std::string& path, IndexedMesh& m, std::string* why =
     return true;
 }
 
+// What sobfu_hip_mesh_align_estimate reported (sobfu_amd.ops.align_info): the status word; the updates applied; stopped by the gate;
+// the solve of iteration `iterations` failed (the pose before it is kept); per iteration that ran: inliers, rms residual, |w|, |t_inc|
+struct Alignment {
+    int status = 0, iterations = 0;
+    bool converged = false, failed = false;
+    std::vector<float> trace;
+};
+
 // ---- TriangleGrid: the grid of sobfu_hip_mesh_grid_build over a mesh kept on the device ---------------------------------------------
 class TriangleGrid {
 public:
@@ -255,6 +266,42 @@ public:
         dd.download(dist);
         if (tri) dt.download(*tri);
         if (closest) dc.download(*closest);
+    }
+    // Point-to-plane ICP of `points` against this mesh from `pose` (row-major 4 x 4, points -> this mesh's frame), refined in place:
+    // `iters` iterations enqueued as one chain, one synchronisation to read the result.  dof 6: rigid, 3: translation only; the loop
+    // stops early once an update is below both eps_rot and eps_trans (0: never).  Without points: failed at iteration 0.
+    Alignment align(const std::vector<float4>& points, float pose[16], int iters = 30, float max_dist = 0.f, int dof = 6, float eps_rot = 0.f,
+                    float eps_trans = 0.f, int mode = SOBFU_MESH_DISTANCE_AUTO, int ring_cap = 0) {
+        if (!built_) kfusion::cuda::error("TriangleGrid::align without a built grid", __FILE__, __LINE__);
+        const int n = (int) points.size();
+        int status = iters > 0 ? 0x10000 : 0;
+        std::vector<float> trace((size_t) 4 * (size_t) std::max(iters, 1), 0.f);
+        if (n > 0) {
+            kfusion::cuda::DeviceArray<float4> dp;
+            kfusion::cuda::DeviceArray<float> dpose, dtrace;
+            kfusion::cuda::DeviceArray<int> dstatus(1);
+            kfusion::cuda::DeviceArray<unsigned char> ws(sobfu_hip_mesh_align_workspace_bytes(n));
+            dp.upload(points);
+            dpose.upload(pose, 16);
+            dtrace.upload(trace);
+            sobfuSafeCall(sobfu_hip_mesh_align_estimate(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
+                                                        nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dp.ptr(), n, max_dist, mode,
+                                                        ring_cap, iters, dof, eps_rot, eps_trans, ws.ptr(), ws.size(), dpose.ptr(), dstatus.ptr(),
+                                                        dtrace.ptr(), nullptr));
+            std::vector<float> got;
+            std::vector<int> st;
+            dstatus.download(st);
+            dpose.download(got);
+            dtrace.download(trace);
+            std::copy(got.begin(), got.end(), pose);
+            status = st[0];
+        }
+        Alignment a;
+        a.status = status, a.failed = (status & 0x10000) != 0, a.converged = (status & 0x20000) != 0;
+        a.iterations = status ? (status & 0xFFFF) : iters;
+        trace.resize((size_t) 4 * (size_t) std::min(iters, a.iterations + (a.failed ? 1 : 0)));
+        a.trace.swap(trace);
+        return a;
     }
     int references() const { return references_; }
     const int* dims() const { return dims_; }
@@ -330,6 +377,35 @@ inline void transform_points(std::vector<float4>& points, const float pose[16]) 
         p = make_float4(o[0], o[1], o[2], 1.f);
     }
 }
+// Refines the pose that carries a ground-truth mesh into the model's frame (sobfu_amd.evaluate.align_meshes): point-to-plane ICP of the
+// model's vertices (the source: a partial surface) against the ground truth (the target: complete; its grid is built once).  pose: in, the
+// caller's ground-truth-to-model guess, whose rigid inverse starts the loop; out, the rigid inverse of the result -- the pose to apply to
+// the ground truth.  false (+ *why): the ground truth is refused.  A refinement within ICP's basin, not a global registration.
+inline bool align_meshes(const std::vector<float4>& model_vertices, const IndexedMesh& gt, float pose[16], Alignment& info, int iters = 30,
+                         float max_dist = 0.f, int dof = 6, float eps_rot = 0.f, float eps_trans = 0.f, std::string* why = nullptr) {
+    TriangleGrid grid;
+    if (!grid.build(gt.vertices, gt.faces, 0.f, why)) return false;
+    float start[16];
+    sobfu_hip::rigid_inverse(pose, start);
+    info = grid.align(model_vertices, start, iters, max_dist, dof, eps_rot, eps_trans);
+    sobfu_hip::rigid_inverse(start, pose);
+    return true;
+}
+// one line (sobfu_amd.evaluate.format_alignment): status, iterations, the inliers and rms residual of the last iteration that ran, the pose
+inline std::string format_alignment(const Alignment& a, const float pose[16]) {
+    char line[1024];
+    const size_t rows = a.trace.size() / 4;
+    int at = std::snprintf(line, sizeof line, "status=0x%x iterations=%d inliers=%d rms=%.9g pose=", a.status, a.iterations,
+                           rows ? (int) a.trace[4 * (rows - 1)] : 0, rows ? (double) a.trace[4 * (rows - 1) + 1] : 0.0);
+    for (int k = 0; k < 16; ++k) at += std::snprintf(line + at, sizeof line - (size_t) at, k ? ",%.9g" : "%.9g", (double) pose[k]);
+    return line;
+}
+// what SobFusion::evaluate_canonical is to align first: in, the guess and the loop's settings; out, the refined pose and the report
+struct AlignRequest {
+    float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // ground truth -> model
+    int iters = 30, dof = 6;
+    Alignment info;
+};
 // Vertex colours by error: a fixed ramp from blue (0) to red (max_dist and beyond), r = round(255 t), b = round(255 (1 - t)), g = 0 with
 // t = clamp(d / max_dist, 0, 1) in double; grey (128, 128, 128) where there is no match
 inline void error_colours(const std::vector<float>& dist, float max_dist, std::vector<kfusion::RGB>& colours) {

@@ -1419,10 +1419,22 @@ public:
     // exact vertex-to-surface distances both ways, in metres (a = the model, b = the ground truth).  evaluate_canonical: the indexed mesh
     // of phi_global; evaluate_live: that mesh carried through psi.  Reads the volumes only.  model / d_model (optional): the evaluated
     // mesh and its vertices' distances.  false (+ *why): the ground truth is refused (an index out of range, a non-finite corner)
+    // align (optional, canonical only): align->pose, the caller's ground-truth-to-model guess, is first refined against the model
+    // (sobfu_amd::align_meshes with max_dist) and applied to a copy of the ground truth; without it the ground truth is taken as given.
     bool evaluate_canonical(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
-                            std::vector<float>* d_model = nullptr, std::string* why = nullptr) {
+                            std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::AlignRequest* align = nullptr) {
         sobfu_amd::IndexedMesh m = get_phi_global_indexed_mesh();
-        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why);
+        bool ok;
+        if (align) {
+            sobfu_amd::IndexedMesh posed = gt;
+            ok = sobfu_amd::align_meshes(m.vertices, gt, align->pose, align->info, align->iters, max_dist, align->dof, 0.f, 0.f, why);
+            if (ok) {
+                sobfu_amd::transform_points(posed.vertices, align->pose);
+                ok = sobfu_amd::compare_meshes(m, posed, max_dist, out, d_model, nullptr, why);
+            }
+        } else {
+            ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why);
+        }
         if (model) *model = std::move(m);
         return ok;
     }

@@ -607,6 +607,32 @@ int sobfu_hip_mesh_distance(void* d_workspace, size_t workspace_bytes, const flo
 /* How many points of the last sobfu_hip_mesh_distance through this workspace hit the ring cap (synchronises the stream). */
 int sobfu_hip_mesh_distance_unresolved(const void* d_workspace, int* h_count, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mesh alignment  (no counterpart in the reference; sobfu_amd/csrc/mesh_align_kernels.hip)
+ * Point-to-plane ICP of n points (dense float4, w ignored) against the mesh and grid of sobfu_hip_mesh_grid_build: per iteration the
+ * points go through the pose in d_pose (16 floats, row-major 4 x 4, source -> target frame; rows 0..2 are read and written), their exact
+ * nearest triangles come from sobfu_hip_mesh_distance (max_dist, mode, ring_cap as there), the 29 fp64 sums of the normal equations
+ * are reduced without floating-point atomics and one workgroup solves and updates the pose.  Bitwise reproducible run to run.
+ * Every argument is checked before any device call (SOBFU_E_BADARG); n = 0 succeeds, launches nothing and writes nothing.
+ * ---------------------------------------------------------------------------------------------------- */
+/* Bytes of the caller-kept workspace (16-byte aligned) for n points: the partial sums, the transformed points and the query's
+ * dist / tri / closest / unresolved arrays.  0 for n < 0. */
+size_t sobfu_hip_mesh_align_workspace_bytes(int n);
+/* One transform + query + sums at the pose in d_pose -> d_sums, 29 doubles laid out as sobfu_hip_icp_step's: the 21 upper-triangular
+ * J_i J_j, the 6 J_i r, the inlier count, the sum of r r.  No solve; the pose is only read.  Asynchronous. */
+int sobfu_hip_mesh_align_step(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                              int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, float max_dist, int mode,
+                              int ring_cap, const float* d_pose, void* d_workspace, size_t workspace_bytes, double* d_sums, void* stream);
+/* `iters` (0..1000) iterations from the pose already in d_pose; enqueues only.  dof: 6 rigid, 3 translation only.  eps_rot (radians),
+ * eps_trans (metres) >= 0: the loop stops once an update is below BOTH (0: never).  *d_status: 0 every iteration ran;
+ * 0x20000 | iterations done: stopped by the gate; 0x10000 | iteration: the solve of that iteration failed (a pivot <= 0 or non-finite:
+ * no inliers, or a geometry that does not fix the pose) and the pose of the iteration before is left in place.  d_trace (may be NULL):
+ * 4 floats per iteration -- inliers, rms residual, |w|, |t_inc| -- written for the iterations that ran. */
+int sobfu_hip_mesh_align_estimate(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                                  int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, float max_dist,
+                                  int mode, int ring_cap, int iters, int dof, float eps_rot, float eps_trans, void* d_workspace, size_t workspace_bytes,
+                                  float* d_pose, int* d_status, float* d_trace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,10 +54,12 @@
 // reduces them with a wave64 __shfl_xor butterfly and then across its 4 waves through LDS (wave 0 + 1 + 2 + 3, in that order), and writes
 // one 32-float slab.  No float atomics anywhere: the sums, and so the pose, are bitwise reproducible.  The solve is one 256-thread
 // workgroup: thread j converts slab j to fp64, the same butterfly and LDS order reduce the slabs, lane 0 solves.  Every index of the
-// 6 x 6 system is a compile-time constant (fully unrolled loops): nothing goes to scratch.
+// 6 x 6 system is a compile-time constant (fully unrolled loops): nothing goes to scratch.  The LDL^T, Rodrigues and the pose
+// composition are sobfu_rigid.hpp's, shared with mesh_align_kernels.hip.
 #include "sobfu_frame.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
+#include "sobfu_rigid.hpp"
 
 #include <cmath>
 
@@ -343,63 +345,22 @@ __global__ void __launch_bounds__(kThreads) icp_solve_kernel(const float* __rest
 #pragma unroll
         for (int r = 0; r < 6; ++r) b[r] = acc[21 + r];
     }
-    double L[6][6], D[6], det = 1.0;
-    bool pivots_ok = true;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double dc = A[c][c];
-#pragma unroll
-        for (int k = 0; k < c; ++k) dc -= L[c][k] * L[c][k] * D[k];
-        D[c] = dc;
-        det *= dc;
-        pivots_ok = pivots_ok && dc > 0.0;
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            double a = A[r][c];
-#pragma unroll
-            for (int k = 0; k < c; ++k) a -= L[r][k] * L[c][k] * D[k];
-            L[r][c] = a / dc;
-        }
-    }
-    if (!(fabs(det) >= 1e-15) || !pivots_ok) {
+    Ldlt<6> f;
+    ldlt_factor<6>(A, f);
+    if (!(fabs(f.det) >= 1e-15) || !f.positive) {
         *status = tag;
         return;
     }
     double x[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {  // L y = b
-        double y = b[r];
-#pragma unroll
-        for (int k = 0; k < r; ++k) y -= L[r][k] * x[k];
-        x[r] = y;
-    }
-#pragma unroll
-    for (int r = 0; r < 6; ++r) x[r] = x[r] / D[r];
-#pragma unroll
-    for (int r = 5; r >= 0; --r) {  // L^T x = z
-        double y = x[r];
-#pragma unroll
-        for (int k = r + 1; k < 6; ++k) y -= L[k][r] * x[k];
-        x[r] = y;
-    }
+    ldlt_solve<6>(f, b, x);
     // Tinc = (Rodrigues(x0..2), x3..5)
-    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    const double th = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-    if (th > 0.0) {
-        const double kx = x[0] / th, ky = x[1] / th, kz = x[2] / th, c = cos(th), s = sin(th), c1 = 1.0 - c;
-        R[0] = c + c1 * kx * kx, R[1] = c1 * kx * ky - s * kz, R[2] = c1 * kx * kz + s * ky;
-        R[3] = c1 * ky * kx + s * kz, R[4] = c + c1 * ky * ky, R[5] = c1 * ky * kz - s * kx;
-        R[6] = c1 * kz * kx - s * ky, R[7] = c1 * kz * ky + s * kx, R[8] = c + c1 * kz * kz;
-    }
+    const double w[3] = {x[0], x[1], x[2]}, t[3] = {x[3], x[4], x[5]};
+    double R[9];
+    rodrigues(w, R);
     float P[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) P[k] = pose[k];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pose[4 * r + c] = (float) (R[3 * r] * P[c] + R[3 * r + 1] * P[4 + c] + R[3 * r + 2] * P[8 + c]);
-        pose[4 * r + 3] = (float) (R[3 * r] * P[3] + R[3 * r + 1] * P[7] + R[3 * r + 2] * P[11] + x[3 + r]);
-    }
+    pose_compose(R, t, P, pose);
 }
 
 Reproj level_reproj(float fx, float fy, float cx, float cy, int level) {

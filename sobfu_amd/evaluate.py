@@ -51,3 +51,41 @@ def format_result(r):
     """the app's printed form: every field at %.9g, a_to_b and b_to_a prefixed"""
     parts = [f"{side}.{k}={r[side][k]:.9g}" for side in ("a_to_b", "b_to_a") for k in STAT_FIELDS]
     return " ".join(parts + [f"chamfer={r['chamfer']:.9g}", f"hausdorff={r['hausdorff']:.9g}"])
+
+
+# ---- automatic rigid alignment of the ground truth (ops.TriangleGrid.align, sobfu_amd/csrc/mesh_align_kernels.hip) ----------------------
+def rigid_inverse(pose):
+    """the inverse of a rigid 4 x 4 float32 pose, in the operation order of sobfu_amd/csrc/sobfu_rigid.hpp: R^T, and
+    t' = (float32) -((P_0r P_03 + P_1r P_13) + P_2r P_23) in float64"""
+    P = np.asarray(pose, np.float32).reshape(4, 4)
+    D = P.astype(np.float64)
+    out = np.zeros((4, 4), np.float32)
+    out[:3, :3] = P[:3, :3].T
+    for r in range(3):
+        out[r, 3] = np.float32(-((D[0, r] * D[0, 3] + D[1, r] * D[1, 3]) + D[2, r] * D[2, 3]))
+    out[3, 3] = 1
+    return out
+
+
+def align_meshes(model_vertices, gt_vertices, gt_faces, pose=None, iters=30, max_dist=None, dof=6, eps_rot=0.0, eps_trans=0.0):
+    """Refines the pose that carries a ground-truth mesh into the model's frame: point-to-plane ICP of the model's vertices (the source: a
+    partial surface, every point of which has a counterpart) against the ground-truth mesh (the target: complete; its grid is built
+    once).  pose: the caller's ground-truth-to-model guess (None: the identity); its rigid inverse starts the loop, and the rigid
+    inverse of the result is returned -> (pose (4, 4) float32 numpy, to apply to the ground truth, info of ops.TriangleGrid.align).
+    ICP needs a start within its basin: this is a refinement, not a global registration."""
+    import torch
+
+    from . import ops
+
+    mv, gv = device_tensor(model_vertices, torch.float32), device_tensor(gt_vertices, torch.float32)
+    gf = device_tensor(gt_faces, torch.int32)
+    start = None if pose is None else rigid_inverse(pose)
+    found, info = ops.TriangleGrid(gv, gf).align(mv, start, iters, max_dist, dof, eps_rot, eps_trans)
+    return rigid_inverse(found.cpu().numpy()), info
+
+
+def format_alignment(info, pose):
+    """the app's printed form: status, iterations, the inliers and rms residual of the last iteration that ran, the 16 pose numbers at %.9g"""
+    last = info["trace"][-1] if len(info["trace"]) else (0.0, 0.0)
+    return "status=0x%x iterations=%d inliers=%d rms=%.9g pose=%s" % (info["status"], info["iterations"], int(last[0]), float(last[1]),
+                                                                   ",".join("%.9g" % float(v) for v in np.asarray(pose, np.float32).reshape(16)))

@@ -190,12 +190,16 @@ class SobFusion:
             return dict(valid=0, mean_abs=0.0, rms=0.0, max=0.0)
         return dict(valid=int(d.size), mean_abs=float(d.mean()), rms=float(np.sqrt((d * d).mean())), max=float(d.max()))
 
-    def evaluate(self, gt_vertices, gt_faces, which="canonical", max_dist=None, pose=None, return_meshes=False):
+    def evaluate(self, gt_vertices, gt_faces, which="canonical", max_dist=None, pose=None, return_meshes=False, align=False, align_dof=6,
+                 align_iters=30):
         """The reconstruction against a ground-truth mesh (vertices (V, 4), faces (F, 3)) in the frame of the meshes the app writes
         (marching-cubes vertices, (x, -y, -z)): exact vertex-to-surface distances both ways (sobfu_amd.evaluate.compare_meshes; a = the
         model, b = the ground truth), in metres.  which: "canonical" meshes phi_global (ops.marching_cubes_indexed at the volume pose),
         "live" carries that mesh through psi (warp_to_live).  pose: a 4 x 4 transform applied to the ground truth first (float32, row by
-        row: (r0 x + r1 y) + r2 z + t).  Reads the volumes only.  return_meshes: -> (dict, model vertices, model faces, gt vertices)."""
+        row: (r0 x + r1 y) + r2 z + t).  Reads the volumes only.  return_meshes: -> (dict, model vertices, model faces, gt vertices).
+        align (canonical only): `pose` (default: the identity) is first refined by sobfu_amd.evaluate.align_meshes -- align_iters
+        iterations, align_dof 6 (rigid) or 3 (translation only: symmetric objects) -- and the dict gains "pose" (the refined 4 x 4) and
+        "align" (the alignment's info).  The live mesh is never aligned: that would hide the tracking error evaluation measures."""
         import torch
 
         from . import evaluate as E
@@ -209,9 +213,16 @@ class SobFusion:
         if which == "live":
             v = self.warp_to_live(v)
         gv = E.device_tensor(gt_vertices, torch.float32)
+        info = None
+        if align:
+            if which != "canonical":
+                raise ValueError("align refines the pose of the canonical evaluation only")
+            pose, info = E.align_meshes(v, gv, gt_faces, pose, iters=align_iters, max_dist=max_dist, dof=align_dof)
         if pose is not None:
             gv = E.device_tensor(transform_points(gv.cpu().numpy(), pose), torch.float32)
         r = E.compare_meshes(v, f, gv, gt_faces, max_dist)
+        if align:
+            r["pose"], r["align"] = pose, info
         return (r, v, f, gv) if return_meshes else r
 
     def close(self):

@@ -638,6 +638,13 @@ def mesh_grid_plan(bbox, n_triangles, cell=None):
     return np.array(list(origin), np.float32), float(h.value), np.array(list(dims), np.int32)
 
 
+def align_info(status, iters, trace):
+    """the status word of sobfu_hip_mesh_align_estimate -> dict(status, iterations, converged, failed, trace)"""
+    failed, converged = bool(status & 0x10000), bool(status & 0x20000)
+    done = (status & 0xFFFF) if status else iters
+    return dict(status=status, iterations=done, converged=converged, failed=failed, trace=np.array(trace[:min(iters, done + (1 if failed else 0))]))
+
+
 class TriangleGrid:
     """A uniform grid over an indexed triangle mesh -- vertices (V, 4) float32, faces (F, 3) int32, GPU tensors that must stay unchanged
     while the grid is used -- for exact nearest-triangle queries.  cell: the cell edge (None: the plan's default).  Owns the workspace.
@@ -694,6 +701,57 @@ class TriangleGrid:
                                                      _ptr(dist), _ptr(tri, torch.int32), None if cl is None else _ptr(cl),
                                                      _ptr(self.unresolved_buffer, torch.int32), _stream()), "mesh_distance")
         return (dist, tri, cl) if closest else (dist, tri)
+
+    # ---- rigid alignment of a point list to this mesh (sobfu_amd/csrc/mesh_align_kernels.hip) ----
+    def _align_workspace(self, n, device):
+        return torch.empty(int(_lib.lib().sobfu_hip_mesh_align_workspace_bytes(C.c_int(n))), dtype=torch.uint8, device=device)
+
+    def _align_target(self, points, n, max_dist, mode, ring_cap):
+        if mode not in _MESH_MODES:
+            raise ValueError(f"unknown mode {mode!r}")
+        return (*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(points, "points") if n else None, C.c_int(n),
+                _f(0.0 if max_dist is None else max_dist), C.c_int(_MESH_MODES[mode]), C.c_int(int(ring_cap or 0)))
+
+    def align_step(self, points, pose, max_dist=None, mode="auto", ring_cap=None):
+        """One transform + nearest-triangle query + reduction of the (n, 4) float32 points at the 4 x 4 `pose` (points -> this mesh's
+        frame) -> the 29 float64 sums of the point-to-plane normal equations (numpy): the 21 upper-triangular J_i J_j, the 6 J_i r, the
+        inlier count, the sum of r r.  No solve."""
+        n = int(points.shape[0])
+        if n == 0:
+            return np.zeros(29)
+        pose_d = torch.as_tensor(np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16)), device=points.device)
+        ws = self._align_workspace(n, points.device)
+        sums = torch.empty(29, dtype=torch.float64, device=points.device)
+        check(_lib.lib().sobfu_hip_mesh_align_step(*self._align_target(points, n, max_dist, mode, ring_cap), _ptr(pose_d), *_ws(ws),
+                                                   _ptr(sums, torch.float64), _stream()), "mesh_align_step")
+        return sums.cpu().numpy()
+
+    def align(self, points, pose=None, iters=30, max_dist=None, dof=6, eps_rot=0.0, eps_trans=0.0, mode="auto", ring_cap=None, trace=None):
+        """Point-to-plane ICP of the (n, 4) float32 points against this mesh from `pose` (4 x 4, points -> this mesh's frame; None: the
+        identity): `iters` iterations enqueued as one chain, one synchronisation to read the result -> (pose (4, 4) float32 tensor,
+        info).  dof 6: rigid; 3: translation only.  The loop stops early once an update is below both eps_rot (radians) and eps_trans
+        (metres); 0 never stops.  info: status (the device's word), iterations (updates applied), converged (stopped by the gate),
+        failed (the solve of iteration `iterations` had a non-positive pivot: the pose before it is returned), trace ((iterations
+        run, 4) float32: inliers, rms residual, |w|, |t_inc|).  Without points there is nothing to solve: failed at iteration 0.
+        trace: an (iters, 4) float32 GPU tensor for the device to write into (rows of iterations that did not run are left as they are)."""
+        n = int(points.shape[0])
+        iters = int(iters)
+        start = np.eye(4, dtype=np.float32) if pose is None else np.ascontiguousarray(np.asarray(pose, np.float32).reshape(4, 4))
+        pose_d = torch.as_tensor(start.reshape(16).copy(), device=points.device)
+        status = torch.zeros(1, dtype=torch.int32, device=points.device)
+        if trace is None:
+            trace = torch.zeros((max(iters, 1), 4), dtype=torch.float32, device=points.device)
+        elif tuple(trace.shape) != (iters, 4) or iters == 0:
+            raise ValueError("the trace must hold (iters, 4) floats")
+        ws = self._align_workspace(n, points.device)
+        if int(dof) not in (3, 6) or iters < 0:
+            raise ValueError("dof is 3 or 6 and iters >= 0")
+        if n:
+            check(_lib.lib().sobfu_hip_mesh_align_estimate(*self._align_target(points, n, max_dist, mode, ring_cap), C.c_int(iters), C.c_int(int(dof)),
+                                                           _f(eps_rot), _f(eps_trans), *_ws(ws), _ptr(pose_d), _ptr(status, torch.int32), _ptr(trace),
+                                                           _stream()), "mesh_align_estimate")
+        st = int(status.item()) if n else (0x10000 if iters else 0)
+        return pose_d.reshape(4, 4), align_info(st, iters, trace.cpu().numpy())
 
     def unresolved(self):
         """how many points of the last query hit the ring cap and were finished by brute force (synchronises)"""
