@@ -40,10 +40,19 @@
 // translation only, for symmetric objects); --evaluate-pose-out FILE writes the refined pose as --evaluate-pose reads it.  --evaluate-live
 // uses the pose as given: aligning every live frame would hide the tracking error that evaluation measures.
 //
+// Depth frames from ground-truth meshes (opt-in; sobfu_amd/csrc/mesh_ray_kernels.hip): --render-mesh PATTERN is a fourth
+// frame source beside --synthetic, --data and depth files, and excludes them.  PATTERN is printf-style like --evaluate-live's: frames 0, 1, ...
+// while the file exists; without a conversion it names one static mesh, rendered for --render-frames N frames (default 1).  The meshes are
+// in the frame --evaluate reads them in (x, -y, -z); --render-pose FILE (16 numbers, as --evaluate-pose) is applied first.  Each is ray cast
+// on the GPU from the depth camera of the .ini into uint16 millimetres, which then goes the way a depth file's pixels go.  When the .ply
+// has vertex colours and --textured is given, colour frames are rendered too.  --render-mesh and --evaluate-live given the same pattern
+// and pose share one triangle grid per ground-truth frame: built once, used to render the frame and to score it.
+//
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
 //                  [--warp-mesh] [--track-mesh K] [--fit-stats]
-//                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | frame0.pgm frame1.pgm ...)
+//                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE]
+//                   [--textured] | frame0.pgm frame1.pgm ...)
 #include <dirent.h>
 #include <sys/stat.h>
 
@@ -189,7 +198,7 @@ static std::string frame_path(const std::string& pattern, int n) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -205,6 +214,8 @@ int main(int argc, char** argv) {
     int track_mesh = -1;  // the frame after which the tracked mesh is cut; -1: off
     std::string dump, mesh_dir, data_dir, mesh_format = "vtk", poses_path;
     std::string eval_gt, eval_live, eval_pose, error_dir, eval_pose_out;
+    std::string render_mesh, render_pose;  // --render-mesh: the frame source; --render-pose: applied to its meshes first
+    int render_frames = 1;
     int eval_align = -1, eval_align_dof = 6;  // --evaluate-align: the iterations; -1: off
     float eval_max_dist = -1.f;  // < 0: 5 x the truncation distance
     Screenshots shots;
@@ -243,6 +254,9 @@ int main(int argc, char** argv) {
         else if (a == "--evaluate-align-dof" && i + 1 < argc) eval_align_dof = std::atoi(argv[++i]);
         else if (a == "--evaluate-pose-out" && i + 1 < argc) eval_pose_out = argv[++i];
         else if (a == "--error-mesh" && i + 1 < argc) error_dir = argv[++i];
+        else if (a == "--render-mesh" && i + 1 < argc) render_mesh = argv[++i];
+        else if (a == "--render-frames" && i + 1 < argc) render_frames = std::atoi(argv[++i]);
+        else if (a == "--render-pose" && i + 1 < argc) render_pose = argv[++i];
         else files.push_back(a);
     }
     if (mesh_format != "vtk" && mesh_format != "ply") {
@@ -270,37 +284,45 @@ int main(int argc, char** argv) {
         p.eta = ev * p.voxel_sizes()[0];
     }
     // ground truth of --evaluate / --evaluate-live: read, posed, compared; one printed line, one optional error mesh
-    float gt_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    if (!eval_pose.empty()) {
-        FILE* f = std::fopen(eval_pose.c_str(), "r");
+    float gt_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, mesh_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    auto read_pose = [](const char* option, const std::string& path, float pose[16]) {
+        if (path.empty()) return true;
+        FILE* f = std::fopen(path.c_str(), "r");
         int got = 0;
-        while (f && got < 16 && std::fscanf(f, "%f", &gt_pose[got]) == 1) ++got;
+        while (f && got < 16 && std::fscanf(f, "%f", &pose[got]) == 1) ++got;
         if (f) std::fclose(f);
-        if (got != 16) {
-            std::printf("--evaluate-pose %s: expected 16 numbers\n", eval_pose.c_str());
-            return 2;
-        }
-    }
+        if (got != 16) std::printf("%s %s: expected 16 numbers\n", option, path.c_str());
+        return got == 16;
+    };
+    if (!read_pose("--evaluate-pose", eval_pose, gt_pose) || !read_pose("--render-pose", render_pose, mesh_pose)) return 2;
+    // the ground-truth frame of --render-mesh being rendered: its mesh (posed) and the grid over it, which --evaluate-live shares
+    struct {
+        std::string path;
+        sobfu_amd::IndexedMesh mesh;
+        sobfu_amd::TriangleGrid grid;
+    } rendered;
     if (!eval_live.empty() && frame_path(eval_live, 0).empty()) {
         std::printf("--evaluate-live needs a pattern with one %%d or %%0Nd, not %s\n", eval_live.c_str());
         return 2;
     }
     if (eval_max_dist < 0.f) eval_max_dist = 5.f * p.tsdf_trunc_dist;
     auto evaluate = [&](SobFusion& fusion, const std::string& gt_path, bool live, int n) {
-        sobfu_amd::IndexedMesh gt, model;
+        sobfu_amd::IndexedMesh read, model;
         std::string why;
-        if (!sobfu_amd::read_ply(gt_path, gt, &why)) {
+        const bool shared = live && gt_path == rendered.path && eval_pose == render_pose;  // the frame just rendered: its mesh and grid
+        if (!shared && !sobfu_amd::read_ply(gt_path, read, &why)) {
             std::printf("cannot read ground truth: %s\n", why.c_str());
             return false;
         }
+        sobfu_amd::IndexedMesh& gt = shared ? rendered.mesh : read;
         const bool align = !live && eval_align >= 0;  // the live evaluation uses the pose as given
-        if (!eval_pose.empty() && !align) sobfu_amd::transform_points(gt.vertices, gt_pose);
+        if (!eval_pose.empty() && !align && !shared) sobfu_amd::transform_points(gt.vertices, gt_pose);
         sobfu_amd::MeshComparison r;
         std::vector<float> d;
         sobfu_amd::AlignRequest request;
         std::copy(gt_pose, gt_pose + 16, request.pose);
         request.iters = eval_align, request.dof = eval_align_dof;
-        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why)
+        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why, shared ? &rendered.grid : nullptr)
                    : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr))) {
             std::printf("cannot evaluate against %s: %s\n", gt_path.c_str(), why.c_str());
             return false;
@@ -344,15 +366,53 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
-    if (textured && synthetic <= 0) {
-        std::printf("--textured needs --synthetic\n");
+    if (!render_mesh.empty() && (synthetic > 0 || !data_dir.empty() || !files.empty())) {
+        std::printf("--render-mesh excludes --synthetic, --data and depth files\n");
         return 2;
     }
-    const bool coloured = textured || !colour_files.empty();
+    if (textured && synthetic <= 0 && render_mesh.empty()) {
+        std::printf("--textured needs --synthetic or --render-mesh\n");
+        return 2;
+    }
+    const bool mesh_sequence = !frame_path(render_mesh, 0).empty();
+    int mesh_frames = 0;
+    if (!render_mesh.empty()) {
+        if (mesh_sequence) {
+            struct stat st;
+            while (stat(frame_path(render_mesh, mesh_frames).c_str(), &st) == 0) ++mesh_frames;
+        } else if (render_mesh.find('%') == std::string::npos) {
+            mesh_frames = render_frames;
+        }
+        if (mesh_frames < 1) {
+            std::printf("--render-mesh %s: no frame 0 (a pattern has one %%d or %%0Nd; a static mesh takes --render-frames N >= 1)\n", render_mesh.c_str());
+            return 2;
+        }
+    }
     kfusion::cuda::setDevice(0);
     kfusion::cuda::printShortCudaDeviceInfo(0);
+    // frame n of --render-mesh: read and posed once, one grid built over it
+    auto load_rendered = [&](int n) {
+        const std::string path = mesh_sequence ? frame_path(render_mesh, n) : render_mesh;
+        if (path == rendered.path) return true;
+        std::string why;
+        rendered.path.clear();
+        if (!sobfu_amd::read_ply(path, rendered.mesh, &why)) {
+            std::printf("cannot read the mesh to render: %s\n", why.c_str());
+            return false;
+        }
+        if (!render_pose.empty()) sobfu_amd::transform_points(rendered.mesh.vertices, mesh_pose);
+        if (!rendered.grid.build(rendered.mesh.vertices, rendered.mesh.faces, 0.f, &why)) {
+            std::printf("cannot render %s: %s\n", path.c_str(), why.c_str());
+            return false;
+        }
+        rendered.path = path;
+        return true;
+    };
+    if (!render_mesh.empty() && !load_rendered(0)) return 2;
+    const bool mesh_coloured = textured && !render_mesh.empty() && !rendered.mesh.colours.empty();
+    const bool coloured = (textured && render_mesh.empty()) || mesh_coloured || !colour_files.empty();
     SobFusion fusion(p);
-    const int nframes = synthetic > 0 ? synthetic : (int) files.size();
+    const int nframes = synthetic > 0 ? synthetic : !render_mesh.empty() ? mesh_frames : (int) files.size();
     std::vector<uint16_t> img, mask;
     std::vector<uint8_t> bgra;
     kfusion::cuda::Depth depth;
@@ -363,6 +423,22 @@ int main(int argc, char** argv) {
         if (synthetic > 0) {
             render_sphere(shift * n, 0.0, 0.75, 0.1, p.intr, p.rows, p.cols, img);
             if (textured) render_sphere_colour(shift * n, 0.0, 0.75, 0.1, p.intr, p.rows, p.cols, bgra);
+        } else if (!render_mesh.empty()) {
+            if (!load_rendered(n)) return 2;
+            if (mesh_coloured && rendered.mesh.colours.empty()) {
+                std::printf("%s has no vertex colours, unlike frame 0\n", rendered.path.c_str());
+                return 2;
+            }
+            sobfu_amd::TriangleGrid::Camera cam;  // the depth camera; the meshes are in its frame with y and z negated
+            cam.R[4] = cam.R[8] = -1.f;
+            cam.fx = p.intr.fx, cam.fy = p.intr.fy, cam.cx = p.intr.cx, cam.cy = p.intr.cy, cam.rows = p.rows, cam.cols = p.cols;
+            rendered.grid.render(cam, &depth, mesh_coloured ? &colour : nullptr, mesh_coloured ? &rendered.mesh.colours : nullptr);
+            img.resize((size_t) p.rows * p.cols);
+            depth.download(img.data(), (size_t) p.cols * sizeof(uint16_t));
+            if (mesh_coloured) {
+                bgra.resize((size_t) p.rows * p.cols * 4);
+                colour.download(bgra.data(), (size_t) p.cols * 4);
+            }
         } else {
             std::string why;
             if (!sobfu_amd::read_depth(files[n], p.rows, p.cols, img, &why)) {

@@ -2,7 +2,8 @@
 // DESIGN.md 4.9): a PLY reader, the triangle grid over the C ABI, the two-way vertex-to-surface comparison and its statistics.  Part of
 // sobfu.hpp, which includes it after IndexedMesh, DeviceArray and sobfuSafeCall: not a header to include on its own.  The Python twins are
 // sobfu_amd/mesh_io.py (read_ply) and sobfu_amd/evaluate.py (compare_meshes, align_meshes).  Automatic rigid alignment of the ground truth
-// (sobfu_amd/csrc/mesh_align_kernels.hip): TriangleGrid::align, align_meshes, format_alignment.
+// (sobfu_amd/csrc/mesh_align_kernels.hip): TriangleGrid::align, align_meshes, format_alignment.  Rays and a camera over
+// the same grid (sobfu_amd/csrc/mesh_ray_kernels.hip): TriangleGrid::raycast, TriangleGrid::render.
 #pragma once
 
 #include "../../sobfu_amd/csrc/sobfu_rigid.hpp"  // the rigid inverse, the same lines as the kernels'
@@ -303,6 +304,72 @@ public:
         a.trace.swap(trace);
         return a;
     }
+    // ---- rays against this mesh (sobfu_amd/csrc/mesh_ray_kernels.hip; ops.TriangleGrid.raycast / render) ----
+    // per ray o + t d (d not normalised): the smallest t in (t_min, t_max] at which it meets a triangle (t_max <= 0: unlimited) and the
+    // lowest triangle index there; optionally the weights (u, v) of that triangle's second and third corner and the side, +1 for the
+    // face whose corners run counter-clockwise as seen from the origin, -1 for the other.  A miss is (+Inf, -1, (0, 0), 0).
+    void raycast(const std::vector<float4>& origins, const std::vector<float4>& dirs, std::vector<float>& t, std::vector<int>& tri, float t_min = 0.f,
+                 float t_max = 0.f, std::vector<float2>* bary = nullptr, std::vector<signed char>* side = nullptr, int mode = SOBFU_MESH_DISTANCE_AUTO) {
+        if (!built_) kfusion::cuda::error("TriangleGrid::raycast without a built grid", __FILE__, __LINE__);
+        if (origins.size() != dirs.size()) kfusion::cuda::error("TriangleGrid::raycast: one direction per origin", __FILE__, __LINE__);
+        const size_t n = origins.size();
+        t.assign(n, INFINITY), tri.assign(n, -1);
+        if (bary) bary->assign(n, make_float2(0.f, 0.f));
+        if (side) side->assign(n, 0);
+        if (n == 0) return;
+        kfusion::cuda::DeviceArray<float4> dorg, ddir;
+        kfusion::cuda::DeviceArray<float> dt(n);
+        kfusion::cuda::DeviceArray<int> dtri(n);
+        kfusion::cuda::DeviceArray<float2> dbary;
+        kfusion::cuda::DeviceArray<signed char> dside;
+        dorg.upload(origins), ddir.upload(dirs);
+        if (bary) dbary.create(n);
+        if (side) dside.create(n);
+        sobfuSafeCall(sobfu_hip_mesh_raycast(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
+                                             nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dorg.ptr(), (const float*) ddir.ptr(), (int) n,
+                                             t_min, t_max, mode, dt.ptr(), dtri.ptr(), bary ? (float*) dbary.ptr() : nullptr,
+                                             side ? (int8_t*) dside.ptr() : nullptr, nullptr));
+        dt.download(t), dtri.download(tri);
+        if (bary) dbary.download(*bary);
+        if (side) dside.download(*side);
+    }
+    // The mesh seen by a pinhole camera: (R row-major, t) takes the mesh's frame to the camera frame (the pose of sobfu_hip_raycast), depths
+    // limited to (z_min, z_max] (z_max <= 0: unlimited).  Every output is optional: depth, uint16 millimetres, 0 for a miss; points and
+    // normals in sobfu_hip_raycast's format; colour (needs vertex_colours, one per vertex), BGRA with alpha 255 on a hit; tri, -1 for a
+    // miss.  vertex_normals (one per vertex) are mixed over the face; without them the face's own normal is used.
+    struct Camera {
+        float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+        float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f;
+        int rows = 0, cols = 0;
+        float z_min = 0.f, z_max = 0.f;
+    };
+    void render(const Camera& cam, kfusion::cuda::Depth* depth, kfusion::cuda::DeviceArray2D<kfusion::RGB>* colour = nullptr,
+                const std::vector<kfusion::RGB>* vertex_colours = nullptr, kfusion::cuda::DeviceArray2D<float4>* points = nullptr,
+                kfusion::cuda::DeviceArray2D<float4>* normals = nullptr, const std::vector<float4>* vertex_normals = nullptr,
+                kfusion::cuda::DeviceArray2D<int>* tri = nullptr) {
+        if (!built_) kfusion::cuda::error("TriangleGrid::render without a built grid", __FILE__, __LINE__);
+        if ((vertex_colours && (int) vertex_colours->size() != nv_) || (vertex_normals && (int) vertex_normals->size() != nv_) || (colour && !vertex_colours))
+            kfusion::cuda::error("TriangleGrid::render: one normal / colour per vertex, and colours for a colour image", __FILE__, __LINE__);
+        kfusion::cuda::DeviceArray<kfusion::RGB> dcol;
+        kfusion::cuda::DeviceArray<float4> dnrm;
+        if (vertex_colours && nv_) dcol.upload(*vertex_colours);
+        if (vertex_normals && nv_) dnrm.upload(*vertex_normals);
+        if (depth) depth->create(cam.rows, cam.cols);
+        if (colour) colour->create(cam.rows, cam.cols);
+        if (points) points->create(cam.rows, cam.cols);
+        if (normals) normals->create(cam.rows, cam.cols);
+        if (tri) tri->create(cam.rows, cam.cols);
+        sobfuSafeCall(sobfu_hip_mesh_render(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
+                                            nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, vertex_normals && nv_ ? (const float*) dnrm.ptr() : nullptr,
+                                            vertex_colours && nv_ ? (const uint8_t*) dcol.ptr() : nullptr, cam.R, cam.t, cam.fx, cam.fy, cam.cx, cam.cy, cam.rows,
+                                            cam.cols, cam.z_min, cam.z_max, depth ? depth->ptr() : nullptr, depth ? (int) depth->step() : 0,
+                                            points ? (float*) points->ptr() : nullptr, points ? (int) points->step() : 0,
+                                            normals ? (float*) normals->ptr() : nullptr, normals ? (int) normals->step() : 0,
+                                            colour ? (uint8_t*) colour->ptr() : nullptr, colour ? (int) colour->step() : 0, tri ? tri->ptr() : nullptr,
+                                            tri ? (int) tri->step() : 0, nullptr));
+        sobfuSafeCall(hipDeviceSynchronize());  // the vertex attributes uploaded above are released on return
+    }
+    bool built() const { return built_; }
     int references() const { return references_; }
     const int* dims() const { return dims_; }
     float cell() const { return h_; }
@@ -341,10 +408,13 @@ inline DistanceStats distance_stats(const std::vector<float>& dist) {
     return s;
 }
 // a = the model, b = the ground truth, by convention; vertex-to-surface both ways.  false: one of the meshes is refused (TriangleGrid::build)
+// grid_b (optional): a grid already built over b -- the one its depth frame was rendered through -- used instead of building another
 inline bool compare_meshes(const IndexedMesh& a, const IndexedMesh& b, float max_dist, MeshComparison& out, std::vector<float>* d_ab = nullptr,
-                           std::vector<float>* d_ba = nullptr, std::string* why = nullptr) {
-    TriangleGrid ga, gb;
-    if (!gb.build(b.vertices, b.faces, 0.f, why) || !ga.build(a.vertices, a.faces, 0.f, why)) return false;
+                           std::vector<float>* d_ba = nullptr, std::string* why = nullptr, TriangleGrid* grid_b = nullptr) {
+    TriangleGrid ga, own;
+    if (!grid_b && !own.build(b.vertices, b.faces, 0.f, why)) return false;
+    TriangleGrid& gb = grid_b ? *grid_b : own;
+    if (!ga.build(a.vertices, a.faces, 0.f, why)) return false;
     std::vector<float> ab, ba;
     gb.query(a.vertices, ab, max_dist);
     ga.query(b.vertices, ba, max_dist);

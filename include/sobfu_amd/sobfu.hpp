@@ -1438,10 +1438,11 @@ public:
         if (model) *model = std::move(m);
         return ok;
     }
+    // gt_grid (optional): a grid already built over gt, used instead of building another
     bool evaluate_live(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
-                       std::vector<float>* d_model = nullptr, std::string* why = nullptr) {
+                       std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::TriangleGrid* gt_grid = nullptr) {
         sobfu_amd::IndexedMesh m = get_phi_global_warped_indexed_mesh();
-        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why);
+        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, gt_grid);
         if (model) *model = std::move(m);
         return ok;
     }

@@ -633,6 +633,38 @@ int sobfu_hip_mesh_align_estimate(void* d_grid_workspace, size_t grid_workspace_
                                   int mode, int ring_cap, int iters, int dof, float eps_rot, float eps_trans, void* d_workspace, size_t workspace_bytes,
                                   float* d_pose, int* d_status, float* d_trace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mesh rays  (no counterpart in the reference; sobfu_amd/csrc/mesh_ray_kernels.hip)
+ * Rays against the mesh and grid of sobfu_hip_mesh_grid_build (the same arrays and plan, unchanged; the workspace is only read).  Per ray
+ * o + t d, d not normalised: t = the smallest parameter in (t_min, t_max] at which it meets a triangle (the watertight fp32 rule of
+ * sobfu_amd/csrc/sobfu_mesh_ray.hpp, two-sided), tri = the lowest triangle index at that t, bary = (u, v), the weights of the triangle's
+ * second and third corner, side = +1 where the ray meets the face whose corners run counter-clockwise as seen from its origin, -1 for
+ * the other face.  A miss is (+Inf, -1, (0, 0), 0): no triangles, a workspace that is not marked as built, a ray that passes the grid's
+ * box, a zero or non-finite origin or direction.  The answer is the same bit for bit whichever mode finds it and from run to run.
+ * Every argument is checked before any device call (SOBFU_E_BADARG).  Asynchronous.
+ * ---------------------------------------------------------------------------------------------------- */
+/* n rays as two dense float4 arrays (w ignored).  t_min: finite; t_max <= 0 or +Inf: unlimited.  mode: SOBFU_MESH_DISTANCE_AUTO (the grid
+ * walk; brute force for meshes of at most 64 triangles), _GRID or _BRUTE.  d_bary (float2 per ray) and d_side (int8 per ray) may be NULL.
+ * n = 0 succeeds and launches nothing. */
+int sobfu_hip_mesh_raycast(void* d_workspace, size_t workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                           int n_triangles, const float origin[3], float h, const int dims[3], const float* d_origins, const float* d_dirs, int n,
+                           float t_min, float t_max, int mode, float* d_t, int* d_tri, float* d_bary, int8_t* d_side, void* stream);
+/* The mesh seen by a pinhole camera: pixel (u, v) casts ((u - cx) / fx, (v - cy) / fy, 1) from the camera of (R row-major, t), mesh frame
+ * -> camera frame -- the pose argument of sobfu_hip_raycast and sobfu_hip_integrate_depth -- so the ray parameter is the depth z, limited
+ * to (z_min, z_max] as t is above.  Outputs, pitched (step in bytes), each may be NULL:
+ *   d_depth    uint16 millimetres, rint(1000 z); 0 for a miss and for z beyond 65.535 m
+ *   d_points   float4 (x, y, z, 0) in the camera frame, d_normals float4 (nx, ny, nz, 1): sobfu_hip_raycast's format, a miss all zero.
+ *              The normal is the barycentric mix of d_vertex_normals (dense float4 per vertex) or, without them, the face's; turned to
+ *              face the camera, rotated into its frame and normalised
+ *   d_colour   8-bit BGRA: the barycentric mix of d_vertex_colours (4 bytes per vertex, kfusion::RGB order), rounded to nearest, alpha
+ *              255; a miss (0, 0, 0, 0).  Needs d_vertex_colours
+ *   d_tri      int32, the triangle's index; a miss -1 */
+int sobfu_hip_mesh_render(void* d_workspace, size_t workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles,
+                          const float origin[3], float h, const int dims[3], const float* d_vertex_normals, const uint8_t* d_vertex_colours,
+                          const float R[9], const float t[3], float fx, float fy, float cx, float cy, int rows, int cols, float z_min, float z_max,
+                          uint16_t* d_depth, int depth_step, float* d_points, int points_step, float* d_normals, int normals_step,
+                          uint8_t* d_colour, int colour_step, int32_t* d_tri, int tri_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

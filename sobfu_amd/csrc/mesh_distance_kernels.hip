@@ -5,7 +5,8 @@
 //   answer   per point: min over all triangles of d2 (closest_on_triangle), the LOWEST triangle index attaining it, that triangle's
 //            closest point; dist = sqrt(min d2).  With max_dist: dist > max_dist -> (+Inf, -1, (0, 0, 0, 0)).  No triangles: the same.
 //            The answer does not depend on the path that finds it: grid and brute force agree bit for bit, run after run.
-//   grid     a uniform grid of cubic cells over the mesh's box (the plan: sobfu_mesh_grid.hpp).  A triangle is referenced from every
+//   grid     a uniform grid of cubic cells over the mesh's box (the plan: sobfu_mesh_grid.hpp; the workspace's layout, shared with the ray
+//            kernels that read it: sobfu_mesh_grid_ws.hpp).  A triangle is referenced from every
 //            cell its axis-aligned box overlaps.  build: count per cell (integer atomics) -> exclusive scan (sobfu_scan.hpp) -> fill
 //            (cursors: the counts, counted back down).  The order of the references inside a cell varies from run to run; the answer
 //            does not (the tie rule).  The count pass also raises a flag for a face index outside [0, n_vertices) or a non-finite
@@ -21,47 +22,13 @@
 //   brute    a 256-lane workgroup per 256 points, the triangles staged through LDS 256 at a time (48 B each), every lane testing the
 //            same triangle (a broadcast LDS read) in ascending index order.  Also the whole call for mode brute and for tiny meshes.
 #include "sobfu_hip.h"
-#include "sobfu_host.hpp"
-#include "sobfu_mesh_distance.hpp"
-#include "sobfu_mesh_grid.hpp"
-#include "sobfu_scan.hpp"
+#include "sobfu_mesh_grid_ws.hpp"
 
 using namespace sobfu_hip;
 
 namespace {
 
 constexpr float kMeshMargin = 1e-4f;
-// workspace header (ints): 0 bad-input flag, 1 unresolved points of the last query, 2-3 references counted (64 bit), 5 built marker
-constexpr int kHdrInts = 16, kHdrBad = 0, kHdrUnresolved = 1, kHdrRefs = 2, kHdrBuilt = 5;
-
-struct Grid {
-    int* hdr;
-    int* count;  // ncells + 1: the build's cursors (all 0 afterwards)
-    int* start;  // ncells + 1: exclusive scan of the counts; start[ncells] = the number of references
-    int* blk;    // the scan's per-block sums
-    int* refs;
-    float ox, oy, oz, h;
-    int dx, dy, dz;
-    int max_refs;
-};
-
-size_t ncells_of(const int dims[3]) { return (size_t) dims[0] * dims[1] * dims[2]; }
-size_t grid_ints(const int dims[3], int max_refs) {
-    const size_t nc = ncells_of(dims) + 1, nb = (nc + kChunk - 1) / kChunk;
-    return kHdrInts + 2 * nc + nb + 1 + (size_t) max_refs;
-}
-Grid grid_of(void* ws, const float origin[3], float h, const int dims[3], int max_refs) {
-    const size_t nc = ncells_of(dims) + 1, nb = (nc + kChunk - 1) / kChunk;
-    Grid g;
-    g.hdr = (int*) ws, g.count = g.hdr + kHdrInts, g.start = g.count + nc, g.blk = g.start + nc, g.refs = g.blk + nb + 1;
-    g.ox = origin[0], g.oy = origin[1], g.oz = origin[2], g.h = h;
-    g.dx = dims[0], g.dy = dims[1], g.dz = dims[2], g.max_refs = max_refs;
-    return g;
-}
-
-SOBFU_DEV int cell_of(float x, float o, float h, int dim) { return (int) fminf(fmaxf(floorf((x - o) / h), 0.f), (float) (dim - 1)); }
-SOBFU_DEV P3 p3(const float4& v) { return P3{v.x, v.y, v.z}; }
-SOBFU_DEV bool finite3(const float4& v) { return fabsf(v.x) < INFINITY && fabsf(v.y) < INFINITY && fabsf(v.z) < INFINITY; }
 
 // one lane per triangle: FILL = false counts the cells its box overlaps (and checks it), FILL = true writes the references
 template <bool FILL>
@@ -211,14 +178,6 @@ __global__ void __launch_bounds__(256) brute_force_kernel(const int* __restrict_
     if (active) write_answer(a, i, best);
 }
 
-bool grid_args_ok(const void* ws, size_t ws_bytes, const float origin[3], float h, const int dims[3], int max_refs) {
-    return ws && aligned(ws, 0, 16) && max_refs >= 0 && mesh_grid_plan_ok(origin, h, dims) && ws_bytes >= grid_ints(dims, max_refs) * sizeof(int);
-}
-bool mesh_args_ok(const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles) {
-    return n_vertices >= 0 && n_triangles >= 0 && (n_triangles == 0 || (d_vertices && d_faces)) && aligned(d_vertices, 0, 16) &&
-           aligned(d_faces, 0, 4);
-}
-
 }  // namespace
 
 extern "C" {
@@ -280,8 +239,7 @@ int sobfu_hip_mesh_distance(void* d_workspace, size_t workspace_bytes, const flo
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t) stream;
     const Grid g   = grid_of(d_workspace, origin, h, dims, 0);
-    float box_l    = 0.f;
-    for (int i = 0; i < 3; ++i) box_l = std::fmax(box_l, std::fmax(std::fabs(origin[i]), std::fabs(origin[i] + (float) dims[i] * h)));
+    const float box_l = grid_box_l(origin, h, dims);
     const Query q{(const float4*) d_vertices, d_faces, n_triangles, (const float4*) d_points, n,
                   max_dist > 0.f ? max_dist : INFINITY, box_l, ring_cap > 0 ? ring_cap : kMeshGridRingCap, d_dist, d_tri, (float4*) d_closest,
                   d_unresolved};

@@ -753,6 +753,79 @@ class TriangleGrid:
         st = int(status.item()) if n else (0x10000 if iters else 0)
         return pose_d.reshape(4, 4), align_info(st, iters, trace.cpu().numpy())
 
+    # ---- rays against this mesh (sobfu_amd/csrc/mesh_ray_kernels.hip) ----
+    def raycast(self, origins, dirs, t_min=0.0, t_max=None, mode="auto", bary=False, side=False):
+        """(n, 4) float32 origins and directions (not normalised, w ignored) -> t (n,) float32, tri (n,) int32 [, bary (n, 2) float32]
+        [, side (n,) int8]: the smallest ray parameter in (t_min, t_max] at which the ray meets a triangle, the lowest triangle index at
+        that parameter, the weights of its second and third corner, and +1 / -1 for the face whose corners run counter-clockwise /
+        clockwise as seen from the origin.  A miss is (+Inf, -1, (0, 0), 0).  t_max None: unlimited.  mode "auto" | "grid" | "brute"
+        never changes the answer."""
+        if mode not in _MESH_MODES:
+            raise ValueError(f"unknown mode {mode!r}")
+        n = int(origins.shape[0])
+        if int(dirs.shape[0]) != n:
+            raise ValueError("origins and dirs must hold the same number of rays")
+        dev = origins.device
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        tri = torch.empty(n, dtype=torch.int32, device=dev)
+        b = torch.empty((n, 2), dtype=torch.float32, device=dev) if bary else None
+        s = torch.empty(n, dtype=torch.int8, device=dev) if side else None
+        if n:
+            check(_lib.lib().sobfu_hip_mesh_raycast(*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(origins, "origins"),
+                                                    _point_list(dirs, "dirs"), C.c_int(n), _f(t_min), _f(0.0 if t_max is None else t_max),
+                                                    C.c_int(_MESH_MODES[mode]), _ptr(t), _ptr(tri, torch.int32), None if b is None else _ptr(b),
+                                                    None if s is None else _ptr(s, torch.int8), _stream()), "mesh_raycast")
+        return tuple(x for x in (t, tri, b, s) if x is not None)
+
+    def render(self, intr, rows, cols, pose=None, z_min=0.0, z_max=None, vertex_normals=None, vertex_colours=None, outputs=("depth",)):
+        """This mesh seen by the pinhole camera intr = (fx, fy, cx, cy) at `pose` = (R, t), mesh frame -> camera frame (the pose raycast
+        and integrate_depth take; None: the identity) -> a dict with the images named in `outputs`: "depth" (rows, cols) int16, the
+        bits of uint16 millimetres as the depth pre-steps take them (0: a miss), "points" and "normals" (rows, cols, 4) float32 in ops.raycast's format, "colour" (rows, cols, 4) uint8
+        BGRA (needs vertex_colours, (V, 4) uint8 BGRA), "tri" (rows, cols) int32 (-1: a miss).  vertex_normals: (V, 4) float32, mixed
+        over the face; None: the face's own normal.  Depths are limited to (z_min, z_max]; z_max None: unlimited.  An entry of
+        `outputs` may also be given as a dict name -> tensor to render into existing (possibly pitched) images."""
+        given = dict(outputs) if isinstance(outputs, dict) else {name: None for name in outputs}
+        kinds = {"depth": (torch.int16, 0), "points": (torch.float32, 4), "normals": (torch.float32, 4), "colour": (torch.uint8, 4), "tri": (torch.int32, 0)}
+        unknown = set(given) - set(kinds)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        if "colour" in given and vertex_colours is None:
+            raise ValueError("the colour output needs vertex_colours")
+        R, t = (np.eye(3), (0.0, 0.0, 0.0)) if pose is None else pose
+        Rm, tv = _pose(R, t)
+        dev = self.vertices.device
+        args = []
+        for name in ("depth", "points", "normals", "colour", "tri"):
+            dtype, ch = kinds[name]
+            if name not in given:
+                args += [None, C.c_int(0)]
+                continue
+            img = given[name]
+            if img is None:
+                img = given[name] = torch.empty((rows, cols, ch) if ch else (rows, cols), dtype=dtype, device=dev)
+            if ch:
+                args += list(_image_ptr(img, dtype, ch))
+            else:
+                sixteen = name == "depth" and img.dtype == torch.uint16  # the same bits
+                if not (img.is_cuda and (img.dtype == dtype or sixteen) and img.dim() == 2 and img.stride(1) == 1):
+                    raise ValueError(f"expected a (rows, cols) {dtype} image on the GPU with contiguous rows, got {img.dtype} {tuple(img.shape)}")
+                args += [C.c_void_p(img.data_ptr()), C.c_int(img.stride(0) * img.element_size())]
+            if tuple(img.shape[:2]) != (rows, cols):
+                raise ValueError(f"the {name} image must be {rows} x {cols}")
+        vn = None if vertex_normals is None else _point_list(vertex_normals, "vertex_normals")
+        vc = None
+        if vertex_colours is not None:
+            if not (vertex_colours.dim() == 2 and vertex_colours.shape[1] == 4):
+                raise ValueError("expected (V, 4) uint8 vertex colours")
+            vc = _ptr(vertex_colours, torch.uint8)
+        for v in (vertex_normals, vertex_colours):
+            if v is not None and int(v.shape[0]) != self.n_vertices:
+                raise ValueError("one normal / colour per vertex")
+        check(_lib.lib().sobfu_hip_mesh_render(*_ws(self.workspace), *self._mesh(), *self._plan, vn, vc, Rm, tv, _f(intr[0]), _f(intr[1]), _f(intr[2]),
+                                               _f(intr[3]), C.c_int(int(rows)), C.c_int(int(cols)), _f(z_min), _f(0.0 if z_max is None else z_max),
+                                               *args, _stream()), "mesh_render")
+        return given
+
     def unresolved(self):
         """how many points of the last query hit the ring cap and were finished by brute force (synchronises)"""
         n = C.c_int(0)
