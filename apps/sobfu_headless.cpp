@@ -48,11 +48,19 @@
 // has vertex colours and --textured is given, colour frames are rendered too.  --render-mesh and --evaluate-live given the same pattern
 // and pose share one triangle grid per ground-truth frame: built once, used to render the frame and to score it.
 //
+// Volumes from ground-truth meshes (opt-in; sobfu_amd/csrc/mesh_voxel_kernels.hip): --voxelise-mesh PATTERN is a fifth frame
+// source that takes --render-mesh's place and its --render-frames / --render-pose: every closed mesh reaches the solver as a full signed
+// TSDF (SobFusion::integrate_mesh), without a depth camera in between; a mesh that is not closed ends the run.  It shares the mesh and the
+// scoring grid with --evaluate-live as --render-mesh does (the voxelisation builds a grid of its own over the vertices in the volume's
+// frame).  --evaluate-signed adds signed_mean, inside and open to each side of the evaluate lines: the sign of a vertex against the
+// other mesh, > 0 outside.
+//
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
 //                  [--warp-mesh] [--track-mesh K] [--fit-stats]
 //                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE]
-//                   [--textured] | frame0.pgm frame1.pgm ...)
+//                   [--textured] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | frame0.pgm frame1.pgm ...)
+//                  [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-signed]
 #include <dirent.h>
 #include <sys/stat.h>
 
@@ -198,7 +206,7 @@ static std::string frame_path(const std::string& pattern, int n) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--evaluate-signed] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -215,6 +223,7 @@ int main(int argc, char** argv) {
     std::string dump, mesh_dir, data_dir, mesh_format = "vtk", poses_path;
     std::string eval_gt, eval_live, eval_pose, error_dir, eval_pose_out;
     std::string render_mesh, render_pose;  // --render-mesh: the frame source; --render-pose: applied to its meshes first
+    bool voxelise = false, eval_signed = false;  // --voxelise-mesh: the meshes reach the solver as volumes, not as depth frames
     int render_frames = 1;
     int eval_align = -1, eval_align_dof = 6;  // --evaluate-align: the iterations; -1: off
     float eval_max_dist = -1.f;  // < 0: 5 x the truncation distance
@@ -254,7 +263,21 @@ int main(int argc, char** argv) {
         else if (a == "--evaluate-align-dof" && i + 1 < argc) eval_align_dof = std::atoi(argv[++i]);
         else if (a == "--evaluate-pose-out" && i + 1 < argc) eval_pose_out = argv[++i];
         else if (a == "--error-mesh" && i + 1 < argc) error_dir = argv[++i];
-        else if (a == "--render-mesh" && i + 1 < argc) render_mesh = argv[++i];
+        else if (a == "--render-mesh" && i + 1 < argc) {
+            if (voxelise) {
+                std::printf("--voxelise-mesh and --render-mesh exclude each other\n");
+                return 2;
+            }
+            render_mesh = argv[++i];
+        }
+        else if (a == "--voxelise-mesh" && i + 1 < argc) {
+            if (!render_mesh.empty()) {
+                std::printf("--voxelise-mesh and --render-mesh exclude each other\n");
+                return 2;
+            }
+            render_mesh = argv[++i], voxelise = true;
+        }
+        else if (a == "--evaluate-signed") eval_signed = true;
         else if (a == "--render-frames" && i + 1 < argc) render_frames = std::atoi(argv[++i]);
         else if (a == "--render-pose" && i + 1 < argc) render_pose = argv[++i];
         else files.push_back(a);
@@ -322,8 +345,8 @@ int main(int argc, char** argv) {
         sobfu_amd::AlignRequest request;
         std::copy(gt_pose, gt_pose + 16, request.pose);
         request.iters = eval_align, request.dof = eval_align_dof;
-        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why, shared ? &rendered.grid : nullptr)
-                   : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr))) {
+        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why, shared ? &rendered.grid : nullptr, eval_signed)
+                   : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr, eval_signed))) {
             std::printf("cannot evaluate against %s: %s\n", gt_path.c_str(), why.c_str());
             return false;
         }
@@ -367,11 +390,15 @@ int main(int argc, char** argv) {
         }
     }
     if (!render_mesh.empty() && (synthetic > 0 || !data_dir.empty() || !files.empty())) {
-        std::printf("--render-mesh excludes --synthetic, --data and depth files\n");
+        std::printf("%s excludes --synthetic, --data and depth files\n", voxelise ? "--voxelise-mesh" : "--render-mesh");
         return 2;
     }
-    if (textured && synthetic <= 0 && render_mesh.empty()) {
+    if (textured && ((synthetic <= 0 && render_mesh.empty()) || voxelise)) {
         std::printf("--textured needs --synthetic or --render-mesh\n");
+        return 2;
+    }
+    if (voxelise && (!shots.dir.empty() || p.track_camera)) {
+        std::printf("--voxelise-mesh has no depth camera: it excludes --screenshots and --track\n");
         return 2;
     }
     const bool mesh_sequence = !frame_path(render_mesh, 0).empty();
@@ -384,7 +411,7 @@ int main(int argc, char** argv) {
             mesh_frames = render_frames;
         }
         if (mesh_frames < 1) {
-            std::printf("--render-mesh %s: no frame 0 (a pattern has one %%d or %%0Nd; a static mesh takes --render-frames N >= 1)\n", render_mesh.c_str());
+            std::printf("%s %s: no frame 0 (a pattern has one %%d or %%0Nd; a static mesh takes --render-frames N >= 1)\n", voxelise ? "--voxelise-mesh" : "--render-mesh", render_mesh.c_str());
             return 2;
         }
     }
@@ -429,15 +456,17 @@ int main(int argc, char** argv) {
                 std::printf("%s has no vertex colours, unlike frame 0\n", rendered.path.c_str());
                 return 2;
             }
-            sobfu_amd::TriangleGrid::Camera cam;  // the depth camera; the meshes are in its frame with y and z negated
-            cam.R[4] = cam.R[8] = -1.f;
-            cam.fx = p.intr.fx, cam.fy = p.intr.fy, cam.cx = p.intr.cx, cam.cy = p.intr.cy, cam.rows = p.rows, cam.cols = p.cols;
-            rendered.grid.render(cam, &depth, mesh_coloured ? &colour : nullptr, mesh_coloured ? &rendered.mesh.colours : nullptr);
-            img.resize((size_t) p.rows * p.cols);
-            depth.download(img.data(), (size_t) p.cols * sizeof(uint16_t));
-            if (mesh_coloured) {
-                bgra.resize((size_t) p.rows * p.cols * 4);
-                colour.download(bgra.data(), (size_t) p.cols * 4);
+            if (!voxelise) {  // --voxelise-mesh renders no frame: the mesh itself is integrated below
+                sobfu_amd::TriangleGrid::Camera cam;  // the depth camera; the meshes are in its frame with y and z negated
+                cam.R[4] = cam.R[8] = -1.f;
+                cam.fx = p.intr.fx, cam.fy = p.intr.fy, cam.cx = p.intr.cx, cam.cy = p.intr.cy, cam.rows = p.rows, cam.cols = p.cols;
+                rendered.grid.render(cam, &depth, mesh_coloured ? &colour : nullptr, mesh_coloured ? &rendered.mesh.colours : nullptr);
+                img.resize((size_t) p.rows * p.cols);
+                depth.download(img.data(), (size_t) p.cols * sizeof(uint16_t));
+                if (mesh_coloured) {
+                    bgra.resize((size_t) p.rows * p.cols * 4);
+                    colour.download(bgra.data(), (size_t) p.cols * 4);
+                }
             }
         } else {
             std::string why;
@@ -461,9 +490,16 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
-        depth.upload(img.data(), (size_t) p.cols * sizeof(uint16_t), p.rows, p.cols);  // demo.cpp:327-329
-        if (coloured) colour.upload(bgra.data(), (size_t) p.cols * 4, p.rows, p.cols);
-        {
+        if (voxelise) {
+            std::string why;
+            kfusion::SampledScopeTime fps(time_ms);
+            if (!fusion.integrate_mesh(rendered.mesh, sobfu_amd::mesh_frame(), false, &why)) {
+                std::printf("cannot voxelise %s: %s\n", rendered.path.c_str(), why.c_str());
+                return 2;
+            }
+        } else {
+            depth.upload(img.data(), (size_t) p.cols * sizeof(uint16_t), p.rows, p.cols);  // demo.cpp:327-329
+            if (coloured) colour.upload(bgra.data(), (size_t) p.cols * 4, p.rows, p.cols);
             kfusion::SampledScopeTime fps(time_ms);  // demo.cpp:331 -- "avg. frame time" every 34 frames
             if (coloured) fusion(depth, colour);
             else fusion(depth);

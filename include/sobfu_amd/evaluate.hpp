@@ -3,7 +3,9 @@
 // sobfu.hpp, which includes it after IndexedMesh, DeviceArray and sobfuSafeCall: not a header to include on its own.  The Python twins are
 // sobfu_amd/mesh_io.py (read_ply) and sobfu_amd/evaluate.py (compare_meshes, align_meshes).  Automatic rigid alignment of the ground truth
 // (sobfu_amd/csrc/mesh_align_kernels.hip): TriangleGrid::align, align_meshes, format_alignment.  Rays and a camera over
-// the same grid (sobfu_amd/csrc/mesh_ray_kernels.hip): TriangleGrid::raycast, TriangleGrid::render.
+// the same grid (sobfu_amd/csrc/mesh_ray_kernels.hip): TriangleGrid::raycast, TriangleGrid::render.  Closed meshes as signed
+// TSDF volumes and the inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip): TriangleGrid::voxelise,
+// TriangleGrid::inside, mesh_to_tsdf, and the signed fields of compare_meshes.
 #pragma once
 
 #include "../../sobfu_amd/csrc/sobfu_rigid.hpp"  // the rigid inverse, the same lines as the kernels'
@@ -369,6 +371,38 @@ public:
                                             tri ? (int) tri->step() : 0, nullptr));
         sobfuSafeCall(hipDeviceSynchronize());  // the vertex attributes uploaded above are released on return
     }
+    // ---- this mesh, closed, as a signed TSDF volume and an inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip, DESIGN.md 4.12;
+    // ops.TriangleGrid.voxelise / inside) ----
+    // d_vol: dims[0] x dims[1] x dims[2] float2 {tsdf, weight} on the device, the mesh's vertices being in the volume's frame: voxel i of
+    // an axis has its centre at i vs + vs / 2; tsdf = clamp(s / trunc, -1, 1), s the exact distance to the mesh, negative inside; weight =
+    // s > -eta.  -> the number of rows along x that cross the mesh an odd number of times: 0 for a closed mesh (synchronises)
+    int voxelise(float* d_vol, const int dims[3], const float vs[3], float trunc, float eta, int mode = SOBFU_MESH_DISTANCE_AUTO) {
+        if (!built_) kfusion::cuda::error("TriangleGrid::voxelise without a built grid", __FILE__, __LINE__);
+        const size_t bytes = sobfu_hip_mesh_voxelise_workspace_bytes(dims[0], dims[1], dims[2]);
+        if (bytes == 0) kfusion::cuda::error("TriangleGrid::voxelise: at most 512 voxels along x", __FILE__, __LINE__);
+        kfusion::cuda::DeviceArray<unsigned char> ws(bytes);
+        kfusion::cuda::DeviceArray<int> open_rows(1);
+        sobfuSafeCall(sobfu_hip_mesh_voxelise(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
+                                              nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, d_vol, dims[0], dims[1], dims[2], vs, trunc, eta, mode,
+                                              ws.ptr(), ws.size(), open_rows.ptr(), nullptr));
+        std::vector<int> n;
+        open_rows.download(n);
+        return n[0];
+    }
+    // per point: inside = 1 where the row from it along +x crosses the mesh an odd number of times; open = 1 where its whole row does
+    void inside(const std::vector<float4>& points, std::vector<unsigned char>& inside, std::vector<unsigned char>& open, int mode = SOBFU_MESH_DISTANCE_AUTO) {
+        if (!built_) kfusion::cuda::error("TriangleGrid::inside without a built grid", __FILE__, __LINE__);
+        const size_t n = points.size();
+        inside.assign(n, 0), open.assign(n, 0);
+        if (n == 0) return;
+        kfusion::cuda::DeviceArray<float4> dp;
+        kfusion::cuda::DeviceArray<unsigned char> di(n), dopen(n);
+        dp.upload(points);
+        sobfuSafeCall(sobfu_hip_mesh_inside(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
+                                            nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dp.ptr(), (int) n, di.ptr(), dopen.ptr(), mode,
+                                            nullptr));
+        di.download(inside), dopen.download(open);
+    }
     bool built() const { return built_; }
     int references() const { return references_; }
     const int* dims() const { return dims_; }
@@ -387,6 +421,11 @@ private:
 struct DistanceStats {
     size_t n = 0, within = 0;
     double mean = 0, rms = 0, median = 0, max = 0;
+    // compare_meshes(..., with_signs): the mean over the finite distances, each negative where its vertex is inside the other mesh; how
+    // many of those vertices are inside; how many of ALL the vertices lie on a row that crosses the other mesh an odd number of times
+    bool has_signs = false;
+    double signed_mean = 0;
+    size_t inside = 0, open = 0;
 };
 struct MeshComparison {
     DistanceStats a_to_b, b_to_a;
@@ -409,8 +448,21 @@ inline DistanceStats distance_stats(const std::vector<float>& dist) {
 }
 // a = the model, b = the ground truth, by convention; vertex-to-surface both ways.  false: one of the meshes is refused (TriangleGrid::build)
 // grid_b (optional): a grid already built over b -- the one its depth frame was rendered through -- used instead of building another
+inline void add_signs(DistanceStats& s, const std::vector<float>& dist, const std::vector<unsigned char>& inside, const std::vector<unsigned char>& open) {
+    double sum = 0;
+    s.has_signs = true, s.signed_mean = 0, s.inside = s.open = 0;
+    for (size_t i = 0; i < dist.size(); ++i) {
+        s.open += open[i] != 0;
+        if (!std::isfinite(dist[i])) continue;
+        sum += inside[i] ? -(double) dist[i] : (double) dist[i];
+        s.inside += inside[i] != 0;
+    }
+    if (s.within) s.signed_mean = sum / (double) s.within;
+}
+// with_signs: each direction gains signed_mean, inside and open -- the sign of the query vertex against the OTHER mesh (TriangleGrid::inside),
+// which should be closed; the unsigned fields are the same with and without
 inline bool compare_meshes(const IndexedMesh& a, const IndexedMesh& b, float max_dist, MeshComparison& out, std::vector<float>* d_ab = nullptr,
-                           std::vector<float>* d_ba = nullptr, std::string* why = nullptr, TriangleGrid* grid_b = nullptr) {
+                           std::vector<float>* d_ba = nullptr, std::string* why = nullptr, TriangleGrid* grid_b = nullptr, bool with_signs = false) {
     TriangleGrid ga, own;
     if (!grid_b && !own.build(b.vertices, b.faces, 0.f, why)) return false;
     TriangleGrid& gb = grid_b ? *grid_b : own;
@@ -420,19 +472,32 @@ inline bool compare_meshes(const IndexedMesh& a, const IndexedMesh& b, float max
     ga.query(b.vertices, ba, max_dist);
     out.a_to_b = distance_stats(ab), out.b_to_a = distance_stats(ba);
     out.chamfer = 0.5 * (out.a_to_b.mean + out.b_to_a.mean), out.hausdorff = std::max(out.a_to_b.max, out.b_to_a.max);
+    if (with_signs) {
+        std::vector<unsigned char> in, open;
+        gb.inside(a.vertices, in, open);
+        add_signs(out.a_to_b, ab, in, open);
+        ga.inside(b.vertices, in, open);
+        add_signs(out.b_to_a, ba, in, open);
+    }
     if (d_ab) d_ab->swap(ab);
     if (d_ba) d_ba->swap(ba);
     return true;
 }
 // one line, every field at %.9g (sobfu_amd.evaluate.format_result); digits: another precision (17 round-trips a double)
 inline std::string format_comparison(const MeshComparison& r, int digits = 9) {
-    char line[1536];
-    const DistanceStats &x = r.a_to_b, &y = r.b_to_a;
-    std::snprintf(line, sizeof line,
-                  "a_to_b.n=%zu a_to_b.within=%zu a_to_b.mean=%.*g a_to_b.rms=%.*g a_to_b.median=%.*g a_to_b.max=%.*g "
-                  "b_to_a.n=%zu b_to_a.within=%zu b_to_a.mean=%.*g b_to_a.rms=%.*g b_to_a.median=%.*g b_to_a.max=%.*g chamfer=%.*g hausdorff=%.*g",
-                  x.n, x.within, digits, x.mean, digits, x.rms, digits, x.median, digits, x.max, y.n, y.within, digits, y.mean, digits, y.rms, digits,
-                  y.median, digits, y.max, digits, r.chamfer, digits, r.hausdorff);
+    char line[2048];
+    int at = 0;
+    const DistanceStats* sides[2] = {&r.a_to_b, &r.b_to_a};
+    for (int k = 0; k < 2; ++k) {  // the signed fields follow each side's own, where the comparison has them
+        const DistanceStats& x = *sides[k];
+        const char* s = k ? "b_to_a" : "a_to_b";
+        at += std::snprintf(line + at, sizeof line - (size_t) at, "%s.n=%zu %s.within=%zu %s.mean=%.*g %s.rms=%.*g %s.median=%.*g %s.max=%.*g ", s, x.n, s,
+                            x.within, s, digits, x.mean, s, digits, x.rms, s, digits, x.median, s, digits, x.max);
+        if (x.has_signs)
+            at += std::snprintf(line + at, sizeof line - (size_t) at, "%s.signed_mean=%.*g %s.inside=%zu %s.open=%zu ", s, digits, x.signed_mean, s, x.inside, s,
+                                x.open);
+    }
+    std::snprintf(line + at, sizeof line - (size_t) at, "chamfer=%.*g hausdorff=%.*g", digits, r.chamfer, digits, r.hausdorff);
     return line;
 }
 // (n, 4) points through a row-major 4 x 4 transform in float32: ((m0 x + m1 y) + m2 z) + t per row, w = 1 (sobfu_amd.fusion.transform_points)
@@ -476,6 +541,49 @@ struct AlignRequest {
     int iters = 30, dof = 6;
     Alignment info;
 };
+// ---- mesh_to_tsdf: a closed mesh as the full 3-D signed TSDF of a volume (sobfu_amd.mesh_voxelise.mesh_to_tsdf) ---------------------------
+// the pose of the meshes the project writes and evaluates against, mesh frame -> camera frame: (x, -y, -z)
+inline cv::Affine3f mesh_frame() {
+    cv::Affine3f a = cv::Affine3f::Identity();
+    a.R[4] = a.R[8] = -1.f;
+    return a;
+}
+// mesh.vertices in the mesh frame -> the volume's frame: mesh -> camera by mesh2cam, camera -> volume by the inverse of vol2cam (a voxel
+// centre v is seen at R v + t), composed in double and applied once per vertex in double
+inline void mesh_to_volume_frame(std::vector<float4>& vertices, const cv::Affine3f& mesh2cam, const cv::Affine3f& vol2cam) {
+    double M[9], m[3];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) {
+            M[3 * i + j] = 0;
+            for (int k = 0; k < 3; ++k) M[3 * i + j] += (double) vol2cam.R[3 * k + i] * (double) mesh2cam.R[3 * k + j];
+        }
+        m[i] = 0;
+        for (int k = 0; k < 3; ++k) m[i] += (double) vol2cam.R[3 * k + i] * ((double) mesh2cam.t[k] - (double) vol2cam.t[k]);
+    }
+    for (float4& v : vertices) {
+        const double x = v.x, y = v.y, z = v.z;
+        v = make_float4((float) (M[0] * x + M[1] * y + M[2] * z + m[0]), (float) (M[3] * x + M[4] * y + M[5] * z + m[1]),
+                        (float) (M[6] * x + M[7] * y + M[8] * z + m[2]), 1.f);
+    }
+}
+// Fills `vol` (its dims, voxel size, truncation distance and eta) with the mesh: the vertices are transformed once and the triangle grid is
+// built with a cell edge of `cell` (0: four voxels, half a brick -- profiles/mesh_voxelise.md).  *open_rows: the rows
+// that cross the mesh an odd number of times, 0 for a closed mesh.  false (+ *why): the mesh is refused (TriangleGrid::build)
+inline bool mesh_to_tsdf(const IndexedMesh& mesh, const cv::Affine3f& mesh2cam, const cv::Affine3f& vol2cam, kfusion::cuda::TsdfVolume& vol, int* open_rows,
+                         std::string* why = nullptr, float cell = 0.f, int mode = SOBFU_MESH_DISTANCE_AUTO) {
+    std::vector<float4> v = mesh.vertices;
+    mesh_to_volume_frame(v, mesh2cam, vol2cam);
+    TriangleGrid grid;
+    const cv::Vec3i d  = vol.getDims();
+    const cv::Vec3f s  = vol.getVoxelSize();
+    if (!grid.build(v, mesh.faces, cell > 0.f ? cell : 4.f * std::max(s[0], std::max(s[1], s[2])), why)) return false;
+    const int dims[3]  = {d[0], d[1], d[2]};
+    const float vs[3]  = {s[0], s[1], s[2]};
+    const int open     = grid.voxelise(vol.data().ptr<float>(), dims, vs, vol.getTruncDist(), vol.getEta(), mode);
+    if (open_rows) *open_rows = open;
+    return true;
+}
+
 // Vertex colours by error: a fixed ramp from blue (0) to red (max_dist and beyond), r = round(255 t), b = round(255 (1 - t)), g = 0 with
 // t = clamp(d / max_dist, 0, 1) in double; grey (128, 128, 128) where there is no match
 inline void error_colours(const std::vector<float>& dist, float max_dist, std::vector<kfusion::RGB>& colours) {

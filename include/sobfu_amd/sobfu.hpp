@@ -1339,29 +1339,29 @@ public:
         kfusion::cuda::computeDists(filtered_, dists_, params.intr);                                   // :91
         if (params.track_camera) track();
         poses_.push_back(camera_pose_);
-        if (frame_counter_ == 0) {                                                                     // :93-123
-            phi_global = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
-            phi_global->integrate(dists_, camera_pose_, params.intr);
-            if (coloured) integrate_colour(image, *phi_global, nullptr);
-            phi_global_psi_inv = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
-            phi_n              = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
-            phi_n_psi          = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
-            psi     = std::make_shared<sobfu::cuda::DeformationField>(params.volume_dims);
-            psi_inv = std::make_shared<sobfu::cuda::DeformationField>(params.volume_dims);
-            solver  = std::make_shared<sobfu::cuda::Solver>(params);
-            return ++frame_counter_, true;
+        return frame(image, [&](kfusion::cuda::TsdfVolume& v, bool fresh) {
+            if (!fresh) v.clear();                                                                     // :129
+            v.integrate(dists_, camera_pose_, params.intr);                                            // :112, :130
+        });
+    }
+    // A frame whose phi_n is the closed mesh itself, voxelised (sobfu_amd::mesh_to_tsdf: exact signed distances on both sides of the surface,
+    // no sensor model) in place of bilateral -> truncate -> dists -> integrate; everything after that is operator()'s.  mesh: in the mesh
+    // frame; mesh2cam: mesh frame -> camera frame (the default: the meshes written here, (x, -y, -z)).  Camera tracking does not apply: the
+    // pose is appended unchanged.  false (+ *why), with nothing fused: the mesh is refused, or it is not closed (rows that cross it an odd
+    // number of times) and allow_open is not set.
+    bool integrate_mesh(const sobfu_amd::IndexedMesh& mesh, const cv::Affine3f& mesh2cam = sobfu_amd::mesh_frame(), bool allow_open = false,
+                        std::string* why = nullptr, int* open_rows = nullptr) {
+        cv::Ptr<kfusion::cuda::TsdfVolume> target = frame_counter_ == 0 ? cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params)) : phi_n;
+        int open = 0;
+        if (!sobfu_amd::mesh_to_tsdf(mesh, mesh2cam, camera_pose_.inv() * params.volume_pose, *target, &open, why)) return false;
+        if (open_rows) *open_rows = open;
+        if (open > 0 && !allow_open) {
+            if (why) *why = "the mesh is not closed: " + std::to_string(open) + " rows of the volume cross it an odd number of times";
+            return false;
         }
-        phi_n->clear();                                                                                // :129
-        phi_n->integrate(dists_, camera_pose_, params.intr);                                           // :130
-        if (frame_counter_ < params.start_frame) {                                                     // :136-139
-            if (coloured) integrate_colour(image, *phi_n, nullptr);
-            phi_global->integrate(*phi_n);
-            return ++frame_counter_, true;
-        }
-        solver->estimate_psi(phi_global, phi_global_psi_inv, phi_n, phi_n_psi, psi, psi_inv);          // :141
-        if (coloured) integrate_colour(image, *phi_n_psi, psi->get_data().ptr<float>());
-        phi_global->integrate(*phi_n_psi);                                                             // :142
-        return ++frame_counter_, true;
+        std::printf("--- FRAME NO. %d ---\n", frame_counter_);
+        poses_.push_back(camera_pose_);
+        return frame(kfusion::cuda::Image(), [](kfusion::cuda::TsdfVolume&, bool) {}, target);
     }
     // the canonical colour warped to live, colour_global o psi_inv: computed on request (not a per-frame cost); null without colour
     std::shared_ptr<kfusion::cuda::ColourVolume> get_colour_global_psi_inv() {
@@ -1422,7 +1422,7 @@ public:
     // align (optional, canonical only): align->pose, the caller's ground-truth-to-model guess, is first refined against the model
     // (sobfu_amd::align_meshes with max_dist) and applied to a copy of the ground truth; without it the ground truth is taken as given.
     bool evaluate_canonical(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
-                            std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::AlignRequest* align = nullptr) {
+                            std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::AlignRequest* align = nullptr, bool with_signs = false) {
         sobfu_amd::IndexedMesh m = get_phi_global_indexed_mesh();
         bool ok;
         if (align) {
@@ -1430,19 +1430,19 @@ public:
             ok = sobfu_amd::align_meshes(m.vertices, gt, align->pose, align->info, align->iters, max_dist, align->dof, 0.f, 0.f, why);
             if (ok) {
                 sobfu_amd::transform_points(posed.vertices, align->pose);
-                ok = sobfu_amd::compare_meshes(m, posed, max_dist, out, d_model, nullptr, why);
+                ok = sobfu_amd::compare_meshes(m, posed, max_dist, out, d_model, nullptr, why, nullptr, with_signs);
             }
         } else {
-            ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why);
+            ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, nullptr, with_signs);
         }
         if (model) *model = std::move(m);
         return ok;
     }
-    // gt_grid (optional): a grid already built over gt, used instead of building another
+    // gt_grid (optional): a grid already built over gt, used instead of building another.  with_signs (both): the comparison's signed fields
     bool evaluate_live(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
-                       std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::TriangleGrid* gt_grid = nullptr) {
+                       std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::TriangleGrid* gt_grid = nullptr, bool with_signs = false) {
         sobfu_amd::IndexedMesh m = get_phi_global_warped_indexed_mesh();
-        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, gt_grid);
+        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, gt_grid, with_signs);
         if (model) *model = std::move(m);
         return ok;
     }
@@ -1459,6 +1459,34 @@ public:
     std::shared_ptr<kfusion::cuda::ColourVolume> colour_global, colour_global_psi_inv;  // null until the first colour frame
 
 private:
+    // frame 0: integrate(phi_global) | frame n: integrate(phi_n), estimate_psi, fuse (sob_fusion.cpp:93-145).  integrate(vol, fresh) fills a
+    // volume with the frame's TSDF (fresh: newly made, cleared); ready: frame 0's volume, already filled (frame n: phi_n is)
+    template <class Integrate>
+    bool frame(const kfusion::cuda::Image& image, Integrate&& integrate, cv::Ptr<kfusion::cuda::TsdfVolume> ready = cv::Ptr<kfusion::cuda::TsdfVolume>()) {
+        const bool coloured = !image.empty();
+        if (frame_counter_ == 0) {                                                                     // :93-123
+            phi_global = ready ? ready : cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
+            integrate(*phi_global, true);
+            if (coloured) integrate_colour(image, *phi_global, nullptr);
+            phi_global_psi_inv = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
+            phi_n              = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
+            phi_n_psi          = cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params));
+            psi     = std::make_shared<sobfu::cuda::DeformationField>(params.volume_dims);
+            psi_inv = std::make_shared<sobfu::cuda::DeformationField>(params.volume_dims);
+            solver  = std::make_shared<sobfu::cuda::Solver>(params);
+            return ++frame_counter_, true;
+        }
+        integrate(*phi_n, false);
+        if (frame_counter_ < params.start_frame) {                                                     // :136-139
+            if (coloured) integrate_colour(image, *phi_n, nullptr);
+            phi_global->integrate(*phi_n);
+            return ++frame_counter_, true;
+        }
+        solver->estimate_psi(phi_global, phi_global_psi_inv, phi_n, phi_n_psi, psi, psi_inv);          // :141
+        if (coloured) integrate_colour(image, *phi_n_psi, psi->get_data().ptr<float>());
+        phi_global->integrate(*phi_n_psi);                                                             // :142
+        return ++frame_counter_, true;
+    }
     void integrate_colour(const kfusion::cuda::Image& image, const kfusion::cuda::TsdfVolume& tsdf, const float* d_psi) {
         if (!colour_global) colour_global = std::make_shared<kfusion::cuda::ColourVolume>(params.volume_dims);
         colour_global->integrate(image, tsdf, d_psi, camera_pose_, params.intr);

@@ -665,6 +665,32 @@ int sobfu_hip_mesh_render(void* d_workspace, size_t workspace_bytes, const float
                           uint16_t* d_depth, int depth_step, float* d_points, int points_step, float* d_normals, int normals_step,
                           uint8_t* d_colour, int colour_step, int32_t* d_tri, int tri_step, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mesh voxelisation  (no counterpart in the reference; sobfu_amd/csrc/mesh_voxel_kernels.hip)
+ * A closed mesh, with the grid of sobfu_hip_mesh_grid_build (the same arrays and plan, unchanged; the workspace is only read) and its
+ * vertices in the volume's frame, into a signed TSDF volume, and the inside / outside test behind it.  A point is inside iff the row
+ * through it along +x crosses the mesh an odd number of times beyond it (the exact counting rule of sobfu_amd/csrc/sobfu_mesh_parity.hpp);
+ * a row that crosses the mesh an odd number of times altogether is open: the mesh is not closed there, and signs along it mean nothing.
+ * mode is SOBFU_MESH_DISTANCE_AUTO (the grid; brute force for meshes of at most 64 triangles), _GRID or _BRUTE and never changes a bit of
+ * the output, nor does the run.  A workspace that is not marked as built, or no triangles: every voxel is (1, 1), every point outside,
+ * nothing open.  Every argument is checked before any device call (SOBFU_E_BADARG).  Asynchronous.
+ * ---------------------------------------------------------------------------------------------------- */
+/* Bytes of the caller-kept workspace (16-byte aligned) of sobfu_hip_mesh_voxelise: the sign bits, ceil(X / 32) words per row.  0 for
+ * X outside [1, 512], Y or Z < 1, or more than INT_MAX rows. */
+size_t sobfu_hip_mesh_voxelise_workspace_bytes(int X, int Y, int Z);
+/* d_vol (X * Y * Z float2 {tsdf, weight}, X <= 512): voxel (i, j, k) has its centre at (i vs + vs / 2) per axis, in fp32; d = its exact
+ * distance to the nearest triangle (sobfu_mesh_distance.hpp), s = -d inside and d outside; it stores tsdf = clamp(s / trunc, -1, 1) and
+ * weight = s > -eta ? 1 : 0, as sobfu_hip_init_sphere does.  *d_open_rows (device): the number of open rows of the volume. */
+int sobfu_hip_mesh_voxelise(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                            int n_triangles, const float origin[3], float h, const int dims[3], float* d_vol, int X, int Y, int Z,
+                            const float voxel_size[3], float trunc, float eta, int mode, void* d_workspace, size_t workspace_bytes,
+                            int* d_open_rows, void* stream);
+/* n points (dense float4, w ignored) -> d_inside[i] = 1 inside, 0 outside; d_open[i] = 1 where the point's row is open.  n = 0 succeeds
+ * and launches nothing. */
+int sobfu_hip_mesh_inside(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                          int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, uint8_t* d_inside,
+                          uint8_t* d_open, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

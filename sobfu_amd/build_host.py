@@ -103,6 +103,13 @@ def build_mesh_ray_tool(force: bool = False, flags=()) -> str:
     return _build("mesh_ray_tool", _test_src("mesh_ray_tool.cpp"), deps, False, force, ["-std=c++14", f"-I{CSRC}", "-ffp-contract=off", *flags])
 
 
+def build_mesh_parity_tool(force: bool = False, flags=()) -> str:
+    """tests/cpp/mesh_parity_tool.cpp: CPU-only driver of the row-crossing rule (sobfu_amd/csrc/sobfu_mesh_parity.hpp, no HIP;
+    -ffp-contract=off, as the kernels are built)."""
+    deps = [os.path.join(CSRC, h) for h in ("sobfu_mesh_parity.hpp", "sobfu_mesh_distance.hpp")]
+    return _build("mesh_parity_tool", _test_src("mesh_parity_tool.cpp"), deps, False, force, ["-std=c++14", f"-I{CSRC}", "-ffp-contract=off", *flags])
+
+
 def build_rigid_tool(force: bool = False) -> str:
     """tests/cpp/rigid_solve_tool.cpp: CPU-only driver of the shared rigid solve (sobfu_amd/csrc/sobfu_rigid.hpp, no HIP; -ffp-contract=off,
     as the kernels are built)."""
@@ -112,7 +119,7 @@ def build_rigid_tool(force: bool = False) -> str:
 
 def build_host(force: bool = False) -> str:
     for build in (build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
-                  build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_rigid_tool):
+                  build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_mesh_parity_tool, build_rigid_tool):
         build(force)
     return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H], True, force)
 

@@ -1,0 +1,333 @@
+// Closed triangle meshes into signed TSDF volumes on gfx950, and the inside / outside test behind them.  The reference
+// has no such step; the rules are this project's, and tests/mesh_parity_reference.py restates them (the row-crossing rule operation by
+// operation: sobfu_mesh_parity.hpp; the distance: sobfu_mesh_distance.hpp).  The kernels only read the grid that
+// sobfu_hip_mesh_grid_build made for the distance query (sobfu_mesh_grid_ws.hpp).  Vertices are in the volume's frame.
+//
+//   centres  voxel i of an axis has its centre at i vs + vs / 2, in fp32
+//   sign     a row is the line through (., py, pz) along +x.  A crossing triangle's box contains (py, pz) -- the fp32 translation of the
+//            rule keeps signs -- so it is referenced from the row's one cell column (cell_of(py), cell_of(pz)), whose cells cx = 0 ..
+//            dx - 1 hold one contiguous range of references.  A triangle referenced from several cells of the column counts only in
+//            cell_of(min(a.x, b.x, c.x)), the expression bin_triangles_kernel uses.  The crossing rule is exact, so the count depends
+//            neither on the cells, nor on the order of the references, nor on grid versus brute force (every triangle once).
+//   rows     one wave per volume row (j, k), up to X = 512: lanes stride over the column's references; each crossing flips, in an LDS mask,
+//            the bit of the first voxel whose centre is not below X (bit X: beyond the last voxel).  XOR is order-independent.  Voxel i
+//            is inside iff the flips at bits above i are odd in number: a suffix parity, written as ceil(X / 32) words per row.  A
+//            row whose flips are odd in number altogether is open: one integer atomic on the counter.
+//   points   one lane per point walks its whole column and counts the crossings with X > p.x, and all of them (open).
+//   volume   d = the exact minimum distance over ALL triangles (closest_on_triangle), s = inside ? -d : d, the voxel
+//            pack_tsdf(s, trunc, s > -eta ? 1 : 0).  |s| at or beyond max(trunc, eta) packs to (+-1, weight by sign alone), so only
+//            triangles nearer than that matter.  One 512-lane workgroup per 8 x 8 x 8 brick (ragged at the edges): the box of its voxel
+//            centres grown by max(trunc, eta) + kMeshMargin L (L = the largest coordinate magnitude of the grid's box and the brick: the
+//            bound on the fp32 error of one distance, as in mesh_distance_kernels.hip); the triangles referenced by the cells that
+//            overlap it are gathered into LDS, each once (taken in the first overlapping cell of its own cell range), kStage at a
+//            time; every lane tests every staged triangle (broadcast LDS reads).  A brick that gathers none stores +-1 from its sign bits.
+//            The reach is not gathered at once: first the cells within one cell edge of the brick's box, then -- while some voxel's best
+//            distance (or the saturating distance) is not below the gathered radius rho by the margin -- the cells out to that largest best
+//            distance, or to 2 rho while some voxel has found nothing, less the cells already visited.  A triangle not yet gathered keeps
+//            its box clear of the brick's box grown by rho, so it is farther than rho from every voxel and cannot change a bit.
+//            min d2 does not depend on order: the volume is the brute-force volume bit for bit, run after run.
+//   nothing  an unbuilt or refused grid, or no triangles: every voxel is (1, 1), empty space, and every point outside; the mesh is
+//            not read.
+#include "sobfu_hip.h"
+#include "sobfu_device.hpp"
+#include "sobfu_mesh_grid_ws.hpp"
+#include "sobfu_mesh_parity.hpp"
+
+using namespace sobfu_hip;
+
+namespace {
+
+constexpr float kMeshMargin = 1e-4f;
+constexpr int kMaxX      = 512;
+constexpr int kMaskWords = kMaxX / 32 + 1;  // bit X of a row: crossings beyond the last voxel
+constexpr int kBrick     = 8;
+constexpr int kStage     = 1024;  // triangles staged in LDS at a time (48 B each)
+
+struct Mesh {
+    const float4* verts;
+    const int* faces;
+    int n_triangles;
+};
+
+struct VoxArgs {
+    Mesh mesh;
+    int brute;
+    Dims d;
+    float vsx, vsy, vsz, trunc, eta;
+    float box_l;  // the largest coordinate magnitude of the grid's box
+    float2* vol;
+    unsigned* bits;  // Y Z rows of nw words
+    int nw;
+    int* open_rows;
+};
+
+SOBFU_DEV float centre(int i, float vs) { return (float) i * vs + vs / 2.f; }
+
+// the first i in [0, n] whose centre is not below X (n: none is)
+SOBFU_DEV int first_not_below(double X, float vs, int n) {
+    const double e = ceil((X - (double) (vs / 2.f)) / (double) vs);
+    int i = (int) fmax(fmin(e, (double) n), 0.0);
+    while (i > 0 && (double) centre(i - 1, vs) >= X) --i;
+    while (i < n && (double) centre(i, vs) < X) ++i;
+    return i;
+}
+
+SOBFU_DEV Crossing cross_triangle(const Mesh& m, int t, float py, float pz, float& min_x) {
+    const int f0 = m.faces[3 * (size_t) t], f1 = m.faces[3 * (size_t) t + 1], f2 = m.faces[3 * (size_t) t + 2];
+    const P3 a = p3(m.verts[f0]), b = p3(m.verts[f1]), c = p3(m.verts[f2]);
+    min_x = fminf(fminf(a.x, b.x), c.x);
+    return row_crossing(a, b, c, py, pz);
+}
+
+// the cell c in [c0, c1] of a row of cells (start: that row's entries) whose references hold position k: the largest c with start[c] <= k
+SOBFU_DEV int cell_of_reference(const int* __restrict__ start, int c0, int c1, int k) {
+    int lo = c0, hi = c1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (start[mid] <= k) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) row_parity_kernel(Grid g, VoxArgs a) {
+    __shared__ unsigned mask[4][kMaskWords];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long row = (long long) blockIdx.x * 4 + wave;
+    const bool valid    = row < (long long) a.d.y * a.d.z;
+    if (lane < kMaskWords) mask[wave][lane] = 0u;
+    __syncthreads();
+    if (valid && g.hdr[kHdrBuilt] == 1) {
+        const float py = centre((int) (row % a.d.y), a.vsy), pz = centre((int) (row / a.d.y), a.vsz);
+        if (a.brute) {
+            for (int t = lane; t < a.mesh.n_triangles; t += 64) {
+                float min_x;
+                const Crossing c = cross_triangle(a.mesh, t, py, pz, min_x);
+                if (c.hit) {
+                    const int i = first_not_below(c.X, a.vsx, a.d.x);
+                    atomicXor(&mask[wave][i >> 5], 1u << (i & 31));
+                }
+            }
+        } else {
+            const int* start = g.start + g.dx * (cell_of(py, g.oy, g.h, g.dy) + g.dy * cell_of(pz, g.oz, g.h, g.dz));
+            const int k1 = start[g.dx];
+            for (int k = start[0] + lane; k < k1; k += 64) {
+                float min_x;
+                const Crossing c = cross_triangle(a.mesh, g.refs[k], py, pz, min_x);
+                if (c.hit && cell_of(min_x, g.ox, g.h, g.dx) == cell_of_reference(start, 0, g.dx - 1, k)) {
+                    const int i = first_not_below(c.X, a.vsx, a.d.x);
+                    atomicXor(&mask[wave][i >> 5], 1u << (i & 31));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (!valid) return;
+    const int nmask = a.d.x / 32 + 1;
+    if (lane < a.nw) {
+        unsigned s = mask[wave][lane];  // bit i: the parity of the flips at bits >= i of this word
+        s ^= s >> 1, s ^= s >> 2, s ^= s >> 4, s ^= s >> 8, s ^= s >> 16;
+        unsigned above = 0u;
+        for (int w = lane + 1; w < nmask; ++w) above ^= mask[wave][w];
+        unsigned inside = (s >> 1) ^ ((__popc(above) & 1) ? 0xffffffffu : 0u);
+        if (lane == a.nw - 1 && (a.d.x & 31)) inside &= (1u << (a.d.x & 31)) - 1u;
+        a.bits[(size_t) row * a.nw + lane] = inside;
+    }
+    if (lane == 0) {
+        unsigned all = 0u;
+        for (int w = 0; w < nmask; ++w) all ^= mask[wave][w];
+        if (__popc(all) & 1) atomicAdd(a.open_rows, 1);
+    }
+}
+
+struct InsideArgs {
+    Mesh mesh;
+    int brute;
+    const float4* points;
+    int n;
+    unsigned char* inside;
+    unsigned char* open;
+};
+
+__global__ void __launch_bounds__(256) mesh_inside_kernel(Grid g, InsideArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    unsigned beyond = 0u, total = 0u;
+    if (g.hdr[kHdrBuilt] == 1) {
+        const float4 p  = a.points[i];
+        const double px = (double) p.x;
+        float min_x;
+        if (a.brute) {
+            for (int t = 0; t < a.mesh.n_triangles; ++t) {
+                const Crossing c = cross_triangle(a.mesh, t, p.y, p.z, min_x);
+                if (c.hit) ++total, beyond += c.X > px ? 1u : 0u;
+            }
+        } else {
+            const int* start = g.start + g.dx * (cell_of(p.y, g.oy, g.h, g.dy) + g.dy * cell_of(p.z, g.oz, g.h, g.dz));
+            for (int cx = 0; cx < g.dx; ++cx)
+                for (int k = start[cx]; k < start[cx + 1]; ++k) {
+                    const Crossing c = cross_triangle(a.mesh, g.refs[k], p.y, p.z, min_x);
+                    if (c.hit && cell_of(min_x, g.ox, g.h, g.dx) == cx) ++total, beyond += c.X > px ? 1u : 0u;
+                }
+        }
+    }
+    a.inside[i] = (unsigned char) (beyond & 1u);
+    a.open[i]   = (unsigned char) (total & 1u);
+}
+
+__global__ void __launch_bounds__(512) brick_kernel(Grid g, VoxArgs a) {
+    __shared__ float4 sa[kStage], sb[kStage], sc[kStage];
+    __shared__ int s_count, s_reach;
+    const int tid = threadIdx.x;
+    const int x = blockIdx.x * kBrick + (tid & 7), y = blockIdx.y * kBrick + ((tid >> 3) & 7), z = blockIdx.z * kBrick + (tid >> 6);
+    const P3 p{centre(x, a.vsx), centre(y, a.vsy), centre(z, a.vsz)};
+    float best = INFINITY;
+    const Mesh& m = a.mesh;
+    auto test = [&](int count) {
+        for (int k = 0; k < count; ++k) best = fminf(best, closest_on_triangle(p, p3(sa[k]), p3(sb[k]), p3(sc[k])).d2);
+    };
+    auto stage = [&](int slot, int t) {
+        sa[slot] = m.verts[m.faces[3 * (size_t) t]], sb[slot] = m.verts[m.faces[3 * (size_t) t + 1]], sc[slot] = m.verts[m.faces[3 * (size_t) t + 2]];
+    };
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    if (g.hdr[kHdrBuilt] == 1 && m.n_triangles > 0) {  // uniform over the workgroup, like every loop bound below
+        if (a.brute) {
+            for (int t0 = 0; t0 < m.n_triangles; t0 += kStage) {
+                __syncthreads();  // the previous chunk has been read
+                for (int s = tid; s < kStage && t0 + s < m.n_triangles; s += 512) stage(s, t0 + s);
+                __syncthreads();
+                test(min(kStage, m.n_triangles - t0));
+            }
+        } else {
+            const float lx = centre(blockIdx.x * kBrick, a.vsx), hx = centre(min((int) blockIdx.x * kBrick + kBrick, a.d.x) - 1, a.vsx);
+            const float ly = centre(blockIdx.y * kBrick, a.vsy), hy = centre(min((int) blockIdx.y * kBrick + kBrick, a.d.y) - 1, a.vsy);
+            const float lz = centre(blockIdx.z * kBrick, a.vsz), hz = centre(min((int) blockIdx.z * kBrick + kBrick, a.d.z) - 1, a.vsz);
+            const float L = fmaxf(fmaxf(a.box_l, fmaxf(fabsf(lx), fabsf(hx))), fmaxf(fmaxf(fabsf(ly), fabsf(hy)), fmaxf(fabsf(lz), fabsf(hz))));
+            const float margin = kMeshMargin * L, cap = fmaxf(a.trunc, a.eta), r = cap + margin;
+            const bool in_volume = x < a.d.x && y < a.d.y && z < a.d.z;
+            // the cells visited so far (p): none; plain ints, selected one by one: a select between two structs goes through the stack
+            int px0 = 1, px1 = 0, py0 = 1, py1 = 0, pz0 = 1, pz1 = 0;
+            int examined = 0;  // references looked at since the stage was last emptied: at least the triangles staged
+            for (float rho = fminf(g.h, r);;) {
+                // the cells that overlap the brick's box grown by rho (n), less those of the radius before
+                const bool near = hx + rho >= g.ox && lx - rho <= g.ox + (float) g.dx * g.h && hy + rho >= g.oy && ly - rho <= g.oy + (float) g.dy * g.h &&
+                                  hz + rho >= g.oz && lz - rho <= g.oz + (float) g.dz * g.h;
+                const int nx0 = near ? cell_of(lx - rho, g.ox, g.h, g.dx) : px0, nx1 = near ? cell_of(hx + rho, g.ox, g.h, g.dx) : px1;
+                const int ny0 = near ? cell_of(ly - rho, g.oy, g.h, g.dy) : py0, ny1 = near ? cell_of(hy + rho, g.oy, g.h, g.dy) : py1;
+                const int nz0 = near ? cell_of(lz - rho, g.oz, g.h, g.dz) : pz0, nz1 = near ? cell_of(hz + rho, g.oz, g.h, g.dz) : pz1;
+                const bool had = px0 <= px1;
+                for (int cz = nz0; cz <= nz1; ++cz)
+                    for (int cy = ny0; cy <= ny1; ++cy) {
+                        const int* start  = g.start + g.dx * (cy + g.dy * cz);
+                        const bool inner  = had && cz >= pz0 && cz <= pz1 && cy >= py0 && cy <= py1;  // this row's middle is done
+                        for (int part = 0; part < (inner ? 2 : 1); ++part) {
+                            const int xa = inner && part == 1 ? px1 + 1 : nx0, xb = inner && part == 0 ? px0 - 1 : nx1;
+                            if (xa > xb) continue;
+                            const int k1 = start[xb + 1];
+                            for (int kb = start[xa]; kb < k1; kb += 512) {
+                                // room for a whole pass?  Decided on the references examined, not on s_count: a wave ahead may already
+                                // be adding to that, and every lane has to take the same branch to the barriers
+                                if (examined + 512 > kStage) {
+                                    test(s_count);
+                                    __syncthreads();
+                                    if (tid == 0) s_count = 0;
+                                    __syncthreads();
+                                    examined = 0;
+                                }
+                                examined += min(512, k1 - kb);
+                                const int k = kb + tid;
+                                if (k < k1) {
+                                    const int t = g.refs[k];
+                                    const float4 va = m.verts[m.faces[3 * (size_t) t]], vb = m.verts[m.faces[3 * (size_t) t + 1]], vc = m.verts[m.faces[3 * (size_t) t + 2]];
+                                    const int tx0 = cell_of(fminf(fminf(va.x, vb.x), vc.x), g.ox, g.h, g.dx), tx1 = cell_of(fmaxf(fmaxf(va.x, vb.x), vc.x), g.ox, g.h, g.dx);
+                                    const int ty0 = cell_of(fminf(fminf(va.y, vb.y), vc.y), g.oy, g.h, g.dy), ty1 = cell_of(fmaxf(fmaxf(va.y, vb.y), vc.y), g.oy, g.h, g.dy);
+                                    const int tz0 = cell_of(fminf(fminf(va.z, vb.z), vc.z), g.oz, g.h, g.dz), tz1 = cell_of(fmaxf(fmaxf(va.z, vb.z), vc.z), g.oz, g.h, g.dz);
+                                    // taken at an earlier radius: its cells met those visited then
+                                    const bool seen = had && tx0 <= px1 && tx1 >= px0 && ty0 <= py1 && ty1 >= py0 && tz0 <= pz1 && tz1 >= pz0;
+                                    // else once, in the first of its cells inside the range
+                                    if (!seen && max(ty0, ny0) == cy && max(tz0, nz0) == cz && max(tx0, nx0) == cell_of_reference(start, xa, xb, k)) {
+                                        const int slot = atomicAdd(&s_count, 1);
+                                        sa[slot] = va, sb[slot] = vb, sc[slot] = vc;
+                                    }
+                                }
+                                __syncthreads();
+                            }
+                        }
+                    }
+                test(s_count);
+                if (!(rho < r)) break;  // the whole reach has been gathered
+                // Every triangle not yet seen keeps its box clear of the brick's box grown by rho: it is farther than rho from every voxel.
+                // Once every voxel's best distance -- or the cap beyond which the voxel saturates whatever the distance -- is below rho by
+                // the margin, none of them can change a bit.
+                __syncthreads();
+                if (tid == 0) s_count = 0, s_reach = 0;
+                examined = 0;
+                __syncthreads();
+                if (in_volume) atomicMax(&s_reach, __float_as_int(fminf(__builtin_sqrtf(best), cap)));  // non-negative floats order as their bits
+                __syncthreads();
+                const float reach = __int_as_float(s_reach);
+                if (reach + margin <= rho) break;
+                px0 = nx0, px1 = nx1, py0 = ny0, py1 = ny1, pz0 = nz0, pz1 = nz1;
+                // every voxel has a triangle within reach < cap: nothing beyond reach matters, and the next round is the last (best only
+                // falls).  Else some voxel has found nothing yet: twice as far
+                rho = fminf(reach < cap ? reach + margin : 2.f * rho, r);
+            }
+        }
+    }
+    if (x >= a.d.x || y >= a.d.y || z >= a.d.z) return;
+    const bool inside = (a.bits[((size_t) z * a.d.y + y) * a.nw + (x >> 5)] >> (x & 31)) & 1u;
+    const float d = __builtin_sqrtf(best), s = inside ? -d : d;
+    a.vol[vidx(a.d, x, y, z)] = pack_tsdf(s, a.trunc, s > -a.eta ? 1.f : 0.f);
+}
+
+int words_per_row(int X) { return (X + 31) / 32; }
+size_t bits_bytes(int X, int Y, int Z) { return ((size_t) Y * Z * words_per_row(X) * sizeof(unsigned) + 15) / 16 * 16; }
+bool mode_ok(int mode) { return mode >= SOBFU_MESH_DISTANCE_AUTO && mode <= SOBFU_MESH_DISTANCE_BRUTE; }
+int is_brute(int mode, int n_triangles) {
+    return mode == SOBFU_MESH_DISTANCE_BRUTE || (mode == SOBFU_MESH_DISTANCE_AUTO && n_triangles <= kMeshGridTinyMesh);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sobfu_hip_mesh_voxelise_workspace_bytes(int X, int Y, int Z) {
+    if (X < 1 || X > kMaxX || Y < 1 || Z < 1 || (long long) Y * Z > INT_MAX) return 0;
+    return bits_bytes(X, Y, Z);
+}
+
+int sobfu_hip_mesh_voxelise(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                            int n_triangles, const float origin[3], float h, const int dims[3], float* d_vol, int X, int Y, int Z,
+                            const float voxel_size[3], float trunc, float eta, int mode, void* d_workspace, size_t workspace_bytes,
+                            int* d_open_rows, void* stream) {
+    SOBFU_CHECK_ARGS(grid_args_ok(d_grid_workspace, grid_workspace_bytes, origin, h, dims, 0) && mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    SOBFU_CHECK_ARGS(d_vol && aligned(d_vol, 0, 8) && volume_ok(X, Y, Z, kGridZ * kBrick) && X <= kMaxX && (long long) Y * Z <= INT_MAX);
+    SOBFU_CHECK_ARGS(voxel_size && positive_finite(voxel_size[0]) && positive_finite(voxel_size[1]) && positive_finite(voxel_size[2]) &&
+                     positive_finite(trunc) && std::isfinite(eta) && mode_ok(mode));
+    SOBFU_CHECK_ARGS(d_workspace && aligned(d_workspace, 0, 16) && workspace_bytes >= bits_bytes(X, Y, Z) && d_open_rows && aligned(d_open_rows, 0, 4));
+    hipStream_t st = (hipStream_t) stream;
+    const Grid g   = grid_of(d_grid_workspace, origin, h, dims, 0);
+    const VoxArgs a{{(const float4*) d_vertices, d_faces, n_triangles}, is_brute(mode, n_triangles), {X, Y, Z}, voxel_size[0], voxel_size[1], voxel_size[2],
+                    trunc, eta, grid_box_l(origin, h, dims), (float2*) d_vol, (unsigned*) d_workspace, words_per_row(X), d_open_rows};
+    SOBFU_HIP_TRY(hipMemsetAsync(d_open_rows, 0, sizeof(int), st));
+    hipLaunchKernelGGL(row_parity_kernel, dim3((unsigned) (((long long) Y * Z + 3) / 4)), dim3(256), 0, st, g, a);
+    SOBFU_HIP_TRY(hipGetLastError());
+    const dim3 bricks((unsigned) ((X + kBrick - 1) / kBrick), (unsigned) ((Y + kBrick - 1) / kBrick), (unsigned) ((Z + kBrick - 1) / kBrick));
+    hipLaunchKernelGGL(brick_kernel, bricks, dim3(512), 0, st, g, a);
+    return (int) hipGetLastError();
+}
+
+int sobfu_hip_mesh_inside(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                          int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, uint8_t* d_inside,
+                          uint8_t* d_open, int mode, void* stream) {
+    SOBFU_CHECK_ARGS(grid_args_ok(d_grid_workspace, grid_workspace_bytes, origin, h, dims, 0) && mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    SOBFU_CHECK_ARGS(d_points && d_inside && d_open && n >= 0 && aligned(d_points, 0, 16) && mode_ok(mode));
+    if (n == 0) return 0;
+    const Grid g = grid_of(d_grid_workspace, origin, h, dims, 0);
+    const InsideArgs a{{(const float4*) d_vertices, d_faces, n_triangles}, is_brute(mode, n_triangles), (const float4*) d_points, n, d_inside, d_open};
+    hipLaunchKernelGGL(mesh_inside_kernel, dim3((unsigned) (((long long) n + 255) / 256)), dim3(256), 0, (hipStream_t) stream, g, a);
+    return (int) hipGetLastError();
+}
+
+}  // extern "C"

@@ -26,20 +26,39 @@ def device_tensor(a, dtype):
     return a.to(device="cuda", dtype=dtype).contiguous()
 
 
-def compare_meshes(a_vertices, a_faces, b_vertices, b_faces, max_dist=None, return_distances=False):
+def signed_stats(dist, inside, open_):
+    """the signed fields of one direction: signed_mean (float64 mean over the finite distances, each negative where its vertex is inside
+    the other mesh), inside (how many of those vertices are inside), open (how many of ALL the vertices lie on a row that crosses the
+    other mesh an odd number of times: it is not closed there and their sign means nothing)"""
+    d = dist.detach().cpu().numpy().astype(np.float64).ravel()
+    i, o = inside.detach().cpu().numpy().astype(bool).ravel(), open_.detach().cpu().numpy().astype(bool).ravel()
+    f = np.isfinite(d)
+    if not f.any():
+        return dict(signed_mean=0.0, inside=0, open=int(o.sum()))
+    return dict(signed_mean=float(np.where(i[f], -d[f], d[f]).mean()), inside=int(i[f].sum()), open=int(o.sum()))
+
+
+def compare_meshes(a_vertices, a_faces, b_vertices, b_faces, max_dist=None, return_distances=False, signed=False):
     """Two indexed meshes (vertices (V, 4) float32, faces (F, 3) int32; tensors or arrays) -> dict(a_to_b, b_to_a: the statistics of
     distance_stats over the distances from each vertex of one mesh to the surface of the other; chamfer: the mean of the two means;
     hausdorff: the larger of the two maxima).  Vertices farther than max_dist have no match and count in n only.
-    return_distances: -> (dict, a_to_b distances, b_to_a distances) (float32 GPU tensors)."""
+    return_distances: -> (dict, a_to_b distances, b_to_a distances) (float32 GPU tensors).
+    signed: each direction gains the fields of signed_stats -- the sign is that of the query vertex against the OTHER mesh
+    (ops.TriangleGrid.inside), which should be closed: a_to_b.signed_mean > 0 says mesh a lies outside b on average (inflated).  The
+    unsigned fields are the same with and without."""
     import torch
 
     from . import ops
 
     av, bv = device_tensor(a_vertices, torch.float32), device_tensor(b_vertices, torch.float32)
     af, bf = device_tensor(a_faces, torch.int32), device_tensor(b_faces, torch.int32)
-    d_ab = ops.TriangleGrid(bv, bf).query(av, max_dist)[0]
-    d_ba = ops.TriangleGrid(av, af).query(bv, max_dist)[0]
+    gb, ga = ops.TriangleGrid(bv, bf), ops.TriangleGrid(av, af)
+    d_ab = gb.query(av, max_dist)[0]
+    d_ba = ga.query(bv, max_dist)[0]
     ab, ba = distance_stats(d_ab), distance_stats(d_ba)
+    if signed:
+        ab.update(signed_stats(d_ab, *gb.inside(av)))
+        ba.update(signed_stats(d_ba, *ga.inside(bv)))
     out = dict(a_to_b=ab, b_to_a=ba, chamfer=0.5 * (ab["mean"] + ba["mean"]), hausdorff=max(ab["max"], ba["max"]))
     return (out, d_ab, d_ba) if return_distances else out
 
@@ -47,9 +66,12 @@ def compare_meshes(a_vertices, a_faces, b_vertices, b_faces, max_dist=None, retu
 STAT_FIELDS = ("n", "within", "mean", "rms", "median", "max")
 
 
+SIGNED_FIELDS = ("signed_mean", "inside", "open")
+
+
 def format_result(r):
-    """the app's printed form: every field at %.9g, a_to_b and b_to_a prefixed"""
-    parts = [f"{side}.{k}={r[side][k]:.9g}" for side in ("a_to_b", "b_to_a") for k in STAT_FIELDS]
+    """the app's printed form: every field at %.9g, a_to_b and b_to_a prefixed; the signed fields follow each side's where present"""
+    parts = [f"{side}.{k}={r[side][k]:.9g}" for side in ("a_to_b", "b_to_a") for k in STAT_FIELDS + SIGNED_FIELDS if k in r[side]]
     return " ".join(parts + [f"chamfer={r['chamfer']:.9g}", f"hausdorff={r['hausdorff']:.9g}"])
 
 

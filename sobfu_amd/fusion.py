@@ -7,6 +7,8 @@ from __future__ import annotations
 
 import numpy as np
 
+MESH_FRAME = (np.diag([1.0, -1.0, -1.0]).astype(np.float32), np.zeros(3, np.float32))  # mesh_render.MESH_FRAME
+
 
 def affine_mul(a, b):
     """a o b of two rigid 4 x 4 transforms in float32, in the operation order of cv::Affine3f's stand-in (include/sobfu_amd/sobfu.hpp)"""
@@ -98,7 +100,7 @@ class SobFusion:
         if colour is not None and tuple(colour.shape) != tuple(depth_u16.shape) + (4,):
             raise ValueError(f"colour frame {tuple(colour.shape)} does not match the depth frame {tuple(depth_u16.shape)}")
         self.image_shape = tuple(depth_u16.shape)
-        dims, vs = P["dims"], tuple(float(v) for v in P["vs"])
+        vs = tuple(float(v) for v in P["vs"])
         ks, ss, sd = P["bilateral"]
         d = ops.bilateral_filter(depth_u16, ks, ss, sd)                                       # sob_fusion.cpp:78
         ops.truncate_depth(d, P["trunc_depth"])                                               # :85
@@ -107,9 +109,44 @@ class SobFusion:
             self._track(d)
         self.poses.append(self.pose.copy())
         R, t = self.vol2cam()
+
+        def integrate(vol, fresh):
+            if not fresh:
+                ops.clear_volume(vol)                                                         # :129
+            ops.integrate_depth(dists, vol, vs, P["trunc"], P["eta"], R, t, P["intr"])        # :112, :130
+
+        return self._frame(integrate, colour)
+
+    def integrate_mesh(self, vertices, faces, pose=MESH_FRAME, allow_open=False):
+        """A frame whose phi_n is the closed mesh itself, voxelised (sobfu_amd.mesh_voxelise.mesh_to_tsdf: exact signed distances on both
+        sides of the surface, no sensor model) in place of bilateral -> truncate -> dists -> integrate_depth; everything after that is
+        __call__'s.  vertices (V, 3 | 4), faces (F, 3) in the mesh frame; pose = (R, t): mesh frame -> camera frame (MESH_FRAME: the
+        meshes the project writes).  Camera tracking does not apply: the pose is appended unchanged.  A mesh that is not closed (rows
+        that cross it an odd number of times) raises ValueError before anything is fused, unless allow_open."""
+        from .mesh_voxelise import mesh_to_tsdf
+
+        ops, P = self.ops, self.P
+        R, t = self.vol2cam()
+        target = ops.new_volume(P["dims"]) if self.frame == 0 else self.phi_n
+        _, open_rows = mesh_to_tsdf(vertices, faces, dict(P, R=R, t=t), pose=pose, out=target)
+        if int(open_rows) > 0 and not allow_open:
+            raise ValueError(f"the mesh is not closed: {int(open_rows)} rows of the volume cross it an odd number of times")
+        self.poses.append(self.pose.copy())
+
+        def integrate(vol, fresh):
+            if vol is not target:
+                vol.copy_(target)
+
+        return self._frame(integrate, None)
+
+    def _frame(self, integrate, colour):
+        """frame 0: integrate(phi_global) | frame n: integrate(phi_n), estimate_psi, fuse (sob_fusion.cpp:93-145).  integrate(vol, fresh)
+        fills a volume with the frame's TSDF; fresh: newly allocated, all zero"""
+        ops, P = self.ops, self.P
+        dims = P["dims"]
         if self.frame == 0:                                                                   # :93-123
             self.phi_global = ops.new_volume(dims)
-            ops.integrate_depth(dists, self.phi_global, vs, P["trunc"], P["eta"], R, t, P["intr"])
+            integrate(self.phi_global, True)
             self._colour(colour, self.phi_global, None)
             self.phi_global_psi_inv, self.phi_n, self.phi_n_psi = ops.new_volume(dims), ops.new_volume(dims), ops.new_volume(dims)
             self.psi, self.psi_inv = ops.new_field(dims), ops.new_field(dims)
@@ -119,8 +156,7 @@ class SobFusion:
                                      max_update_norm=P["max_update_norm"])
             self.frame += 1
             return None
-        ops.clear_volume(self.phi_n)                                                          # :129
-        ops.integrate_depth(dists, self.phi_n, vs, P["trunc"], P["eta"], R, t, P["intr"])    # :130
+        integrate(self.phi_n, False)
         if self.frame < P["start_frame"]:                                                     # :136-139
             self._colour(colour, self.phi_n, None)
             ops.integrate_fuse(self.phi_global, self.phi_n, P["max_weight"])
@@ -191,7 +227,7 @@ class SobFusion:
         return dict(valid=int(d.size), mean_abs=float(d.mean()), rms=float(np.sqrt((d * d).mean())), max=float(d.max()))
 
     def evaluate(self, gt_vertices, gt_faces, which="canonical", max_dist=None, pose=None, return_meshes=False, align=False, align_dof=6,
-                 align_iters=30):
+                 align_iters=30, signed=False):
         """The reconstruction against a ground-truth mesh (vertices (V, 4), faces (F, 3)) in the frame of the meshes the app writes
         (marching-cubes vertices, (x, -y, -z)): exact vertex-to-surface distances both ways (sobfu_amd.evaluate.compare_meshes; a = the
         model, b = the ground truth), in metres.  which: "canonical" meshes phi_global (ops.marching_cubes_indexed at the volume pose),
@@ -199,7 +235,9 @@ class SobFusion:
         row: (r0 x + r1 y) + r2 z + t).  Reads the volumes only.  return_meshes: -> (dict, model vertices, model faces, gt vertices).
         align (canonical only): `pose` (default: the identity) is first refined by sobfu_amd.evaluate.align_meshes -- align_iters
         iterations, align_dof 6 (rigid) or 3 (translation only: symmetric objects) -- and the dict gains "pose" (the refined 4 x 4) and
-        "align" (the alignment's info).  The live mesh is never aligned: that would hide the tracking error evaluation measures."""
+        "align" (the alignment's info).  The live mesh is never aligned: that would hide the tracking error evaluation measures.
+        signed: each direction gains signed_mean, inside and open (compare_meshes): a_to_b.signed_mean > 0 says the model lies outside
+        the (closed) ground truth on average."""
         import torch
 
         from . import evaluate as E
@@ -220,7 +258,7 @@ class SobFusion:
             pose, info = E.align_meshes(v, gv, gt_faces, pose, iters=align_iters, max_dist=max_dist, dof=align_dof)
         if pose is not None:
             gv = E.device_tensor(transform_points(gv.cpu().numpy(), pose), torch.float32)
-        r = E.compare_meshes(v, f, gv, gt_faces, max_dist)
+        r = E.compare_meshes(v, f, gv, gt_faces, max_dist, signed=signed)
         if align:
             r["pose"], r["align"] = pose, info
         return (r, v, f, gv) if return_meshes else r

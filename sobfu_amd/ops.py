@@ -826,6 +826,42 @@ class TriangleGrid:
                                                *args, _stream()), "mesh_render")
         return given
 
+    # ---- this mesh, closed, as a signed TSDF volume and an inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip) ----
+    def voxelise(self, dims, vs, trunc, eta, out=None, mode="auto"):
+        """This mesh, its vertices in the volume's frame, as a TSDF volume of dims = (X, Y, Z) voxels of size vs (3,): voxel (i, j, k) has
+        its centre at i vs + vs / 2 per axis; tsdf = clamp(s / trunc, -1, 1) with s the exact distance to the mesh, negative inside;
+        weight = s > -eta -> (volume (Z, Y, X, 2) float32, open_rows (1,) int32 GPU tensor: the rows along x that cross the mesh an odd
+        number of times -- 0 for a closed mesh).  out: a volume to write into.  mode never changes a bit.  X <= 512."""
+        if mode not in _MESH_MODES:
+            raise ValueError(f"unknown mode {mode!r}")
+        X, Y, Z = (int(d) for d in dims)
+        dev = self.vertices.device
+        vol = torch.empty((Z, Y, X, 2), dtype=torch.float32, device=dev) if out is None else out
+        if tuple(vol.shape) != (Z, Y, X, 2):
+            raise ValueError(f"the volume must be {(Z, Y, X, 2)}, got {tuple(vol.shape)}")
+        nbytes = int(_lib.lib().sobfu_hip_mesh_voxelise_workspace_bytes(C.c_int(X), C.c_int(Y), C.c_int(Z)))
+        if nbytes == 0:
+            raise ValueError(f"cannot voxelise into {X} x {Y} x {Z} voxels (X <= 512)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        open_rows = torch.empty(1, dtype=torch.int32, device=dev)
+        check(_lib.lib().sobfu_hip_mesh_voxelise(*_ws(self.workspace), *self._mesh(), *self._plan, _ptr(vol), C.c_int(X), C.c_int(Y), C.c_int(Z),
+                                                 _vs3(vs), _f(trunc), _f(eta), C.c_int(_MESH_MODES[mode]), *_ws(ws), _ptr(open_rows, torch.int32),
+                                                 _stream()), "mesh_voxelise")
+        return vol, open_rows
+
+    def inside(self, points, mode="auto"):
+        """(n, 4) float32 points -> inside (n,) uint8 (1: the row from the point along +x crosses the mesh an odd number of times), open
+        (n,) uint8 (1: the point's whole row crosses it an odd number of times: the mesh is not closed there)"""
+        if mode not in _MESH_MODES:
+            raise ValueError(f"unknown mode {mode!r}")
+        n = int(points.shape[0])
+        ins = torch.empty(n, dtype=torch.uint8, device=points.device)
+        opn = torch.empty(n, dtype=torch.uint8, device=points.device)
+        if n:
+            check(_lib.lib().sobfu_hip_mesh_inside(*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(points, "points"), C.c_int(n),
+                                                   _ptr(ins, torch.uint8), _ptr(opn, torch.uint8), C.c_int(_MESH_MODES[mode]), _stream()), "mesh_inside")
+        return ins, opn
+
     def unresolved(self):
         """how many points of the last query hit the ring cap and were finished by brute force (synchronises)"""
         n = C.c_int(0)
