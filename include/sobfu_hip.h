@@ -49,7 +49,9 @@ int sobfu_hip_clear_volume(float* d_vol, int X, int Y, int Z, void* stream);
 /* integrate(dists, volume, aff, proj) (tsdf_volume.cu:56-101,141-162).  d_dists: pitched float image
  * (step in bytes) of ray lengths in metres; R (row-major 3x3) and t: vol2cam = camera_pose^-1 * volume_pose
  * (src/kfusion/tsdf_volume.cpp:95-106); voxel_size[3]; trunc/eta in metres.  Voxels that project outside
- * the image, onto Dp <= 0 or behind the camera are left untouched. */
+ * the image, onto Dp <= 0 or behind the camera are left untouched.  A voxel's camera point is R * centre + t
+ * for any rotation (the z march adds R * (0, 0, vs_z) per plane; the reference adds (0, 0, vs_z), which is
+ * the same bits for the rotations it passes -- third column (0, 0, 1) -- and not the voxel otherwise). */
 int sobfu_hip_integrate_depth(const float* d_dists, int dists_step_bytes, int rows, int cols, float* d_vol, int X,
                               int Y, int Z, const float voxel_size[3], float trunc_dist, float eta,
                               const float R[9], const float t[3], float fx, float fy, float cx, float cy,

@@ -252,7 +252,10 @@ void so_integrate_depth(const float *dists, int step_bytes, int rows, int cols, 
             float camx = dot3(R + 0, vcx, vcy, vcz) + t[0];                              /* :72 */
             float camy = dot3(R + 3, vcx, vcy, vcz) + t[1];
             float camz = dot3(R + 6, vcx, vcy, vcz) + t[2];
-            for (int i = 0; i < Z; ++i, camx += 0.f, camy += 0.f, camz += vsz) {        /* :76 */
+            /* :76 adds (0, 0, vsz) in the camera frame: right only while R's third column is (0, 0, 1), which is all the reference
+             * passes.  The step is R * (0, 0, vsz) -- the same bits for such an R, the voxel's true step for a rotated vol2cam. */
+            const float sx = R[2] * vsz, sy = R[5] * vsz, sz = R[8] * vsz;
+            for (int i = 0; i < Z; ++i, camx += sx, camy += sy, camz += sz) {
                 float coox = fmaf(fx, so_div(camx, camz), cx), cooy = fmaf(fy, so_div(camy, camz), cy); /* device.hpp:38-39 */
                 if (coox < 0 || cooy < 0 || coox >= (float) cols || cooy >= (float) rows) continue; /* :79 */
                 if (!(camz > 0)) continue; /* :84 second clause, hoisted before the fetch (both `continue`) */

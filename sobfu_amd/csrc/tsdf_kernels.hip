@@ -36,9 +36,13 @@ __global__ void __launch_bounds__(256) integrate_depth_kernel(IntegrateArgs a) {
     float camx = dot3(a.R + 0, vcx, vcy, vcz) + a.t[0];
     float camy = dot3(a.R + 3, vcx, vcy, vcz) + a.t[1];
     float camz = dot3(a.R + 6, vcx, vcy, vcz) + a.t[2];
-    for (int i = 0; i < z0 + a.zbase; ++i) camx += 0.f, camy += 0.f, camz += a.vsz;  // replay of `vc_cam += zstep` (:76)
+    // `vc_cam += zstep` (:76).  The reference adds (0, 0, vs_z) in the CAMERA frame, which is the voxel's step only while R's third column
+    // is (0, 0, 1) -- all the reference ever passes.  The step here is R * (0, 0, vs_z): the same bits for such an R (0 * vs_z = 0,
+    // 1 * vs_z = vs_z), and the voxel centre's true camera point under the rotated vol2cam of a tracked camera.
+    const float sx = a.R[2] * a.vsz, sy = a.R[5] * a.vsz, sz = a.R[8] * a.vsz;
+    for (int i = 0; i < z0 + a.zbase; ++i) camx += sx, camy += sy, camz += sz;  // replay of the running sums
     int z1 = min(z0 + kZC, a.d.z);
-    for (int z = z0; z < z1; ++z, camx += 0.f, camy += 0.f, camz += a.vsz) {
+    for (int z = z0; z < z1; ++z, camx += sx, camy += sy, camz += sz) {
         float coox = __builtin_fmaf(a.fx, camx / camz, a.cx), cooy = __builtin_fmaf(a.fy, camy / camz, a.cy);
         if (coox < 0 || cooy < 0 || coox >= (float) a.cols || cooy >= (float) a.rows) continue;
         if (!(camz > 0)) continue;
