@@ -331,7 +331,11 @@ int sobfu_hip_mc_indexed_generate(void* stream, const float* d_vol, int X, int Y
 /* raycast: pixel (u, v) casts ((u - cx) / fx, (v - cy) / fy, 1) from the camera of vol2cam = (R row-major, t) -- the pose argument of
  * sobfu_hip_integrate_depth -- through the trilinear TSDF; a hit is the first front-face zero crossing between two samples whose 8
  * corner weights are all > 0.  Hit: point (x, y, z, 0) in the camera frame, normal (nx, ny, nz, 1); miss: both all zero.
- * step_factor: the fine step in units of the smallest voxel size (KinFu: 0.75); trunc: the truncation distance in metres. */
+ * step_factor: the fine step in units of the smallest voxel size (KinFu: 0.75); trunc: the truncation distance in metres.
+ * A corner weight that is not > 0 (0, negative, NaN) makes a sample invalid.  SOBFU_E_BADARG, before any launch: X, Y or Z < 2, rows or
+ * cols < 1, a step below cols * 16 or a step / pointer off 16 bytes, a voxel size, trunc or step_factor that is not positive and finite,
+ * fx or fy 0, non-finite intrinsics, or a NaN / Inf anywhere in R or t (as sobfu_hip_mesh_render).  SOBFU_E_UNSUPPORTED: a step so small
+ * that the box diagonal takes 10^6 fine steps or more. */
 int sobfu_hip_raycast(const float* d_vol, int X, int Y, int Z, float vsx, float vsy, float vsz, float trunc, const float R[9],
                       const float t[3], float fx, float fy, float cx, float cy, int rows, int cols, float step_factor, float* d_points,
                       int points_step, float* d_normals, int normals_step, void* stream);

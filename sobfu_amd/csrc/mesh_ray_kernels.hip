@@ -247,11 +247,6 @@ __global__ void __launch_bounds__(256) mesh_render_kernel(Grid g, RenderArgs a) 
 
 // a pitched output image that may be absent: room for cols elements of `size` bytes per row, aligned to `to`
 bool image_ok(const void* p, int step, int cols, int size, int to) { return !p || ((long long) step >= (long long) cols * size && aligned(p, step, to)); }
-bool finite_all(const float* v, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
 float unlimited(float t_max) { return t_max > 0.f ? t_max : INFINITY; }
 
 }  // namespace

@@ -152,7 +152,7 @@ int sobfu_hip_raycast(const float* d_vol, int X, int Y, int Z, float vsx, float 
     SOBFU_CHECK_ARGS(aligned(d_points, points_step, 16) && aligned(d_normals, normals_step, 16));
     SOBFU_CHECK_ARGS(positive_finite(trunc) && positive_finite(step_factor));
     SOBFU_CHECK_ARGS(positive_finite(vsx) && positive_finite(vsy) && positive_finite(vsz));
-    SOBFU_CHECK_ARGS(intr_ok(fx, fy, cx, cy));
+    SOBFU_CHECK_ARGS(intr_ok(fx, fy, cx, cy) && finite_all(R, 9) && finite_all(t, 3));
     RaycastArgs a{(const float2*) d_vol, {X, Y, Z}, vsx, vsy, vsz, trunc, {}, {}, {}, fx, fy, cx, cy, rows, cols, 0.f, 0,
                   (float4*) d_points, points_step, (float4*) d_normals, normals_step};
     fill_pose(R, t, a.R, a.Rt, nullptr);

@@ -64,7 +64,8 @@ SOBFU_DEV float sample_tsdf(const float2* __restrict__ v, const Dims& d, float g
     const Cell c = cell_at(v, d, gx, gy, gz);
     const float2 ggg = c.base[0], ggh = c.base[c.dz], ghg = c.base[c.dy], ghh = c.base[c.dy + c.dz];
     const float2 hgg = c.base[c.dx], hgh = c.base[c.dx + c.dz], hhg = c.base[c.dx + c.dy], hhh = c.base[c.dx + c.dy + c.dz];
-    valid = fminf(fminf(fminf(ggg.y, ggh.y), fminf(ghg.y, ghh.y)), fminf(fminf(hgg.y, hgh.y), fminf(hhg.y, hhh.y))) > 0.f;
+    // comparisons, not a minimum: fminf drops a NaN operand, and a NaN weight is not > 0
+    valid = ggg.y > 0.f && ggh.y > 0.f && ghg.y > 0.f && ghh.y > 0.f && hgg.y > 0.f && hgh.y > 0.f && hhg.y > 0.f && hhh.y > 0.f;
     return tri_lerp(c, ggg.x, ggh.x, ghg.x, ghh.x, hgg.x, hgh.x, hhg.x, hhh.x);
 }
 

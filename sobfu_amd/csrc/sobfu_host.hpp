@@ -68,6 +68,11 @@ inline hipError_t event_create(EventPtr& out, unsigned flags) {
 // the pointer and the row size of its pitched image (bytes; 0 for a dense array) are multiples of `to`
 inline bool aligned(const void* p, long long step, int to) { return ((uintptr_t) p % (uintptr_t) to) == 0 && step % to == 0; }
 inline bool positive_finite(float x) { return std::isfinite(x) && x > 0.f; }
+inline bool finite_all(const float* v, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
 inline bool intr_ok(float fx, float fy, float cx, float cy) {
     return std::isfinite(fx) && std::isfinite(fy) && fx != 0.f && fy != 0.f && std::isfinite(cx) && std::isfinite(cy);
 }

@@ -1,6 +1,6 @@
 """float32 numpy restatement of the colour kernels of sobfu_amd/csrc/colour_kernels.hip, in the kernels' operation order: integrate_colour,
 the renormalised trilinear colour sampler (apply_colour, sample_colour) and render_colour.  fmaf / dot3 / tri_setup are those of
-tests/render_reference.py (fmaf through float64: only the rare double rounding of a sum can differ from the device).  Used by
+tests/render_reference.py (an exact fmaf: one rounding, as on the device).  Used by
 tests/test_colour_cpu.py and tests/test_gpu_colour.py."""
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 """float32 numpy restatement of the indexed (welded) marching-cubes path of sobfu_amd/csrc/mc_kernels.hip: the edge rule, the vertex
-order, positions, normals and faces.  fmaf / dot3 are those of tests/render_reference.py (fmaf through float64).  Used by
+order, positions, normals and faces.  fmaf / dot3 are those of tests/render_reference.py (an exact fmaf, one rounding).  Used by
 tests/test_mc_indexed_cpu.py (against the oracle's triangle soup) and tests/test_gpu_mc_indexed.py (against the HIP path)."""
 from __future__ import annotations
 

@@ -1,7 +1,7 @@
 """float32 numpy restatement of sobfu_amd/csrc/warp_points_kernels.hip in the kernels' operation order: points and normals carried through
 psi (warp_points) and a TSDF sampled at points (sample_tsdf).  The point -> grid mapping is tests/colour_reference.py's (sample_colour),
-the valid sampler tests/render_reference.py's; fma / dot3 / lerp1 / tri_setup are render_reference's (fmaf through float64: only the rare
-double rounding of a sum can differ from the device).  Used by tests/test_mesh_warp_cpu.py and tests/test_gpu_mesh_warp.py."""
+the valid sampler tests/render_reference.py's; fma / dot3 / lerp1 / tri_setup are render_reference's (its fma is an exact fmaf: one
+rounding, as on the device).  Used by tests/test_mesh_warp_cpu.py and tests/test_gpu_mesh_warp.py."""
 from __future__ import annotations
 
 import numpy as np

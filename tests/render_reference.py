@@ -1,8 +1,10 @@
 """float32 numpy restatement of the raycaster and the two shaders of sobfu_amd/csrc/render_kernels.hip, in the kernel's operation order.
 
-fmaf(a, b, c) is evaluated as float32(float64(a) * float64(b) + float64(c)): the product of two floats is exact in double, so only the
-rare double rounding of the sum can differ from the device's single rounding.  Every ray is marched in lock step with the others
-(vectorised over rays); a ray's arithmetic does not depend on the others.  Used by tests/test_render_cpu.py, tests/test_gpu_render.py
+fmaf(a, b, c) is exact (one rounding, as the device's): the product of two floats is exact in float64, the sum is rounded to odd in
+float64 -- where the float64 sum is inexact and its last mantissa bit is even, it moves one ulp toward the exact sum (the sign of the
+TwoSum error says which way) -- and that is rounded to float32; 53 >= 2 * 24 + 2 bits make the second rounding the only one that counts.
+tests/test_render_cpu.py compares it with libm's fmaf.  Every ray is marched in lock step with the others (vectorised over rays); a
+ray's arithmetic does not depend on the others.  Used by tests/test_render_cpu.py, tests/test_gpu_render.py
 and tools/render_time.py (samples per ray)."""
 from __future__ import annotations
 
@@ -11,8 +13,26 @@ import numpy as np
 F = np.float32
 
 
-def fma(a, b, c):
+def fma_double_rounded(a, b, c):
+    """float32(float64(a) * float64(b) + float64(c)): rounds the sum twice, so it differs from fmaf at float32 ties (kept for the test
+    that shows fma below is not this)"""
     return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F)
+
+
+def fma(a, b, c):
+    """fmaf on float32 values, one rounding (the module docstring says how)"""
+    a, b, c = np.broadcast_arrays(np.asarray(a, F), np.asarray(b, F), np.asarray(c, F))
+    shape = a.shape
+    with np.errstate(all="ignore"):
+        p = np.atleast_1d(a).astype(np.float64) * np.atleast_1d(b).astype(np.float64)  # exact
+        c = np.atleast_1d(c).astype(np.float64)
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)  # TwoSum: s + e = p + c exactly (NaN where s is not finite)
+        bits = s.view(np.int64)
+        odd = (e != 0) & np.isfinite(e) & np.isfinite(s) & ((bits & 1) == 0)
+        toward = np.where((e > 0) == (s > 0), 1, -1)  # the magnitude grows when e has the sign of s
+        return np.where(odd, bits + toward, bits).view(np.float64).astype(F).reshape(shape)
 
 
 def lerp1(v0, v1, t):  # sobfu_device.hpp: fma(t, v0, fma(-t, v1, v1))
@@ -20,7 +40,8 @@ def lerp1(v0, v1, t):  # sobfu_device.hpp: fma(t, v0, fma(-t, v1, v1))
 
 
 def dot3(a, bx, by, bz):  # fma(a0, bx, fma(a1, by, a2 * bz))
-    return fma(a[0], bx, fma(a[1], by, F(a[2]) * bz))
+    with np.errstate(invalid="ignore"):  # 0 * Inf
+        return fma(a[0], bx, fma(a[1], by, F(a[2]) * bz))
 
 
 def tri_setup(p, dim):
@@ -93,8 +114,11 @@ def _clip(o, D, top, tmin, tmax):
     return tmin.astype(F), tmax.astype(F)
 
 
-def raycast(vol, vs, trunc, R, t, intr, rows, cols, step_factor=0.75, return_samples=False):
-    """vol: (Z, Y, X, 2) float32 -> points, normals (rows, cols, 4) float32 [, samples per ray (rows, cols) int]"""
+def raycast(vol, vs, trunc, R, t, intr, rows, cols, step_factor=0.75, return_samples=False, trace=None):
+    """vol: (Z, Y, X, 2) float32 -> points, normals (rows, cols, 4) float32 [, samples per ray (rows, cols) int].  trace: a dict that
+    receives what the march did per ray, (rows, cols) arrays -- `enters` (tmin <= tmax), `crossing` (a crossing was found, whether
+    or not its gradient made it a hit), `regained` (a valid sample after an invalid one after a valid one), `samples` -- and the
+    host's `max_steps`, `D` and `O`"""
     Z, Y, X = vol.shape[:3]
     dims = (X, Y, Z)
     flat = np.ascontiguousarray(vol, F).reshape(-1, 2)
@@ -115,12 +139,18 @@ def raycast(vol, vs, trunc, R, t, intr, rows, cols, step_factor=0.75, return_sam
 
     act = np.nonzero(tmin.reshape(n) <= tmax)[0]
     z = tmin.reshape(n)[act]
+    crossing, stage = np.zeros(n, bool), np.zeros(n, np.int8)  # stage: 1 valid seen, 2 then invalid, 3 then valid again
+
+    def note(ids, ok):
+        st = stage[ids]
+        stage[ids] = np.where(ok & (st != 1), np.where(st == 0, 1, 3), np.where(~ok & (st == 1), 2, st))
 
     def g_at(zz, ids):
         return [fma(zz, D[i][ids], O[i]) for i in range(3)]
 
     f, valid = sample(flat, dims, *g_at(z, act))
     samples[act] += 1
+    note(act, valid)
     for _ in range(max_steps):
         if act.size == 0:
             break
@@ -134,9 +164,11 @@ def raycast(vol, vs, trunc, R, t, intr, rows, cols, step_factor=0.75, return_sam
             break
         f, valid = sample(flat, dims, *g_at(z, act))
         samples[act] += 1
+        note(act, valid)
         hit = vp & (fp > 0) & valid & (f < 0)
         if hit.any():
             h = act[hit]
+            crossing[h] = True
             zs = (zp[hit] + ((z[hit] - zp[hit]) * fp[hit] / (fp[hit] - f[hit])).astype(F)).astype(F)
             gx, gy, gz = g_at(zs, h)
             tops = [F(d - 1) for d in dims]
@@ -155,6 +187,9 @@ def raycast(vol, vs, trunc, R, t, intr, rows, cols, step_factor=0.75, return_sam
             with np.errstate(invalid="ignore", divide="ignore"):
                 normals[hk] = np.stack([c[0][ok] / ln[ok], c[1][ok] / ln[ok], c[2][ok] / ln[ok], np.ones(hk.size, F)], 1)
             act, z, f, valid = act[~hit], z[~hit], f[~hit], valid[~hit]
+    if trace is not None:
+        trace.update(enters=(tmin <= tmax.reshape(rows, cols)), crossing=crossing.reshape(rows, cols), regained=(stage == 3).reshape(rows, cols),
+                     samples=samples.reshape(rows, cols), max_steps=max_steps, D=[d.reshape(rows, cols) for d in D], O=O)
     out = points.reshape(rows, cols, 4), normals.reshape(rows, cols, 4)
     return out + (samples.reshape(rows, cols),) if return_samples else out
 

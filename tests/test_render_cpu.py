@@ -100,3 +100,65 @@ def test_shaders_follow_their_formulas():
     assert col[0, 1].tolist() == [128, 128, 255, 255]
     assert col[1, 0].tolist() == [25, 51, 128, 255]  # (-0.8 * 0.5 + 0.5) * 255 is 25.4999... in float32
     assert col[1, 1].tolist() == [0, 0, 0, 0]
+
+
+def _libm_fmaf(a, b, c):
+    import ctypes
+    import ctypes.util
+
+    m = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    m.fmaf.restype = ctypes.c_float
+    m.fmaf.argtypes = [ctypes.c_float] * 3
+    return np.array([m.fmaf(x, y, z) for x, y, z in zip(a.tolist(), b.tolist(), c.tolist())], np.float32)
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def planted_ties():
+    """a = 1 + k 2^-23, b = 1 + 2^-12, c = +-2^-60: a b has 36 significant bits, so for many k the float64 sum rounds c away and lands
+    on a float32 tie, which the second rounding then breaks to even whatever the sign of c"""
+    k = np.arange(50000, dtype=np.float64)
+    a = np.repeat((1 + k * 2.0 ** -23).astype(np.float32), 2)
+    b = np.full_like(a, 1 + 2.0 ** -12)
+    c = np.tile(np.array([2.0 ** -60, -2.0 ** -60], np.float32), k.size)
+    return a, b, c
+
+
+def test_fma_is_libm_fmaf():
+    """RR.fma against libm's fmaf, bit for bit: random triples across 60 binades, heavy cancellation, float32 ties (where the formula it
+    replaced, float32(float64 sum), is shown to differ), and the special values."""
+    rng = np.random.default_rng(20)
+    n = 100000
+
+    def spread():
+        return (rng.standard_normal(n) * 2.0 ** rng.integers(-30, 30, n)).astype(np.float32)
+
+    a, b = spread(), spread()
+    ab = a.astype(np.float64) * b.astype(np.float64)
+    near = (1 + rng.integers(-4, 5, n) * 2.0 ** -24)
+    with np.errstate(over="ignore"):
+        sets = {"random": (a, b, spread()), "half": (a, b, (-ab / 2 * near).astype(np.float32)), "cancel": (a, b, (-ab * near).astype(np.float32)),
+                "ties": planted_ties()}
+    for name, (a, b, c) in sets.items():
+        want = _libm_fmaf(a, b, c)
+        got = RR.fma(a, b, c)
+        assert got.dtype == np.float32 and got.shape == a.shape
+        assert np.isfinite(want).all(), name
+        assert np.array_equal(_bits(got), _bits(want)), name
+    a, b, c = sets["ties"]
+    old = RR.fma_double_rounded(a, b, c)
+    differs = _bits(old) != _bits(_libm_fmaf(a, b, c))
+    print("double-rounded formula differs on", int(differs.sum()), "of", a.size, "planted ties")
+    assert differs.sum() >= 1
+    # zeros, infinities, NaN: the same class of result, and the sign of a zero
+    sp = np.array([0.0, -0.0, 1.0, -1.0, np.inf, -np.inf, np.nan, 2.0 ** -149, -2.0 ** -149, 3.4e38, -3.4e38, 2.0 ** -126], np.float32)
+    a, b, c = (g.ravel() for g in np.meshgrid(sp, sp, sp, indexing="ij"))
+    want, got = _libm_fmaf(a, b, c), RR.fma(a, b, c)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    ok = ~np.isnan(want)
+    assert np.array_equal(_bits(got)[ok], _bits(want)[ok])  # bits: +-0 and +-inf keep their signs
+    assert (want[ok] == 0).sum() > 50 and np.isinf(want[ok]).sum() > 50 and (~ok).sum() > 50
+    # scalars and broadcasting keep working
+    assert RR.fma(np.float32(2), np.float32(3), np.float32(1)) == 7 and RR.fma(np.float32(2), np.ones(3, np.float32), 1).shape == (3,)
