@@ -263,9 +263,8 @@ public:
         kfusion::cuda::DeviceArray<int> dt(n), du(n);
         dp.upload(points);
         if (closest) dc.create(n);
-        sobfuSafeCall(sobfu_hip_mesh_distance(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
-                                              nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dp.ptr(), (int) n, max_dist, mode, ring_cap,
-                                              dd.ptr(), dt.ptr(), closest ? (float*) dc.ptr() : nullptr, du.ptr(), nullptr));
+        sobfuSafeCall(with_target(sobfu_hip_mesh_distance, (const float*) dp.ptr(), (int) n, max_dist, mode, ring_cap, dd.ptr(), dt.ptr(),
+                                  closest ? (float*) dc.ptr() : nullptr, du.ptr(), nullptr));
         dd.download(dist);
         if (tri) dt.download(*tri);
         if (closest) dc.download(*closest);
@@ -287,10 +286,8 @@ public:
             dp.upload(points);
             dpose.upload(pose, 16);
             dtrace.upload(trace);
-            sobfuSafeCall(sobfu_hip_mesh_align_estimate(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
-                                                        nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dp.ptr(), n, max_dist, mode,
-                                                        ring_cap, iters, dof, eps_rot, eps_trans, ws.ptr(), ws.size(), dpose.ptr(), dstatus.ptr(),
-                                                        dtrace.ptr(), nullptr));
+            sobfuSafeCall(with_target(sobfu_hip_mesh_align_estimate, (const float*) dp.ptr(), n, max_dist, mode, ring_cap, iters, dof, eps_rot, eps_trans,
+                                      ws.ptr(), ws.size(), dpose.ptr(), dstatus.ptr(), dtrace.ptr(), nullptr));
             std::vector<float> got;
             std::vector<int> st;
             dstatus.download(st);
@@ -327,10 +324,8 @@ public:
         dorg.upload(origins), ddir.upload(dirs);
         if (bary) dbary.create(n);
         if (side) dside.create(n);
-        sobfuSafeCall(sobfu_hip_mesh_raycast(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
-                                             nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dorg.ptr(), (const float*) ddir.ptr(), (int) n,
-                                             t_min, t_max, mode, dt.ptr(), dtri.ptr(), bary ? (float*) dbary.ptr() : nullptr,
-                                             side ? (int8_t*) dside.ptr() : nullptr, nullptr));
+        sobfuSafeCall(with_target(sobfu_hip_mesh_raycast, (const float*) dorg.ptr(), (const float*) ddir.ptr(), (int) n, t_min, t_max, mode, dt.ptr(),
+                                  dtri.ptr(), bary ? (float*) dbary.ptr() : nullptr, side ? (int8_t*) dside.ptr() : nullptr, nullptr));
         dt.download(t), dtri.download(tri);
         if (bary) dbary.download(*bary);
         if (side) dside.download(*side);
@@ -361,14 +356,13 @@ public:
         if (points) points->create(cam.rows, cam.cols);
         if (normals) normals->create(cam.rows, cam.cols);
         if (tri) tri->create(cam.rows, cam.cols);
-        sobfuSafeCall(sobfu_hip_mesh_render(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
-                                            nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, vertex_normals && nv_ ? (const float*) dnrm.ptr() : nullptr,
-                                            vertex_colours && nv_ ? (const uint8_t*) dcol.ptr() : nullptr, cam.R, cam.t, cam.fx, cam.fy, cam.cx, cam.cy, cam.rows,
-                                            cam.cols, cam.z_min, cam.z_max, depth ? depth->ptr() : nullptr, depth ? (int) depth->step() : 0,
-                                            points ? (float*) points->ptr() : nullptr, points ? (int) points->step() : 0,
-                                            normals ? (float*) normals->ptr() : nullptr, normals ? (int) normals->step() : 0,
-                                            colour ? (uint8_t*) colour->ptr() : nullptr, colour ? (int) colour->step() : 0, tri ? tri->ptr() : nullptr,
-                                            tri ? (int) tri->step() : 0, nullptr));
+        sobfuSafeCall(with_target(sobfu_hip_mesh_render, vertex_normals && nv_ ? (const float*) dnrm.ptr() : nullptr,
+                                  vertex_colours && nv_ ? (const uint8_t*) dcol.ptr() : nullptr, cam.R, cam.t, cam.fx, cam.fy, cam.cx, cam.cy, cam.rows, cam.cols,
+                                  cam.z_min, cam.z_max, depth ? depth->ptr() : nullptr, depth ? (int) depth->step() : 0,
+                                  points ? (float*) points->ptr() : nullptr, points ? (int) points->step() : 0,
+                                  normals ? (float*) normals->ptr() : nullptr, normals ? (int) normals->step() : 0,
+                                  colour ? (uint8_t*) colour->ptr() : nullptr, colour ? (int) colour->step() : 0, tri ? tri->ptr() : nullptr,
+                                  tri ? (int) tri->step() : 0, nullptr));
         sobfuSafeCall(hipDeviceSynchronize());  // the vertex attributes uploaded above are released on return
     }
     // ---- this mesh, closed, as a signed TSDF volume and an inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip, DESIGN.md 4.12;
@@ -382,9 +376,8 @@ public:
         if (bytes == 0) kfusion::cuda::error("TriangleGrid::voxelise: at most 512 voxels along x", __FILE__, __LINE__);
         kfusion::cuda::DeviceArray<unsigned char> ws(bytes);
         kfusion::cuda::DeviceArray<int> open_rows(1);
-        sobfuSafeCall(sobfu_hip_mesh_voxelise(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
-                                              nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, d_vol, dims[0], dims[1], dims[2], vs, trunc, eta, mode,
-                                              ws.ptr(), ws.size(), open_rows.ptr(), nullptr));
+        sobfuSafeCall(with_target(sobfu_hip_mesh_voxelise, d_vol, dims[0], dims[1], dims[2], vs, trunc, eta, mode, ws.ptr(), ws.size(), open_rows.ptr(),
+                                  nullptr));
         std::vector<int> n;
         open_rows.download(n);
         return n[0];
@@ -398,9 +391,7 @@ public:
         kfusion::cuda::DeviceArray<float4> dp;
         kfusion::cuda::DeviceArray<unsigned char> di(n), dopen(n);
         dp.upload(points);
-        sobfuSafeCall(sobfu_hip_mesh_inside(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_,
-                                            nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_, dims_, (const float*) dp.ptr(), (int) n, di.ptr(), dopen.ptr(), mode,
-                                            nullptr));
+        sobfuSafeCall(with_target(sobfu_hip_mesh_inside, (const float*) dp.ptr(), (int) n, di.ptr(), dopen.ptr(), mode, nullptr));
         di.download(inside), dopen.download(open);
     }
     bool built() const { return built_; }
@@ -409,6 +400,12 @@ public:
     float cell() const { return h_; }
 
 private:
+    // a mesh entry point of the C ABI, called with its nine leading arguments (the grid's workspace, the mesh, the plan) ahead of the caller's
+    template <class F, class... A>
+    int with_target(F f, A... a) {
+        return f(workspace_.ptr(), workspace_.size(), nv_ ? (const float*) vertices_.ptr() : nullptr, nv_, nt_ ? faces_.ptr() : nullptr, nt_, origin_, h_,
+                 dims_, a...);
+    }
     kfusion::cuda::DeviceArray<float4> vertices_;
     kfusion::cuda::DeviceArray<int> faces_;
     kfusion::cuda::DeviceArray<unsigned char> workspace_;

@@ -54,23 +54,19 @@
 // reduces them with a wave64 __shfl_xor butterfly and then across its 4 waves through LDS (wave 0 + 1 + 2 + 3, in that order), and writes
 // one 32-float slab.  No float atomics anywhere: the sums, and so the pose, are bitwise reproducible.  The solve is one 256-thread
 // workgroup: thread j converts slab j to fp64, the same butterfly and LDS order reduce the slabs, lane 0 solves.  Every index of the
-// 6 x 6 system is a compile-time constant (fully unrolled loops): nothing goes to scratch.  The LDL^T, Rodrigues and the pose
-// composition are sobfu_rigid.hpp's, shared with mesh_align_kernels.hip.
+// 6 x 6 system is a compile-time constant (fully unrolled loops): nothing goes to scratch.  The sums of a row, the workgroup reduction,
+// the unpacking into A x = b, the pose update and the four launch constants (kMaxParts = the solve's workgroup size) are
+// sobfu_normal_eq.hpp's, shared with mesh_align_kernels.hip; the LDL^T, Rodrigues and the pose composition are sobfu_rigid.hpp's.
 #include "sobfu_frame.hpp"
 #include "sobfu_hip.h"
 #include "sobfu_host.hpp"
-#include "sobfu_rigid.hpp"
+#include "sobfu_normal_eq.hpp"
 
 #include <cmath>
 
 using namespace sobfu_hip;
 
 namespace {
-
-constexpr int kSums = 29;
-constexpr int kSlab = 32;       // floats per partial slab
-constexpr int kMaxParts = 256;  // partial slabs of one correspondence pass (= the solve's workgroup size)
-constexpr int kThreads = 256;
 
 SOBFU_DEV bool finite3(float x, float y, float z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 SOBFU_DEV bool valid_pn(const float4& p, const float4& n) {
@@ -197,32 +193,6 @@ struct IcpLevel {
     Reproj rp;  // the level's intrinsics
 };
 
-// wave64 butterfly over N values: every lane ends with the sum in the same (fixed) association order
-template <class T, int N>
-SOBFU_DEV void wave_sum(T (&v)[N]) {
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] += __shfl_xor(v[k], h, 64);
-    }
-}
-
-// workgroup sum of N values per thread (4 waves): the wave butterfly, then wave 0 + 1 + 2 + 3 through LDS; valid in wave 0
-template <class T, int N>
-SOBFU_DEV void block_sum(T (&v)[N], T (*lds)[N]) {
-    wave_sum<T, N>(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) lds[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
-    }
-}
-
 // correspondence code of pixel (x, y); on 0, s, d and nd of the pair
 template <bool DEPTH>
 SOBFU_DEV int correspond(const IcpLevel& L, const float* aff, int x, int y, float3& s, float3& d, float3& nd) {
@@ -288,17 +258,8 @@ __global__ void __launch_bounds__(kThreads) icp_correspond_kernel(IcpLevel L, co
         if (codes) row_ptr(codes, codes_step, y)[x] = (uint8_t) code;
         if (code == 0) {
             const float r = nd.x * (d.x - s.x) + nd.y * (d.y - s.y) + nd.z * (d.z - s.z);
-            const float row[7] = {s.y * nd.z - s.z * nd.y, s.z * nd.x - s.x * nd.z, s.x * nd.y - s.y * nd.x, nd.x, nd.y, nd.z, r};
-            int k = 0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-#pragma unroll
-                for (int j = i; j < 6; ++j) acc[k++] += row[i] * row[j];
-            }
-#pragma unroll
-            for (int i = 0; i < 6; ++i) acc[21 + i] += row[i] * r;
-            acc[27] += 1.f;
-            acc[28] += r * r;
+            const float row[6] = {s.y * nd.z - s.z * nd.y, s.z * nd.x - s.x * nd.z, s.x * nd.y - s.y * nd.x, nd.x, nd.y, nd.z};
+            add_row(acc, row, r);
         }
     }
     block_sum<float, kSums>(acc, lds);
@@ -335,16 +296,7 @@ __global__ void __launch_bounds__(kThreads) icp_solve_kernel(const float* __rest
         trace[1] = acc[27] > 0.0 ? (float) sqrt(acc[28] / acc[27]) : 0.f;
     }
     double A[6][6], b[6];
-    {
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-#pragma unroll
-            for (int c = r; c < 6; ++c) A[r][c] = A[c][r] = acc[k++];
-        }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) b[r] = acc[21 + r];
-    }
+    unpack_sums(acc, A, b);
     Ldlt<6> f;
     ldlt_factor<6>(A, f);
     if (!(fabs(f.det) >= 1e-15) || !f.positive) {
@@ -355,12 +307,7 @@ __global__ void __launch_bounds__(kThreads) icp_solve_kernel(const float* __rest
     ldlt_solve<6>(f, b, x);
     // Tinc = (Rodrigues(x0..2), x3..5)
     const double w[3] = {x[0], x[1], x[2]}, t[3] = {x[3], x[4], x[5]};
-    double R[9];
-    rodrigues(w, R);
-    float P[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) P[k] = pose[k];
-    pose_compose(R, t, P, pose);
+    apply_increment(w, t, pose);
 }
 
 Reproj level_reproj(float fx, float fy, float cx, float cy, int level) {

@@ -2,7 +2,8 @@
 // triangles of mesh_distance_kernels.hip, the whole loop enqueued on one stream with no host synchronisation.  The
 // reference has no such step; the rules are this project's, and tests/mesh_align_reference.py restates them in the same operation order
 // (every TU is built with -ffp-contract=off; there is no fused operation and no fast division in this file).  The 6 x 6 solve, Rodrigues,
-// the pose composition and the rigid inverse are sobfu_rigid.hpp's.
+// the pose composition and the rigid inverse are sobfu_rigid.hpp's; the sums of a row, the workgroup reduction, the unpacking into A x = b,
+// the pose update and the launch constants sobfu_normal_eq.hpp's, shared with icp_kernels.hip; the target and its check sobfu_mesh.hpp's.
 //
 //   pose         16 floats in device memory, row-major 4 x 4, mapping the source (the points) to the target (the mesh) frame; rows 0..2 are
 //                read and written, row 3 is the caller's
@@ -31,17 +32,13 @@
 //   trace        optional, 4 floats per iteration: inliers, sqrt(sum r r / inliers) (0 without inliers), |w|, |t_inc| (both 0 on the failed
 //                iteration).  Entries of iterations that did not run are not written.
 #include "sobfu_hip.h"
-#include "sobfu_host.hpp"
-#include "sobfu_rigid.hpp"
+#include "sobfu_mesh.hpp"
+#include "sobfu_normal_eq.hpp"
 
 using namespace sobfu_hip;
 
 namespace {
 
-constexpr int kSums = 29;
-constexpr int kSlab = 32;       // doubles per partial slab
-constexpr int kMaxParts = 256;  // partial slabs of one pass
-constexpr int kThreads = 256;
 constexpr int kMaxIters = 1000;
 
 __global__ void __launch_bounds__(kThreads) align_transform_kernel(const float* __restrict__ pose, const int* __restrict__ status,
@@ -57,25 +54,6 @@ __global__ void __launch_bounds__(kThreads) align_transform_kernel(const float* 
     }
 }
 
-// wave64 butterfly, then wave 0 + 1 + 2 + 3 through LDS: every run adds in the same order; valid in wave 0
-__device__ __forceinline__ void block_sum(double (&v)[kSums], double (*lds)[kSums]) {
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) v[k] += __shfl_xor(v[k], h, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) lds[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) v[k] = ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
-    }
-}
-
 __global__ void __launch_bounds__(kThreads) align_sums_kernel(const int* __restrict__ status, const float4* __restrict__ src,
                                                               const float4* __restrict__ s4, const int* __restrict__ tri,
                                                               const float4* __restrict__ closest, const float4* __restrict__ verts,
@@ -88,8 +66,8 @@ __global__ void __launch_bounds__(kThreads) align_sums_kernel(const int* __restr
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
         const float4 p = src[i];
         const int t = tri[i];
-        if (!(fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY) || t < 0 || t >= n_triangles) continue;
-        const float4 a = verts[faces[3 * (size_t) t]], b = verts[faces[3 * (size_t) t + 1]], c2 = verts[faces[3 * (size_t) t + 2]];
+        if (!finite3(p) || t < 0 || t >= n_triangles) continue;
+        const auto [a, b, c2] = corners_of(Mesh{verts, faces, n_triangles}, t);
         const double ux = (double) b.x - (double) a.x, uy = (double) b.y - (double) a.y, uz = (double) b.z - (double) a.z;
         const double vx = (double) c2.x - (double) a.x, vy = (double) c2.y - (double) a.y, vz = (double) c2.z - (double) a.z;
         const double mx = uy * vz - uz * vy, my = uz * vx - ux * vz, mz = ux * vy - uy * vx;
@@ -100,18 +78,9 @@ __global__ void __launch_bounds__(kThreads) align_sums_kernel(const int* __restr
         const double sx = sf.x, sy = sf.y, sz = sf.z;
         const double r = (nx * ((double) cf.x - sx) + ny * ((double) cf.y - sy)) + nz * ((double) cf.z - sz);
         const double row[6] = {sy * nz - sz * ny, sz * nx - sx * nz, sx * ny - sy * nx, nx, ny, nz};
-        int k = 0;
-#pragma unroll
-        for (int ii = 0; ii < 6; ++ii) {
-#pragma unroll
-            for (int j = ii; j < 6; ++j) acc[k++] += row[ii] * row[j];
-        }
-#pragma unroll
-        for (int ii = 0; ii < 6; ++ii) acc[21 + ii] += row[ii] * r;
-        acc[27] += 1.0;
-        acc[28] += r * r;
+        add_row(acc, row, r);
     }
-    block_sum(acc, lds);
+    block_sum<double, kSums>(acc, lds);
     if (threadIdx.x == 0) {
         double* o = parts + (size_t) blockIdx.x * kSlab;
 #pragma unroll
@@ -150,14 +119,7 @@ __global__ void __launch_bounds__(64) align_solve_kernel(const double* __restric
     bool ok;
     if (dof == 6) {
         double A[6][6], b[6], x[6];
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-#pragma unroll
-            for (int c = r; c < 6; ++c) A[r][c] = A[c][r] = acc[k++];
-        }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) b[r] = acc[21 + r];
+        unpack_sums(acc, A, b);
         Ldlt<6> f;
         ldlt_factor<6>(A, f);
         ok = ldlt_ok(f);
@@ -175,13 +137,8 @@ __global__ void __launch_bounds__(64) align_solve_kernel(const double* __restric
         *status = 0x10000 | it;
         return;
     }
-    double R[9];
-    const double th = rodrigues(w, R);
     const double tn = sqrt((tinc[0] * tinc[0] + tinc[1] * tinc[1]) + tinc[2] * tinc[2]);
-    float P[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) P[k] = pose[k];
-    pose_compose(R, tinc, P, pose);
+    const double th = apply_increment(w, tinc, pose);
     if (trace) {
         trace[2] = (float) th;
         trace[3] = (float) tn;
@@ -216,24 +173,19 @@ Workspace carve(void* ws, int n) {
 }
 
 struct Target {
-    void* grid;
-    size_t grid_bytes;
-    const float* vertices;
-    int n_vertices;
-    const int* faces;
-    int n_triangles;
-    const float* origin;
-    float h;
-    const int* dims;
+    MeshTarget m;
     float max_dist;
     int mode, ring_cap;
 };
 int query(const Target& t, const Workspace& w, int n, hipStream_t s) {
-    return sobfu_hip_mesh_distance(t.grid, t.grid_bytes, t.vertices, t.n_vertices, t.faces, t.n_triangles, t.origin, t.h, t.dims, (const float*) w.s, n,
-                                   t.max_dist, t.mode, t.ring_cap, w.dist, w.tri, (float*) w.closest, w.unresolved, (void*) s);
+    const Grid& g = t.m.grid;
+    const float origin[3] = {g.ox, g.oy, g.oz};
+    const int dims[3] = {g.dx, g.dy, g.dz};
+    return sobfu_hip_mesh_distance(g.hdr, t.m.ws_bytes, (const float*) t.m.mesh.verts, t.m.n_vertices, t.m.mesh.faces, t.m.mesh.n_triangles, origin, g.h,
+                                   dims, (const float*) w.s, n, t.max_dist, t.mode, t.ring_cap, w.dist, w.tri, (float*) w.closest, w.unresolved, (void*) s);
 }
-// every check of both entry points; the mesh and grid arguments are sobfu_hip_mesh_distance's to judge, asked with no points (it launches
-// nothing then)
+// every check of both entry points after mesh_target's; the query's own arguments are sobfu_hip_mesh_distance's to judge, asked with no
+// points (it launches nothing then)
 bool args_ok(const Target& t, const float* d_points, int n, const float* d_pose, void* ws, size_t ws_bytes) {
     if (!(d_pose && aligned(d_pose, 0, 4) && n >= 0 && ws && aligned(ws, 0, 16) && ws_bytes >= workspace_bytes_of(n))) return false;
     if (!(d_points && aligned(d_points, 0, 16))) return false;
@@ -247,7 +199,7 @@ int enqueue_pass(const Target& t, const Workspace& w, const float* d_points, int
     SOBFU_HIP_TRY(hipGetLastError());
     SOBFU_TRY(query(t, w, n, s));
     hipLaunchKernelGGL(align_sums_kernel, grid, dim3(kThreads), 0, s, d_status, (const float4*) d_points, (const float4*) w.s, (const int*) w.tri,
-                       (const float4*) w.closest, (const float4*) t.vertices, t.faces, t.n_triangles, n, w.parts);
+                       (const float4*) w.closest, t.m.mesh.verts, t.m.mesh.faces, t.m.mesh.n_triangles, n, w.parts);
     return (int) hipGetLastError();
 }
 
@@ -260,7 +212,8 @@ size_t sobfu_hip_mesh_align_workspace_bytes(int n) { return n < 0 ? 0 : workspac
 int sobfu_hip_mesh_align_step(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
                               int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, float max_dist, int mode,
                               int ring_cap, const float* d_pose, void* d_workspace, size_t workspace_bytes, double* d_sums, void* stream) {
-    const Target t{d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, max_dist, mode, ring_cap};
+    Target t{{}, max_dist, mode, ring_cap};
+    SOBFU_CHECK_ARGS(mesh_target(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &t.m));
     SOBFU_CHECK_ARGS(d_sums && aligned(d_sums, 0, 8) && args_ok(t, d_points, n, d_pose, d_workspace, workspace_bytes));
     if (n == 0) return 0;
     const Workspace w = carve(d_workspace, n);
@@ -274,7 +227,8 @@ int sobfu_hip_mesh_align_estimate(void* d_grid_workspace, size_t grid_workspace_
                                   int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, float max_dist,
                                   int mode, int ring_cap, int iters, int dof, float eps_rot, float eps_trans, void* d_workspace, size_t workspace_bytes,
                                   float* d_pose, int* d_status, float* d_trace, void* stream) {
-    const Target t{d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, max_dist, mode, ring_cap};
+    Target t{{}, max_dist, mode, ring_cap};
+    SOBFU_CHECK_ARGS(mesh_target(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &t.m));
     SOBFU_CHECK_ARGS(d_status && aligned(d_status, 0, 4) && aligned(d_trace, 0, 4) && (dof == 3 || dof == 6) && iters >= 0 && iters <= kMaxIters);
     SOBFU_CHECK_ARGS(eps_rot >= 0.f && eps_trans >= 0.f && std::isfinite(eps_rot) && std::isfinite(eps_trans));
     SOBFU_CHECK_ARGS(args_ok(t, d_points, n, d_pose, d_workspace, workspace_bytes));

@@ -5,9 +5,9 @@
 //   answer   per point: min over all triangles of d2 (closest_on_triangle), the LOWEST triangle index attaining it, that triangle's
 //            closest point; dist = sqrt(min d2).  With max_dist: dist > max_dist -> (+Inf, -1, (0, 0, 0, 0)).  No triangles: the same.
 //            The answer does not depend on the path that finds it: grid and brute force agree bit for bit, run after run.
-//   grid     a uniform grid of cubic cells over the mesh's box (the plan: sobfu_mesh_grid.hpp; the workspace's layout, shared with the ray
-//            kernels that read it: sobfu_mesh_grid_ws.hpp).  A triangle is referenced from every
-//            cell its axis-aligned box overlaps.  build: count per cell (integer atomics) -> exclusive scan (sobfu_scan.hpp) -> fill
+//   grid     a uniform grid of cubic cells over the mesh's box (the plan: sobfu_mesh_grid.hpp; the workspace's layout, the mesh record and
+//            all else the ray and voxel kernels share: sobfu_mesh.hpp).  A triangle is referenced from every cell its axis-aligned box
+//            overlaps (cells_of).  build: count per cell (integer atomics) -> exclusive scan (sobfu_scan.hpp) -> fill
 //            (cursors: the counts, counted back down).  The order of the references inside a cell varies from run to run; the answer
 //            does not (the tie rule).  The count pass also raises a flag for a face index outside [0, n_vertices) or a non-finite
 //            corner: build then returns SOBFU_E_BADARG and the workspace stays unmarked -- every query through it answers (+Inf, -1).
@@ -22,13 +22,12 @@
 //   brute    a 256-lane workgroup per 256 points, the triangles staged through LDS 256 at a time (48 B each), every lane testing the
 //            same triangle (a broadcast LDS read) in ascending index order.  Also the whole call for mode brute and for tiny meshes.
 #include "sobfu_hip.h"
-#include "sobfu_mesh_grid_ws.hpp"
+#include "sobfu_mesh.hpp"
+#include "sobfu_scan.hpp"
 
 using namespace sobfu_hip;
 
 namespace {
-
-constexpr float kMeshMargin = 1e-4f;
 
 // one lane per triangle: FILL = false counts the cells its box overlaps (and checks it), FILL = true writes the references
 template <bool FILL>
@@ -37,23 +36,22 @@ __global__ void __launch_bounds__(256) bin_triangles_kernel(Grid g, const float4
     const int i = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cells = 0;
     if (i < n_triangles) {
-        const int f0 = faces[3 * (size_t) i], f1 = faces[3 * (size_t) i + 1], f2 = faces[3 * (size_t) i + 2];
-        bool ok = f0 >= 0 && f0 < n_vertices && f1 >= 0 && f1 < n_vertices && f2 >= 0 && f2 < n_vertices;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
+        const Mesh m{verts, faces, n_triangles};
+        const int3 f = face_of(m, i);
+        bool ok = f.x >= 0 && f.x < n_vertices && f.y >= 0 && f.y < n_vertices && f.z >= 0 && f.z < n_vertices;
+        Corners t{make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
         if (ok) {
-            a = verts[f0], b = verts[f1], c = verts[f2];
-            ok = finite3(a) && finite3(b) && finite3(c);
+            t  = corners_of(m, f);
+            ok = finite3(t.a) && finite3(t.b) && finite3(t.c);
         }
         if (!ok) {
             if (!FILL) atomicOr(g.hdr + kHdrBad, 1);
         } else {
-            const int x0 = cell_of(fminf(fminf(a.x, b.x), c.x), g.ox, g.h, g.dx), x1 = cell_of(fmaxf(fmaxf(a.x, b.x), c.x), g.ox, g.h, g.dx);
-            const int y0 = cell_of(fminf(fminf(a.y, b.y), c.y), g.oy, g.h, g.dy), y1 = cell_of(fmaxf(fmaxf(a.y, b.y), c.y), g.oy, g.h, g.dy);
-            const int z0 = cell_of(fminf(fminf(a.z, b.z), c.z), g.oz, g.h, g.dz), z1 = cell_of(fmaxf(fmaxf(a.z, b.z), c.z), g.oz, g.h, g.dz);
-            cells = (unsigned long long) (x1 - x0 + 1) * (unsigned long long) (y1 - y0 + 1) * (unsigned long long) (z1 - z0 + 1);
-            for (int z = z0; z <= z1; ++z)
-                for (int y = y0; y <= y1; ++y)
-                    for (int x = x0; x <= x1; ++x) {
+            const CellRange r = cells_of(g, t);
+            cells = (unsigned long long) (r.x1 - r.x0 + 1) * (unsigned long long) (r.y1 - r.y0 + 1) * (unsigned long long) (r.z1 - r.z0 + 1);
+            for (int z = r.z0; z <= r.z1; ++z)
+                for (int y = r.y0; y <= r.y1; ++y)
+                    for (int x = r.x0; x <= r.x1; ++x) {
                         const int cell = x + g.dx * (y + g.dy * z);
                         if (!FILL) {
                             atomicAdd(g.count + cell, 1);
@@ -72,9 +70,7 @@ __global__ void __launch_bounds__(256) bin_triangles_kernel(Grid g, const float4
 }
 
 struct Query {
-    const float4* verts;
-    const int* faces;
-    int n_triangles;
+    Mesh mesh;
     const float4* points;
     int n;
     float max_dist;  // +Inf: unlimited
@@ -104,8 +100,8 @@ SOBFU_DEV void visit_cell(const Grid& g, const Query& a, const P3& p, int cell, 
     const int end = g.start[cell + 1];
     for (int k = g.start[cell]; k < end; ++k) {
         const int t = g.refs[k];
-        const int f0 = a.faces[3 * (size_t) t], f1 = a.faces[3 * (size_t) t + 1], f2 = a.faces[3 * (size_t) t + 2];
-        const Closest c = closest_on_triangle(p, p3(a.verts[f0]), p3(a.verts[f1]), p3(a.verts[f2]));
+        const Corners v = corners_of(a.mesh, t);
+        const Closest c = closest_on_triangle(p, p3(v.a), p3(v.b), p3(v.c));
         if (c.d2 < best.d2 || (c.d2 == best.d2 && t < best.tri)) best = Best{c.d2, t, c.q};
     }
 }
@@ -160,16 +156,11 @@ __global__ void __launch_bounds__(256) brute_force_kernel(const int* __restrict_
     const bool built  = hdr[kHdrBuilt] == 1;
     const P3 p        = p3(a.points[i]);
     Best best{INFINITY, -1, P3{0.f, 0.f, 0.f}};
-    for (int t0 = 0; built && t0 < a.n_triangles; t0 += 256) {
+    for (int t0 = 0; built && t0 < a.mesh.n_triangles; t0 += 256) {
         __syncthreads();  // the previous chunk has been read
-        const int t = t0 + (int) threadIdx.x;
-        if (t < a.n_triangles) {
-            sa[threadIdx.x] = a.verts[a.faces[3 * (size_t) t]];
-            sb[threadIdx.x] = a.verts[a.faces[3 * (size_t) t + 1]];
-            sc[threadIdx.x] = a.verts[a.faces[3 * (size_t) t + 2]];
-        }
+        stage_triangles(a.mesh, t0, sa, sb, sc);
         __syncthreads();
-        const int m = min(256, a.n_triangles - t0);
+        const int m = min(256, a.mesh.n_triangles - t0);
         for (int k = 0; k < m; ++k) {
             const Closest c = closest_on_triangle(p, p3(sa[k]), p3(sb[k]), p3(sc[k]));
             if (c.d2 < best.d2) best = Best{c.d2, t0 + k, c.q};  // ascending index: the first minimum is the lowest
@@ -200,15 +191,15 @@ size_t sobfu_hip_mesh_grid_workspace_bytes(const int dims[3], int max_refs) {
 
 int sobfu_hip_mesh_grid_build(const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles, const float origin[3], float h,
                               const int dims[3], void* d_workspace, size_t workspace_bytes, int max_refs, int* h_refs, void* stream) {
-    SOBFU_CHECK_ARGS(h_refs && grid_args_ok(d_workspace, workspace_bytes, origin, h, dims, max_refs));
-    SOBFU_CHECK_ARGS(mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    MeshTarget tg;
+    SOBFU_CHECK_ARGS(h_refs && mesh_target(d_workspace, workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, max_refs, &tg));
     hipStream_t st = (hipStream_t) stream;
-    const Grid g   = grid_of(d_workspace, origin, h, dims, max_refs);
+    const Grid& g  = tg.grid;
     const int nc   = (int) ncells_of(dims) + 1;
     const dim3 blocks((unsigned) (((long long) n_triangles + 255) / 256));
     SOBFU_HIP_TRY(hipMemsetAsync(g.hdr, 0, (size_t) (kHdrInts + nc) * sizeof(int), st));
     if (n_triangles > 0) {
-        hipLaunchKernelGGL(bin_triangles_kernel<false>, blocks, dim3(256), 0, st, g, (const float4*) d_vertices, n_vertices, d_faces, n_triangles);
+        hipLaunchKernelGGL(bin_triangles_kernel<false>, blocks, dim3(256), 0, st, g, tg.mesh.verts, n_vertices, d_faces, n_triangles);
         SOBFU_HIP_TRY(hipGetLastError());
     }
     SOBFU_TRY(scan_exclusive(g.count, nc, g.start, g.blk, st));
@@ -222,7 +213,7 @@ int sobfu_hip_mesh_grid_build(const float* d_vertices, int n_vertices, const int
     *h_refs = (int) total;
     if ((int) total > max_refs) return SOBFU_E_UNSUPPORTED;  // the caller enlarges the workspace to *h_refs and builds again
     if (n_triangles > 0) {
-        hipLaunchKernelGGL(bin_triangles_kernel<true>, blocks, dim3(256), 0, st, g, (const float4*) d_vertices, n_vertices, d_faces, n_triangles);
+        hipLaunchKernelGGL(bin_triangles_kernel<true>, blocks, dim3(256), 0, st, g, tg.mesh.verts, n_vertices, d_faces, n_triangles);
         SOBFU_HIP_TRY(hipGetLastError());
     }
     return (int) hipMemsetD32Async((hipDeviceptr_t) (g.hdr + kHdrBuilt), 1, 1, st);
@@ -231,21 +222,19 @@ int sobfu_hip_mesh_grid_build(const float* d_vertices, int n_vertices, const int
 int sobfu_hip_mesh_distance(void* d_workspace, size_t workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles,
                             const float origin[3], float h, const int dims[3], const float* d_points, int n, float max_dist, int mode,
                             int ring_cap, float* d_dist, int* d_tri, float* d_closest, int* d_unresolved, void* stream) {
-    SOBFU_CHECK_ARGS(grid_args_ok(d_workspace, workspace_bytes, origin, h, dims, 0) && mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    MeshTarget tg;
+    SOBFU_CHECK_ARGS(mesh_target(d_workspace, workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
     SOBFU_CHECK_ARGS(d_points && d_dist && d_tri && n >= 0 && aligned(d_points, 0, 16) && aligned(d_dist, 0, 4) && aligned(d_tri, 0, 4) &&
                      aligned(d_closest, 0, 16) && aligned(d_unresolved, 0, 4));
-    SOBFU_CHECK_ARGS(!std::isnan(max_dist) && mode >= SOBFU_MESH_DISTANCE_AUTO && mode <= SOBFU_MESH_DISTANCE_BRUTE && ring_cap >= 0 &&
-                     (mode == SOBFU_MESH_DISTANCE_BRUTE || d_unresolved));
+    SOBFU_CHECK_ARGS(!std::isnan(max_dist) && mode_ok(mode) && ring_cap >= 0 && (mode == SOBFU_MESH_DISTANCE_BRUTE || d_unresolved));
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t) stream;
-    const Grid g   = grid_of(d_workspace, origin, h, dims, 0);
-    const float box_l = grid_box_l(origin, h, dims);
-    const Query q{(const float4*) d_vertices, d_faces, n_triangles, (const float4*) d_points, n,
-                  max_dist > 0.f ? max_dist : INFINITY, box_l, ring_cap > 0 ? ring_cap : kMeshGridRingCap, d_dist, d_tri, (float4*) d_closest,
-                  d_unresolved};
+    const Grid& g  = tg.grid;
+    const Query q{tg.mesh, (const float4*) d_points, n, max_dist > 0.f ? max_dist : INFINITY, tg.box_l, ring_cap > 0 ? ring_cap : kMeshGridRingCap,
+                  d_dist, d_tri, (float4*) d_closest, d_unresolved};
     const dim3 blocks((unsigned) (((long long) n + 255) / 256));
     SOBFU_HIP_TRY(hipMemsetAsync(g.hdr + kHdrUnresolved, 0, sizeof(int), st));
-    if (mode == SOBFU_MESH_DISTANCE_BRUTE || (mode == SOBFU_MESH_DISTANCE_AUTO && n_triangles <= kMeshGridTinyMesh)) {
+    if (is_brute(mode, n_triangles)) {
         hipLaunchKernelGGL(brute_force_kernel<false>, blocks, dim3(256), 0, st, (const int*) g.hdr, q);
         return (int) hipGetLastError();
     }

@@ -1,7 +1,8 @@
 // Rays against an indexed triangle mesh on gfx950: for every ray the nearest triangle it meets, and a pinhole camera that turns a mesh
 // into depth, points, normals, colour and triangle-index images.  The reference has no such step; the rules are this
 // project's, and tests/mesh_ray_reference.py restates them (the ray-triangle rule operation by operation: sobfu_mesh_ray.hpp).  The
-// kernels only read the grid that sobfu_hip_mesh_grid_build made for the distance query (sobfu_mesh_grid_ws.hpp).
+// kernels only read the grid that sobfu_hip_mesh_grid_build made for the distance query; the grid's view, the mesh record, the corner and
+// staging loads, the mode and the check of the leading arguments are the mesh side's shared ones (sobfu_mesh.hpp).
 //
 //   answer   per ray: min over all triangles of t (ray_triangle, t_min < t <= t_max), the LOWEST triangle index attaining it, that
 //            triangle's barycentrics and side.  A miss: (+Inf, -1, (0, 0), 0).  The answer does not depend on the path that finds it: grid
@@ -32,7 +33,7 @@
 //            a miss is 0 everywhere and tri = -1.
 #include "sobfu_hip.h"
 #include "sobfu_frame.hpp"
-#include "sobfu_mesh_grid_ws.hpp"
+#include "sobfu_mesh.hpp"
 #include "sobfu_mesh_ray.hpp"
 
 using namespace sobfu_hip;
@@ -40,12 +41,6 @@ using namespace sobfu_hip;
 namespace {
 
 constexpr float kRayMargin = 1e-4f;
-
-struct Mesh {
-    const float4* verts;
-    const int* faces;
-    int n_triangles;
-};
 
 struct Best {
     float t;
@@ -62,8 +57,8 @@ SOBFU_DEV void visit_cell(const Grid& g, const Mesh& m, const Ray& r, float t_mi
     const int end = g.start[cell + 1];
     for (int k = g.start[cell]; k < end; ++k) {
         const int t = g.refs[k];
-        const int f0 = m.faces[3 * (size_t) t], f1 = m.faces[3 * (size_t) t + 1], f2 = m.faces[3 * (size_t) t + 2];
-        const RayHit h = ray_triangle(r, p3(m.verts[f0]), p3(m.verts[f1]), p3(m.verts[f2]), t_min, t_max);
+        const Corners v = corners_of(m, t);
+        const RayHit h  = ray_triangle(r, p3(v.a), p3(v.b), p3(v.c), t_min, t_max);
         if (h.t < best.t || (h.t == best.t && t < best.tri)) best = Best{h.t, t, h.u, h.v, h.side};
     }
 }
@@ -152,12 +147,7 @@ __global__ void __launch_bounds__(256) ray_brute_kernel(const int* __restrict__ 
     Best best = no_hit();
     for (int t0 = 0; built && t0 < a.mesh.n_triangles; t0 += 256) {
         __syncthreads();  // the previous chunk has been read
-        const int t = t0 + (int) threadIdx.x;
-        if (t < a.mesh.n_triangles) {
-            sa[threadIdx.x] = a.mesh.verts[a.mesh.faces[3 * (size_t) t]];
-            sb[threadIdx.x] = a.mesh.verts[a.mesh.faces[3 * (size_t) t + 1]];
-            sc[threadIdx.x] = a.mesh.verts[a.mesh.faces[3 * (size_t) t + 2]];
-        }
+        stage_triangles(a.mesh, t0, sa, sb, sc);
         __syncthreads();
         const int m = min(256, a.mesh.n_triangles - t0);
         for (int k = 0; r.valid && k < m; ++k) {
@@ -210,19 +200,19 @@ __global__ void __launch_bounds__(256) mesh_render_kernel(Grid g, RenderArgs a) 
     if (a.tri) row_ptr(a.tri, a.tri_step, v)[u] = best.tri;
     if (a.points) row_ptr(a.points, a.points_step, v)[u] = hit ? make_float4(z * dx, z * dy, z, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     if (!a.normals && !a.colour) return;
-    int f0 = 0, f1 = 0, f2 = 0;
-    if (hit) f0 = a.mesh.faces[3 * (size_t) best.tri], f1 = a.mesh.faces[3 * (size_t) best.tri + 1], f2 = a.mesh.faces[3 * (size_t) best.tri + 2];
+    int3 f = make_int3(0, 0, 0);
+    if (hit) f = face_of(a.mesh, best.tri);
     const float bu = best.u, bv = best.v, bw = (1.f - bu) - bv;
     if (a.normals) {
         float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
         if (hit) {
             float nx, ny, nz;
             if (a.vertex_normals) {
-                const float4 na = a.vertex_normals[f0], nb = a.vertex_normals[f1], nc = a.vertex_normals[f2];
+                const float4 na = a.vertex_normals[f.x], nb = a.vertex_normals[f.y], nc = a.vertex_normals[f.z];
                 nx = mix3(bw, bu, bv, na.x, nb.x, nc.x), ny = mix3(bw, bu, bv, na.y, nb.y, nc.y), nz = mix3(bw, bu, bv, na.z, nb.z, nc.z);
             } else {
-                const P3 pa = p3(a.mesh.verts[f0]);
-                const P3 e1 = md_sub(p3(a.mesh.verts[f1]), pa), e2 = md_sub(p3(a.mesh.verts[f2]), pa);
+                const Corners t = corners_of(a.mesh, f);
+                const P3 pa = p3(t.a), e1 = md_sub(p3(t.b), pa), e2 = md_sub(p3(t.c), pa);
                 nx = e1.y * e2.z - e1.z * e2.y, ny = e1.z * e2.x - e1.x * e2.z, nz = e1.x * e2.y - e1.y * e2.x;
             }
             if ((nx * d.x + ny * d.y) + nz * d.z > 0.f) nx = -nx, ny = -ny, nz = -nz;
@@ -236,7 +226,7 @@ __global__ void __launch_bounds__(256) mesh_render_kernel(Grid g, RenderArgs a) 
     if (a.colour) {
         uchar4 out = make_uchar4(0, 0, 0, 0);
         if (hit) {
-            const uchar4 ca = a.vertex_colours[f0], cb = a.vertex_colours[f1], cc = a.vertex_colours[f2];
+            const uchar4 ca = a.vertex_colours[f.x], cb = a.vertex_colours[f.y], cc = a.vertex_colours[f.z];
             out = make_uchar4(to_byte(mix3(bw, bu, bv, (float) ca.x, (float) cb.x, (float) cc.x)),
                               to_byte(mix3(bw, bu, bv, (float) ca.y, (float) cb.y, (float) cc.y)),
                               to_byte(mix3(bw, bu, bv, (float) ca.z, (float) cb.z, (float) cc.z)), 255);
@@ -256,20 +246,18 @@ extern "C" {
 int sobfu_hip_mesh_raycast(void* d_workspace, size_t workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles,
                            const float origin[3], float h, const int dims[3], const float* d_origins, const float* d_dirs, int n, float t_min,
                            float t_max, int mode, float* d_t, int* d_tri, float* d_bary, int8_t* d_side, void* stream) {
-    SOBFU_CHECK_ARGS(grid_args_ok(d_workspace, workspace_bytes, origin, h, dims, 0) && mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    MeshTarget tg;
+    SOBFU_CHECK_ARGS(mesh_target(d_workspace, workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
     SOBFU_CHECK_ARGS(d_origins && d_dirs && d_t && d_tri && n >= 0 && aligned(d_origins, 0, 16) && aligned(d_dirs, 0, 16) && aligned(d_t, 0, 4) &&
                      aligned(d_tri, 0, 4) && aligned(d_bary, 0, 8));
-    SOBFU_CHECK_ARGS(std::isfinite(t_min) && !std::isnan(t_max) && mode >= SOBFU_MESH_DISTANCE_AUTO && mode <= SOBFU_MESH_DISTANCE_BRUTE);
+    SOBFU_CHECK_ARGS(std::isfinite(t_min) && !std::isnan(t_max) && mode_ok(mode));
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t) stream;
-    const Grid g   = grid_of(d_workspace, origin, h, dims, 0);
-    const RayArgs a{{(const float4*) d_vertices, d_faces, n_triangles}, (const float4*) d_origins, (const float4*) d_dirs, n, t_min, unlimited(t_max),
-                    grid_box_l(origin, h, dims), d_t, d_tri, (float2*) d_bary, (signed char*) d_side};
+    const RayArgs a{tg.mesh, (const float4*) d_origins, (const float4*) d_dirs, n, t_min, unlimited(t_max), tg.box_l, d_t, d_tri, (float2*) d_bary,
+                    (signed char*) d_side};
     const dim3 blocks((unsigned) (((long long) n + 255) / 256));
-    if (mode == SOBFU_MESH_DISTANCE_BRUTE || (mode == SOBFU_MESH_DISTANCE_AUTO && n_triangles <= kMeshGridTinyMesh))
-        hipLaunchKernelGGL(ray_brute_kernel, blocks, dim3(256), 0, st, (const int*) g.hdr, a);
-    else
-        hipLaunchKernelGGL(ray_grid_kernel, blocks, dim3(256), 0, st, g, a);
+    if (is_brute(mode, n_triangles)) hipLaunchKernelGGL(ray_brute_kernel, blocks, dim3(256), 0, st, (const int*) tg.grid.hdr, a);
+    else hipLaunchKernelGGL(ray_grid_kernel, blocks, dim3(256), 0, st, tg.grid, a);
     return (int) hipGetLastError();
 }
 
@@ -278,7 +266,8 @@ int sobfu_hip_mesh_render(void* d_workspace, size_t workspace_bytes, const float
                           const float R[9], const float t[3], float fx, float fy, float cx, float cy, int rows, int cols, float z_min, float z_max,
                           uint16_t* d_depth, int depth_step, float* d_points, int points_step, float* d_normals, int normals_step, uint8_t* d_colour,
                           int colour_step, int32_t* d_tri, int tri_step, void* stream) {
-    SOBFU_CHECK_ARGS(grid_args_ok(d_workspace, workspace_bytes, origin, h, dims, 0) && mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    MeshTarget tg;
+    SOBFU_CHECK_ARGS(mesh_target(d_workspace, workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
     SOBFU_CHECK_ARGS(R && t && finite_all(R, 9) && finite_all(t, 3) && intr_ok(fx, fy, cx, cy) && rows >= 1 && cols >= 1);
     SOBFU_CHECK_ARGS(std::isfinite(z_min) && !std::isnan(z_max) && aligned(d_vertex_normals, 0, 16) && aligned(d_vertex_colours, 0, 4));
     SOBFU_CHECK_ARGS(image_ok(d_depth, depth_step, cols, 2, 2) && image_ok(d_points, points_step, cols, 16, 16) &&
@@ -286,17 +275,16 @@ int sobfu_hip_mesh_render(void* d_workspace, size_t workspace_bytes, const float
                      image_ok(d_tri, tri_step, cols, 4, 4));
     SOBFU_CHECK_ARGS(!d_colour || d_vertex_colours);
     if (!d_depth && !d_points && !d_normals && !d_colour && !d_tri) return 0;
-    RenderArgs a{{(const float4*) d_vertices, d_faces, n_triangles}, (const float4*) d_vertex_normals, (const uchar4*) d_vertex_colours, {}, {},
-                 fx, fy, cx, cy, rows, cols, z_min, unlimited(z_max), grid_box_l(origin, h, dims), d_depth, depth_step, (float4*) d_points,
-                 points_step, (float4*) d_normals, normals_step, (uchar4*) d_colour, colour_step, d_tri, tri_step};
+    RenderArgs a{tg.mesh, (const float4*) d_vertex_normals, (const uchar4*) d_vertex_colours, {}, {}, fx, fy, cx, cy, rows, cols, z_min, unlimited(z_max),
+                 tg.box_l, d_depth, depth_step, (float4*) d_points, points_step, (float4*) d_normals, normals_step, (uchar4*) d_colour, colour_step, d_tri,
+                 tri_step};
     fill_pose(R, t, a.R, nullptr, nullptr);
     for (int i = 0; i < 3; ++i) {
         double o = 0.0;
         for (int j = 0; j < 3; ++j) o -= (double) R[3 * j + i] * (double) t[j];
         a.o[i] = (float) o;
     }
-    const Grid g = grid_of(d_workspace, origin, h, dims, 0);
-    hipLaunchKernelGGL(mesh_render_kernel, dim3((unsigned) ((cols + 15) / 16), (unsigned) ((rows + 15) / 16)), dim3(256), 0, (hipStream_t) stream, g, a);
+    hipLaunchKernelGGL(mesh_render_kernel, dim3((unsigned) ((cols + 15) / 16), (unsigned) ((rows + 15) / 16)), dim3(256), 0, (hipStream_t) stream, tg.grid, a);
     return (int) hipGetLastError();
 }
 

@@ -1,13 +1,14 @@
 // Closed triangle meshes into signed TSDF volumes on gfx950, and the inside / outside test behind them.  The reference
 // has no such step; the rules are this project's, and tests/mesh_parity_reference.py restates them (the row-crossing rule operation by
 // operation: sobfu_mesh_parity.hpp; the distance: sobfu_mesh_distance.hpp).  The kernels only read the grid that
-// sobfu_hip_mesh_grid_build made for the distance query (sobfu_mesh_grid_ws.hpp).  Vertices are in the volume's frame.
+// sobfu_hip_mesh_grid_build made for the distance query; the grid's view, the mesh record, the corner loads, the cell range the rows and
+// points ask for, the margin, the mode and the check of the leading arguments are shared (sobfu_mesh.hpp).  Vertices are in the volume's frame.
 //
 //   centres  voxel i of an axis has its centre at i vs + vs / 2, in fp32
 //   sign     a row is the line through (., py, pz) along +x.  A crossing triangle's box contains (py, pz) -- the fp32 translation of the
 //            rule keeps signs -- so it is referenced from the row's one cell column (cell_of(py), cell_of(pz)), whose cells cx = 0 ..
 //            dx - 1 hold one contiguous range of references.  A triangle referenced from several cells of the column counts only in
-//            cell_of(min(a.x, b.x, c.x)), the expression bin_triangles_kernel uses.  The crossing rule is exact, so the count depends
+//            the first cell in x of its cell range (cells_of, which the build bins by).  The crossing rule is exact, so the count depends
 //            neither on the cells, nor on the order of the references, nor on grid versus brute force (every triangle once).
 //   rows     one wave per volume row (j, k), up to X = 512: lanes stride over the column's references; each crossing flips, in an LDS mask,
 //            the bit of the first voxel whose centre is not below X (bit X: beyond the last voxel).  XOR is order-independent.  Voxel i
@@ -30,24 +31,17 @@
 //            not read.
 #include "sobfu_hip.h"
 #include "sobfu_device.hpp"
-#include "sobfu_mesh_grid_ws.hpp"
+#include "sobfu_mesh.hpp"
 #include "sobfu_mesh_parity.hpp"
 
 using namespace sobfu_hip;
 
 namespace {
 
-constexpr float kMeshMargin = 1e-4f;
 constexpr int kMaxX      = 512;
 constexpr int kMaskWords = kMaxX / 32 + 1;  // bit X of a row: crossings beyond the last voxel
 constexpr int kBrick     = 8;
 constexpr int kStage     = 1024;  // triangles staged in LDS at a time (48 B each)
-
-struct Mesh {
-    const float4* verts;
-    const int* faces;
-    int n_triangles;
-};
 
 struct VoxArgs {
     Mesh mesh;
@@ -72,12 +66,7 @@ SOBFU_DEV int first_not_below(double X, float vs, int n) {
     return i;
 }
 
-SOBFU_DEV Crossing cross_triangle(const Mesh& m, int t, float py, float pz, float& min_x) {
-    const int f0 = m.faces[3 * (size_t) t], f1 = m.faces[3 * (size_t) t + 1], f2 = m.faces[3 * (size_t) t + 2];
-    const P3 a = p3(m.verts[f0]), b = p3(m.verts[f1]), c = p3(m.verts[f2]);
-    min_x = fminf(fminf(a.x, b.x), c.x);
-    return row_crossing(a, b, c, py, pz);
-}
+SOBFU_DEV Crossing cross_triangle(const Corners& t, float py, float pz) { return row_crossing(p3(t.a), p3(t.b), p3(t.c), py, pz); }
 
 // the cell c in [c0, c1] of a row of cells (start: that row's entries) whose references hold position k: the largest c with start[c] <= k
 SOBFU_DEV int cell_of_reference(const int* __restrict__ start, int c0, int c1, int k) {
@@ -101,8 +90,7 @@ __global__ void __launch_bounds__(256) row_parity_kernel(Grid g, VoxArgs a) {
         const float py = centre((int) (row % a.d.y), a.vsy), pz = centre((int) (row / a.d.y), a.vsz);
         if (a.brute) {
             for (int t = lane; t < a.mesh.n_triangles; t += 64) {
-                float min_x;
-                const Crossing c = cross_triangle(a.mesh, t, py, pz, min_x);
+                const Crossing c = cross_triangle(corners_of(a.mesh, t), py, pz);
                 if (c.hit) {
                     const int i = first_not_below(c.X, a.vsx, a.d.x);
                     atomicXor(&mask[wave][i >> 5], 1u << (i & 31));
@@ -112,9 +100,9 @@ __global__ void __launch_bounds__(256) row_parity_kernel(Grid g, VoxArgs a) {
             const int* start = g.start + g.dx * (cell_of(py, g.oy, g.h, g.dy) + g.dy * cell_of(pz, g.oz, g.h, g.dz));
             const int k1 = start[g.dx];
             for (int k = start[0] + lane; k < k1; k += 64) {
-                float min_x;
-                const Crossing c = cross_triangle(a.mesh, g.refs[k], py, pz, min_x);
-                if (c.hit && cell_of(min_x, g.ox, g.h, g.dx) == cell_of_reference(start, 0, g.dx - 1, k)) {
+                const Corners t  = corners_of(a.mesh, g.refs[k]);
+                const Crossing c = cross_triangle(t, py, pz);
+                if (c.hit && cells_of(g, t).x0 == cell_of_reference(start, 0, g.dx - 1, k)) {
                     const int i = first_not_below(c.X, a.vsx, a.d.x);
                     atomicXor(&mask[wave][i >> 5], 1u << (i & 31));
                 }
@@ -156,18 +144,18 @@ __global__ void __launch_bounds__(256) mesh_inside_kernel(Grid g, InsideArgs a) 
     if (g.hdr[kHdrBuilt] == 1) {
         const float4 p  = a.points[i];
         const double px = (double) p.x;
-        float min_x;
         if (a.brute) {
             for (int t = 0; t < a.mesh.n_triangles; ++t) {
-                const Crossing c = cross_triangle(a.mesh, t, p.y, p.z, min_x);
+                const Crossing c = cross_triangle(corners_of(a.mesh, t), p.y, p.z);
                 if (c.hit) ++total, beyond += c.X > px ? 1u : 0u;
             }
         } else {
             const int* start = g.start + g.dx * (cell_of(p.y, g.oy, g.h, g.dy) + g.dy * cell_of(p.z, g.oz, g.h, g.dz));
             for (int cx = 0; cx < g.dx; ++cx)
                 for (int k = start[cx]; k < start[cx + 1]; ++k) {
-                    const Crossing c = cross_triangle(a.mesh, g.refs[k], p.y, p.z, min_x);
-                    if (c.hit && cell_of(min_x, g.ox, g.h, g.dx) == cx) ++total, beyond += c.X > px ? 1u : 0u;
+                    const Corners t  = corners_of(a.mesh, g.refs[k]);
+                    const Crossing c = cross_triangle(t, p.y, p.z);
+                    if (c.hit && cells_of(g, t).x0 == cx) ++total, beyond += c.X > px ? 1u : 0u;
                 }
         }
     }
@@ -186,16 +174,16 @@ __global__ void __launch_bounds__(512) brick_kernel(Grid g, VoxArgs a) {
     auto test = [&](int count) {
         for (int k = 0; k < count; ++k) best = fminf(best, closest_on_triangle(p, p3(sa[k]), p3(sb[k]), p3(sc[k])).d2);
     };
-    auto stage = [&](int slot, int t) {
-        sa[slot] = m.verts[m.faces[3 * (size_t) t]], sb[slot] = m.verts[m.faces[3 * (size_t) t + 1]], sc[slot] = m.verts[m.faces[3 * (size_t) t + 2]];
-    };
     if (tid == 0) s_count = 0;
     __syncthreads();
     if (g.hdr[kHdrBuilt] == 1 && m.n_triangles > 0) {  // uniform over the workgroup, like every loop bound below
         if (a.brute) {
             for (int t0 = 0; t0 < m.n_triangles; t0 += kStage) {
                 __syncthreads();  // the previous chunk has been read
-                for (int s = tid; s < kStage && t0 + s < m.n_triangles; s += 512) stage(s, t0 + s);
+                for (int s = tid; s < kStage && t0 + s < m.n_triangles; s += 512) {
+                    const Corners v = corners_of(m, t0 + s);
+                    sa[s] = v.a, sb[s] = v.b, sc[s] = v.c;
+                }
                 __syncthreads();
                 test(min(kStage, m.n_triangles - t0));
             }
@@ -238,8 +226,9 @@ __global__ void __launch_bounds__(512) brick_kernel(Grid g, VoxArgs a) {
                                 examined += min(512, k1 - kb);
                                 const int k = kb + tid;
                                 if (k < k1) {
-                                    const int t = g.refs[k];
-                                    const float4 va = m.verts[m.faces[3 * (size_t) t]], vb = m.verts[m.faces[3 * (size_t) t + 1]], vc = m.verts[m.faces[3 * (size_t) t + 2]];
+                                    const auto [va, vb, vc] = corners_of(m, g.refs[k]);
+                                    // the cell range, written out as cells_of (sobfu_mesh.hpp) has it: through cells_of, and with another form
+                                    // of the staging loop above, this kernel measured 0.8 % and 4.4 % slower (profiles/mesh_side_home.md)
                                     const int tx0 = cell_of(fminf(fminf(va.x, vb.x), vc.x), g.ox, g.h, g.dx), tx1 = cell_of(fmaxf(fmaxf(va.x, vb.x), vc.x), g.ox, g.h, g.dx);
                                     const int ty0 = cell_of(fminf(fminf(va.y, vb.y), vc.y), g.oy, g.h, g.dy), ty1 = cell_of(fmaxf(fmaxf(va.y, vb.y), vc.y), g.oy, g.h, g.dy);
                                     const int tz0 = cell_of(fminf(fminf(va.z, vb.z), vc.z), g.oz, g.h, g.dz), tz1 = cell_of(fmaxf(fmaxf(va.z, vb.z), vc.z), g.oz, g.h, g.dz);
@@ -283,10 +272,6 @@ __global__ void __launch_bounds__(512) brick_kernel(Grid g, VoxArgs a) {
 
 int words_per_row(int X) { return (X + 31) / 32; }
 size_t bits_bytes(int X, int Y, int Z) { return ((size_t) Y * Z * words_per_row(X) * sizeof(unsigned) + 15) / 16 * 16; }
-bool mode_ok(int mode) { return mode >= SOBFU_MESH_DISTANCE_AUTO && mode <= SOBFU_MESH_DISTANCE_BRUTE; }
-int is_brute(int mode, int n_triangles) {
-    return mode == SOBFU_MESH_DISTANCE_BRUTE || (mode == SOBFU_MESH_DISTANCE_AUTO && n_triangles <= kMeshGridTinyMesh);
-}
 
 }  // namespace
 
@@ -301,15 +286,16 @@ int sobfu_hip_mesh_voxelise(void* d_grid_workspace, size_t grid_workspace_bytes,
                             int n_triangles, const float origin[3], float h, const int dims[3], float* d_vol, int X, int Y, int Z,
                             const float voxel_size[3], float trunc, float eta, int mode, void* d_workspace, size_t workspace_bytes,
                             int* d_open_rows, void* stream) {
-    SOBFU_CHECK_ARGS(grid_args_ok(d_grid_workspace, grid_workspace_bytes, origin, h, dims, 0) && mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    MeshTarget tg;
+    SOBFU_CHECK_ARGS(mesh_target(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
     SOBFU_CHECK_ARGS(d_vol && aligned(d_vol, 0, 8) && volume_ok(X, Y, Z, kGridZ * kBrick) && X <= kMaxX && (long long) Y * Z <= INT_MAX);
     SOBFU_CHECK_ARGS(voxel_size && positive_finite(voxel_size[0]) && positive_finite(voxel_size[1]) && positive_finite(voxel_size[2]) &&
                      positive_finite(trunc) && std::isfinite(eta) && mode_ok(mode));
     SOBFU_CHECK_ARGS(d_workspace && aligned(d_workspace, 0, 16) && workspace_bytes >= bits_bytes(X, Y, Z) && d_open_rows && aligned(d_open_rows, 0, 4));
     hipStream_t st = (hipStream_t) stream;
-    const Grid g   = grid_of(d_grid_workspace, origin, h, dims, 0);
-    const VoxArgs a{{(const float4*) d_vertices, d_faces, n_triangles}, is_brute(mode, n_triangles), {X, Y, Z}, voxel_size[0], voxel_size[1], voxel_size[2],
-                    trunc, eta, grid_box_l(origin, h, dims), (float2*) d_vol, (unsigned*) d_workspace, words_per_row(X), d_open_rows};
+    const Grid& g  = tg.grid;
+    const VoxArgs a{tg.mesh, is_brute(mode, n_triangles), {X, Y, Z}, voxel_size[0], voxel_size[1], voxel_size[2], trunc, eta, tg.box_l, (float2*) d_vol,
+                    (unsigned*) d_workspace, words_per_row(X), d_open_rows};
     SOBFU_HIP_TRY(hipMemsetAsync(d_open_rows, 0, sizeof(int), st));
     hipLaunchKernelGGL(row_parity_kernel, dim3((unsigned) (((long long) Y * Z + 3) / 4)), dim3(256), 0, st, g, a);
     SOBFU_HIP_TRY(hipGetLastError());
@@ -321,12 +307,12 @@ int sobfu_hip_mesh_voxelise(void* d_grid_workspace, size_t grid_workspace_bytes,
 int sobfu_hip_mesh_inside(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
                           int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, uint8_t* d_inside,
                           uint8_t* d_open, int mode, void* stream) {
-    SOBFU_CHECK_ARGS(grid_args_ok(d_grid_workspace, grid_workspace_bytes, origin, h, dims, 0) && mesh_args_ok(d_vertices, n_vertices, d_faces, n_triangles));
+    MeshTarget tg;
+    SOBFU_CHECK_ARGS(mesh_target(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
     SOBFU_CHECK_ARGS(d_points && d_inside && d_open && n >= 0 && aligned(d_points, 0, 16) && mode_ok(mode));
     if (n == 0) return 0;
-    const Grid g = grid_of(d_grid_workspace, origin, h, dims, 0);
-    const InsideArgs a{{(const float4*) d_vertices, d_faces, n_triangles}, is_brute(mode, n_triangles), (const float4*) d_points, n, d_inside, d_open};
-    hipLaunchKernelGGL(mesh_inside_kernel, dim3((unsigned) (((long long) n + 255) / 256)), dim3(256), 0, (hipStream_t) stream, g, a);
+    const InsideArgs a{tg.mesh, is_brute(mode, n_triangles), (const float4*) d_points, n, d_inside, d_open};
+    hipLaunchKernelGGL(mesh_inside_kernel, dim3((unsigned) (((long long) n + 255) / 256)), dim3(256), 0, (hipStream_t) stream, tg.grid, a);
     return (int) hipGetLastError();
 }
 

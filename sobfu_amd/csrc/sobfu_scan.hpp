@@ -4,11 +4,10 @@
 #pragma once
 
 #include "sobfu_device.hpp"
+#include "sobfu_scan_layout.hpp"  // kBlock, kItems, kChunk
 
 namespace sobfu_hip {
 namespace {
-
-constexpr int kBlock = 256, kItems = 8, kChunk = kBlock * kItems;  // cells per workgroup
 
 // block-wide exclusive prefix of one int per lane; returns the prefix, *total = block sum (valid in every lane)
 SOBFU_DEV int block_exclusive(int v, int* total, int* s_wave /* kBlock / 64 + 1 */) {

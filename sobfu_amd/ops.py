@@ -684,21 +684,28 @@ class TriangleGrid:
         return (_ptr(self.vertices) if self.n_vertices else None, C.c_int(self.n_vertices),
                 _ptr(self.faces, torch.int32) if self.n_triangles else None, C.c_int(self.n_triangles))
 
+    def _target(self):  # the nine arguments every mesh entry point of the C ABI starts with: the grid's workspace, the mesh, the plan
+        return (*_ws(self.workspace), *self._mesh(), *self._plan)
+
+    @staticmethod
+    def _mode(mode):
+        if mode not in _MESH_MODES:
+            raise ValueError(f"unknown mode {mode!r}")
+        return C.c_int(_MESH_MODES[mode])
+
     def query(self, points, max_dist=None, closest=False, mode="auto", ring_cap=None):
         """(n, 4) float32 points -> dist (n,) float32, tri (n,) int32 [, closest (n, 4) float32]: the distance to the nearest triangle, the
         lowest triangle index at that distance and its closest point (x, y, z, 1).  max_dist: farther points get (+Inf, -1, zeros).
         mode "auto" | "grid" | "brute" and ring_cap (shells walked before a point goes to brute force) never change the answer."""
-        if mode not in _MESH_MODES:
-            raise ValueError(f"unknown mode {mode!r}")
+        mode = self._mode(mode)
         n = int(points.shape[0])
         dist = torch.empty(n, dtype=torch.float32, device=points.device)
         tri = torch.empty(n, dtype=torch.int32, device=points.device)
         cl = torch.empty((n, 4), dtype=torch.float32, device=points.device) if closest else None
         if n:
             self.unresolved_buffer = torch.empty(n, dtype=torch.int32, device=points.device)
-            check(_lib.lib().sobfu_hip_mesh_distance(*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(points, "points"), C.c_int(n),
-                                                     _f(0.0 if max_dist is None else max_dist), C.c_int(_MESH_MODES[mode]), C.c_int(int(ring_cap or 0)),
-                                                     _ptr(dist), _ptr(tri, torch.int32), None if cl is None else _ptr(cl),
+            check(_lib.lib().sobfu_hip_mesh_distance(*self._target(), _point_list(points, "points"), C.c_int(n), _f(0.0 if max_dist is None else max_dist),
+                                                     mode, C.c_int(int(ring_cap or 0)), _ptr(dist), _ptr(tri, torch.int32), None if cl is None else _ptr(cl),
                                                      _ptr(self.unresolved_buffer, torch.int32), _stream()), "mesh_distance")
         return (dist, tri, cl) if closest else (dist, tri)
 
@@ -707,10 +714,9 @@ class TriangleGrid:
         return torch.empty(int(_lib.lib().sobfu_hip_mesh_align_workspace_bytes(C.c_int(n))), dtype=torch.uint8, device=device)
 
     def _align_target(self, points, n, max_dist, mode, ring_cap):
-        if mode not in _MESH_MODES:
-            raise ValueError(f"unknown mode {mode!r}")
-        return (*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(points, "points") if n else None, C.c_int(n),
-                _f(0.0 if max_dist is None else max_dist), C.c_int(_MESH_MODES[mode]), C.c_int(int(ring_cap or 0)))
+        mode = self._mode(mode)
+        return (*self._target(), _point_list(points, "points") if n else None, C.c_int(n), _f(0.0 if max_dist is None else max_dist), mode,
+                C.c_int(int(ring_cap or 0)))
 
     def align_step(self, points, pose, max_dist=None, mode="auto", ring_cap=None):
         """One transform + nearest-triangle query + reduction of the (n, 4) float32 points at the 4 x 4 `pose` (points -> this mesh's
@@ -760,8 +766,7 @@ class TriangleGrid:
         that parameter, the weights of its second and third corner, and +1 / -1 for the face whose corners run counter-clockwise /
         clockwise as seen from the origin.  A miss is (+Inf, -1, (0, 0), 0).  t_max None: unlimited.  mode "auto" | "grid" | "brute"
         never changes the answer."""
-        if mode not in _MESH_MODES:
-            raise ValueError(f"unknown mode {mode!r}")
+        mode = self._mode(mode)
         n = int(origins.shape[0])
         if int(dirs.shape[0]) != n:
             raise ValueError("origins and dirs must hold the same number of rays")
@@ -771,10 +776,9 @@ class TriangleGrid:
         b = torch.empty((n, 2), dtype=torch.float32, device=dev) if bary else None
         s = torch.empty(n, dtype=torch.int8, device=dev) if side else None
         if n:
-            check(_lib.lib().sobfu_hip_mesh_raycast(*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(origins, "origins"),
-                                                    _point_list(dirs, "dirs"), C.c_int(n), _f(t_min), _f(0.0 if t_max is None else t_max),
-                                                    C.c_int(_MESH_MODES[mode]), _ptr(t), _ptr(tri, torch.int32), None if b is None else _ptr(b),
-                                                    None if s is None else _ptr(s, torch.int8), _stream()), "mesh_raycast")
+            check(_lib.lib().sobfu_hip_mesh_raycast(*self._target(), _point_list(origins, "origins"), _point_list(dirs, "dirs"), C.c_int(n), _f(t_min),
+                                                    _f(0.0 if t_max is None else t_max), mode, _ptr(t), _ptr(tri, torch.int32),
+                                                    None if b is None else _ptr(b), None if s is None else _ptr(s, torch.int8), _stream()), "mesh_raycast")
         return tuple(x for x in (t, tri, b, s) if x is not None)
 
     def render(self, intr, rows, cols, pose=None, z_min=0.0, z_max=None, vertex_normals=None, vertex_colours=None, outputs=("depth",)):
@@ -821,9 +825,8 @@ class TriangleGrid:
         for v in (vertex_normals, vertex_colours):
             if v is not None and int(v.shape[0]) != self.n_vertices:
                 raise ValueError("one normal / colour per vertex")
-        check(_lib.lib().sobfu_hip_mesh_render(*_ws(self.workspace), *self._mesh(), *self._plan, vn, vc, Rm, tv, _f(intr[0]), _f(intr[1]), _f(intr[2]),
-                                               _f(intr[3]), C.c_int(int(rows)), C.c_int(int(cols)), _f(z_min), _f(0.0 if z_max is None else z_max),
-                                               *args, _stream()), "mesh_render")
+        check(_lib.lib().sobfu_hip_mesh_render(*self._target(), vn, vc, Rm, tv, *map(_f, intr[:4]), C.c_int(int(rows)), C.c_int(int(cols)), _f(z_min),
+                                               _f(0.0 if z_max is None else z_max), *args, _stream()), "mesh_render")
         return given
 
     # ---- this mesh, closed, as a signed TSDF volume and an inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip) ----
@@ -832,8 +835,7 @@ class TriangleGrid:
         its centre at i vs + vs / 2 per axis; tsdf = clamp(s / trunc, -1, 1) with s the exact distance to the mesh, negative inside;
         weight = s > -eta -> (volume (Z, Y, X, 2) float32, open_rows (1,) int32 GPU tensor: the rows along x that cross the mesh an odd
         number of times -- 0 for a closed mesh).  out: a volume to write into.  mode never changes a bit.  X <= 512."""
-        if mode not in _MESH_MODES:
-            raise ValueError(f"unknown mode {mode!r}")
+        mode = self._mode(mode)
         X, Y, Z = (int(d) for d in dims)
         dev = self.vertices.device
         vol = torch.empty((Z, Y, X, 2), dtype=torch.float32, device=dev) if out is None else out
@@ -844,22 +846,20 @@ class TriangleGrid:
             raise ValueError(f"cannot voxelise into {X} x {Y} x {Z} voxels (X <= 512)")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         open_rows = torch.empty(1, dtype=torch.int32, device=dev)
-        check(_lib.lib().sobfu_hip_mesh_voxelise(*_ws(self.workspace), *self._mesh(), *self._plan, _ptr(vol), C.c_int(X), C.c_int(Y), C.c_int(Z),
-                                                 _vs3(vs), _f(trunc), _f(eta), C.c_int(_MESH_MODES[mode]), *_ws(ws), _ptr(open_rows, torch.int32),
-                                                 _stream()), "mesh_voxelise")
+        check(_lib.lib().sobfu_hip_mesh_voxelise(*self._target(), _ptr(vol), C.c_int(X), C.c_int(Y), C.c_int(Z), _vs3(vs), _f(trunc), _f(eta), mode,
+                                                 *_ws(ws), _ptr(open_rows, torch.int32), _stream()), "mesh_voxelise")
         return vol, open_rows
 
     def inside(self, points, mode="auto"):
         """(n, 4) float32 points -> inside (n,) uint8 (1: the row from the point along +x crosses the mesh an odd number of times), open
         (n,) uint8 (1: the point's whole row crosses it an odd number of times: the mesh is not closed there)"""
-        if mode not in _MESH_MODES:
-            raise ValueError(f"unknown mode {mode!r}")
+        mode = self._mode(mode)
         n = int(points.shape[0])
         ins = torch.empty(n, dtype=torch.uint8, device=points.device)
         opn = torch.empty(n, dtype=torch.uint8, device=points.device)
         if n:
-            check(_lib.lib().sobfu_hip_mesh_inside(*_ws(self.workspace), *self._mesh(), *self._plan, _point_list(points, "points"), C.c_int(n),
-                                                   _ptr(ins, torch.uint8), _ptr(opn, torch.uint8), C.c_int(_MESH_MODES[mode]), _stream()), "mesh_inside")
+            check(_lib.lib().sobfu_hip_mesh_inside(*self._target(), _point_list(points, "points"), C.c_int(n), _ptr(ins, torch.uint8),
+                                                   _ptr(opn, torch.uint8), mode, _stream()), "mesh_inside")
         return ins, opn
 
     def unresolved(self):
