@@ -55,11 +55,23 @@
 // frame).  --evaluate-signed adds signed_mean, inside and open to each side of the evaluate lines: the sign of a vertex against the
 // other mesh, > 0 outside.
 //
+// A depth sensor and a moving camera for --render-mesh (opt-in; sobfu_amd/csrc/depth_sensor_kernels.hip): --sensor kinect|ideal
+// passes every rendered frame -- its points and normals -- through the depth sensor model before it goes the way a depth file's pixels go:
+// lateral jitter, axial noise, disparity quantisation, dropouts and a range gate, drawn from --sensor-seed N (default 0) and the frame
+// number, so a run repeats bit for bit.  --sensor-set name=value (repeatable, after --sensor; the names of sobfu_hip_sensor_params:
+// lateral, z_min, z_max, cos_min, edge_radius, edge_jump, edge_drop, drop, a0, a1, z0, a2, disparity) overrides one field.  --sensor ideal
+// changes nothing.  --render-trajectory FILE reads camera poses in the format --poses writes (camera -> frame 0's camera): frame n is
+// rendered from pose n of the file, that is with inverse(pose_n) applied to the mesh after --render-pose and the (x, -y, -z) flip; fewer
+// poses than frames is an error, and --voxelise-mesh, which has no camera, excludes it.  With --track as well, one line after the last
+// frame scores the tracked poses against the file: "trajectory: ate=... rpe_trans=... rpe_rot=..." (sobfu_amd/trajectory.hpp: metres,
+// metres, radians; steps of one frame).
+//
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
 //                  [--warp-mesh] [--track-mesh K] [--fit-stats]
 //                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE]
-//                   [--textured] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | frame0.pgm frame1.pgm ...)
+//                   [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE]
+//                   | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | frame0.pgm frame1.pgm ...)
 //                  [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-signed]
 #include <dirent.h>
 #include <sys/stat.h>
@@ -73,6 +85,7 @@
 
 #include <sobfu_amd/depth_io.hpp>
 #include <sobfu_amd/sobfu.hpp>
+#include <sobfu_amd/trajectory.hpp>
 
 // uint16 mm depth of a sphere, same convention as sobfu_amd/synthetic.py::render_sphere_depth (float64, rint)
 static void render_sphere(double cx, double cy, double cz, double r, const kfusion::Intr& in, int rows, int cols, std::vector<uint16_t>& out) {
@@ -206,7 +219,7 @@ static std::string frame_path(const std::string& pattern, int n) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--evaluate-signed] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--evaluate-signed] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -225,6 +238,10 @@ int main(int argc, char** argv) {
     std::string render_mesh, render_pose;  // --render-mesh: the frame source; --render-pose: applied to its meshes first
     bool voxelise = false, eval_signed = false;  // --voxelise-mesh: the meshes reach the solver as volumes, not as depth frames
     int render_frames = 1;
+    bool sensor = false;  // --sensor: rendered frames pass through sensor_model
+    sobfu_amd::SensorModel sensor_model;
+    uint64_t sensor_seed = 0;
+    std::string render_trajectory;  // --render-trajectory: frame n is rendered from pose n of this file
     int eval_align = -1, eval_align_dof = 6;  // --evaluate-align: the iterations; -1: off
     float eval_max_dist = -1.f;  // < 0: 5 x the truncation distance
     Screenshots shots;
@@ -280,6 +297,26 @@ int main(int argc, char** argv) {
         else if (a == "--evaluate-signed") eval_signed = true;
         else if (a == "--render-frames" && i + 1 < argc) render_frames = std::atoi(argv[++i]);
         else if (a == "--render-pose" && i + 1 < argc) render_pose = argv[++i];
+        else if (a == "--sensor" && i + 1 < argc) {
+            const std::string name = argv[++i];
+            if (name != "kinect" && name != "ideal") {
+                std::printf("--sensor is kinect or ideal, not %s\n", name.c_str());
+                return 2;
+            }
+            sensor = true, sensor_model = name == "kinect" ? sobfu_amd::SensorModel::kinect() : sobfu_amd::SensorModel::ideal();
+        }
+        else if (a == "--sensor-seed" && i + 1 < argc) sensor_seed = std::strtoull(argv[++i], nullptr, 0);
+        else if (a == "--sensor-set" && i + 1 < argc) {
+            const std::string kv = argv[++i];
+            const size_t eq = kv.find('=');
+            char* end = nullptr;
+            const double value = eq == std::string::npos ? 0.0 : std::strtod(kv.c_str() + eq + 1, &end);
+            if (!sensor || eq == std::string::npos || end == kv.c_str() + eq + 1 || *end != '\0' || !sensor_model.set(kv.substr(0, eq), value)) {
+                std::printf("--sensor-set %s: expected name=value after --sensor, name a field of sobfu_hip_sensor_params\n", kv.c_str());
+                return 2;
+            }
+        }
+        else if (a == "--render-trajectory" && i + 1 < argc) render_trajectory = argv[++i];
         else files.push_back(a);
     }
     if (mesh_format != "vtk" && mesh_format != "ply") {
@@ -401,6 +438,10 @@ int main(int argc, char** argv) {
         std::printf("--voxelise-mesh has no depth camera: it excludes --screenshots and --track\n");
         return 2;
     }
+    if ((sensor || !render_trajectory.empty()) && (render_mesh.empty() || voxelise)) {
+        std::printf("--sensor and --render-trajectory need --render-mesh (--voxelise-mesh has no depth camera)\n");
+        return 2;
+    }
     const bool mesh_sequence = !frame_path(render_mesh, 0).empty();
     int mesh_frames = 0;
     if (!render_mesh.empty()) {
@@ -414,6 +455,19 @@ int main(int argc, char** argv) {
             std::printf("%s %s: no frame 0 (a pattern has one %%d or %%0Nd; a static mesh takes --render-frames N >= 1)\n", voxelise ? "--voxelise-mesh" : "--render-mesh", render_mesh.c_str());
             return 2;
         }
+    }
+    sobfu_amd::Trajectory trajectory;  // --render-trajectory: the camera of every rendered frame
+    if (!render_trajectory.empty()) {
+        std::string why;
+        if (!sobfu_amd::read_tum(render_trajectory, trajectory, &why)) {
+            std::printf("--render-trajectory: %s\n", why.c_str());
+            return 2;
+        }
+        if ((int) trajectory.size() < mesh_frames) {
+            std::printf("--render-trajectory %s: %zu poses for %d frames\n", render_trajectory.c_str(), trajectory.size(), mesh_frames);
+            return 2;
+        }
+        trajectory.resize((size_t) mesh_frames);
     }
     kfusion::cuda::setDevice(0);
     kfusion::cuda::printShortCudaDeviceInfo(0);
@@ -444,6 +498,8 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> bgra;
     kfusion::cuda::Depth depth;
     kfusion::cuda::Image colour;
+    kfusion::cuda::Cloud clean_points;  // --sensor: the clean render the sensor model reads
+    kfusion::cuda::Normals clean_normals;
     double time_ms = 0.0;
     sobfu_amd::IndexedMesh tracked;  // --track-mesh: the canonical mesh cut after frame track_mesh
     for (int n = 0; n < nframes; ++n) {
@@ -460,7 +516,22 @@ int main(int argc, char** argv) {
                 sobfu_amd::TriangleGrid::Camera cam;  // the depth camera; the meshes are in its frame with y and z negated
                 cam.R[4] = cam.R[8] = -1.f;
                 cam.fx = p.intr.fx, cam.fy = p.intr.fy, cam.cx = p.intr.cx, cam.cy = p.intr.cy, cam.rows = p.rows, cam.cols = p.cols;
-                rendered.grid.render(cam, &depth, mesh_coloured ? &colour : nullptr, mesh_coloured ? &rendered.mesh.colours : nullptr);
+                if (!trajectory.empty()) {  // inverse(pose n) after the flip
+                    double R[9];
+                    sobfu_amd::trajectory_rotation(trajectory[n], R);
+                    cv::Affine3f pose, flip;
+                    for (int k = 0; k < 9; ++k) pose.R[k] = (float) R[k];
+                    for (int k = 0; k < 3; ++k) pose.t[k] = (float) trajectory[n].t[k];
+                    flip.R[4] = flip.R[8] = -1.f;
+                    const cv::Affine3f view = pose.inv() * flip;
+                    std::copy(view.R, view.R + 9, cam.R), std::copy(view.t, view.t + 3, cam.t);
+                }
+                rendered.grid.render(cam, sensor ? nullptr : &depth, mesh_coloured ? &colour : nullptr, mesh_coloured ? &rendered.mesh.colours : nullptr,
+                                     sensor ? &clean_points : nullptr, sensor ? &clean_normals : nullptr);
+                if (sensor && !sobfu_amd::depth_sensor(clean_points, clean_normals, sensor_model, sensor_seed, (uint32_t) n, depth)) {
+                    std::printf("--sensor: a parameter is outside its range (include/sobfu_hip.h, sobfu_hip_sensor_params)\n");
+                    return 2;
+                }
                 img.resize((size_t) p.rows * p.cols);
                 depth.download(img.data(), (size_t) p.cols * sizeof(uint16_t));
                 if (mesh_coloured) {
@@ -565,33 +636,16 @@ int main(int argc, char** argv) {
             }
         }
     }
-    if (!poses_path.empty()) {  // TUM trajectory format: frame tx ty tz qx qy qz qw
-        FILE* f = std::fopen(poses_path.c_str(), "w");
-        if (!f) {
-            std::printf("cannot write %s\n", poses_path.c_str());
-            return 2;
-        }
-        const std::vector<cv::Affine3f>& poses = fusion.getPoses();
-        for (size_t n = 0; n < poses.size(); ++n) {
-            const float* R = poses[n].R;
-            double q[4];  // x, y, z, w from the rotation matrix (Shepperd's branch on the largest diagonal term)
-            const double tr = (double) R[0] + R[4] + R[8];
-            if (tr > 0) {
-                const double s = std::sqrt(tr + 1.0) * 2;
-                q[3] = 0.25 * s, q[0] = (R[7] - R[5]) / s, q[1] = (R[2] - R[6]) / s, q[2] = (R[3] - R[1]) / s;
-            } else if (R[0] > R[4] && R[0] > R[8]) {
-                const double s = std::sqrt(1.0 + R[0] - R[4] - R[8]) * 2;
-                q[3] = (R[7] - R[5]) / s, q[0] = 0.25 * s, q[1] = (R[1] + R[3]) / s, q[2] = (R[2] + R[6]) / s;
-            } else if (R[4] > R[8]) {
-                const double s = std::sqrt(1.0 + R[4] - R[0] - R[8]) * 2;
-                q[3] = (R[2] - R[6]) / s, q[0] = (R[1] + R[3]) / s, q[1] = 0.25 * s, q[2] = (R[5] + R[7]) / s;
-            } else {
-                const double s = std::sqrt(1.0 + R[8] - R[0] - R[4]) * 2;
-                q[3] = (R[3] - R[1]) / s, q[0] = (R[2] + R[6]) / s, q[1] = (R[5] + R[7]) / s, q[2] = 0.25 * s;
-            }
-            std::fprintf(f, "%zu %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", n, poses[n].t[0], poses[n].t[1], poses[n].t[2], q[0], q[1], q[2], q[3]);
-        }
-        std::fclose(f);
+    sobfu_amd::Trajectory tracked_poses;  // TUM trajectory format: frame tx ty tz qx qy qz qw
+    for (size_t n = 0; n < fusion.getPoses().size(); ++n) tracked_poses.push_back(sobfu_amd::trajectory_pose((int) n, fusion.getPoses()[n].R, fusion.getPoses()[n].t));
+    if (!poses_path.empty() && !sobfu_amd::write_tum(poses_path, tracked_poses)) {
+        std::printf("cannot write %s\n", poses_path.c_str());
+        return 2;
+    }
+    if (p.track_camera && !trajectory.empty()) {  // the tracked poses against the trajectory the frames were rendered from
+        double rpe_trans = NAN, rpe_rot = NAN;
+        sobfu_amd::rpe(tracked_poses, trajectory, &rpe_trans, &rpe_rot);
+        std::printf("trajectory: ate=%.9g rpe_trans=%.9g rpe_rot=%.9g\n", sobfu_amd::ate(tracked_poses, trajectory), rpe_trans, rpe_rot);
     }
     if (!dump.empty() && fusion.psi) {  // .npy dumps (replace the reference's commented-out .vti writer, demo.cpp:252-283)
         cv::Vec3i d = p.volume_dims;

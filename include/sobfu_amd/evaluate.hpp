@@ -414,6 +414,52 @@ private:
     bool built_ = false;
 };
 
+// ---- the depth sensor model (sobfu_amd/csrc/depth_sensor_kernels.hip; ops.SensorModel / ops.depth_sensor) ---------------
+// The fields of sobfu_hip_sensor_params but seed and frame; include/sobfu_hip.h states the rule they enter.
+struct SensorModel {
+    float lateral = 0.f, z_min = 0.f, z_max = INFINITY, cos_min = 0.f;
+    int edge_radius = 0;
+    float edge_jump = 0.f, edge_drop = 0.f, drop = 0.f, a0 = 0.f, a1 = 0.f, z0 = 0.f, a2 = 0.f, disparity = 0.f;
+    // the identity: the frame is the renderer's own depth image
+    static SensorModel ideal() { return SensorModel(); }
+    // a first-generation structured-light camera (disparity: 8 sub-pixel levels x 0.075 m x 580 px)
+    static SensorModel kinect() {
+        SensorModel m;
+        m.lateral = 0.8f, m.z_min = 0.4f, m.z_max = 4.f, m.cos_min = 0.2f, m.edge_radius = 1, m.edge_jump = 0.05f, m.edge_drop = 0.5f, m.drop = 0.f;
+        m.a0 = 0.0012f, m.a1 = 0.0019f, m.z0 = 0.4f, m.a2 = 0.0001f, m.disparity = 348.f;
+        return m;
+    }
+    // a field by its name in the struct; false: no such field
+    bool set(const std::string& name, double value) {
+        float* const fields[] = {&lateral, &z_min, &z_max, &cos_min, &edge_jump, &edge_drop, &drop, &a0, &a1, &z0, &a2, &disparity};
+        const char* const names[] = {"lateral", "z_min", "z_max", "cos_min", "edge_jump", "edge_drop", "drop", "a0", "a1", "z0", "a2", "disparity"};
+        if (name == "edge_radius") return edge_radius = (int) value, true;
+        for (int i = 0; i < 12; ++i)
+            if (name == names[i]) return *fields[i] = (float) value, true;
+        return false;
+    }
+    sobfu_hip_sensor_params params(uint64_t seed, uint32_t frame) const {
+        return sobfu_hip_sensor_params{seed, frame, lateral, z_min, z_max, cos_min, edge_radius, edge_jump, edge_drop, drop, a0, a1, z0, a2, disparity};
+    }
+};
+// What the sensor `model` reports of a clean render (points and normals as TriangleGrid::render and TsdfVolume::raycast give them): depth,
+// uint16 millimetres, 0 where there is no reading; flags (optional), SOBFU_SENSOR_* per pixel.  The same (seed, frame) gives the same frame.
+// false: a parameter of the model is out of its range
+inline bool depth_sensor(const kfusion::cuda::DeviceArray2D<float4>& points, const kfusion::cuda::DeviceArray2D<float4>& normals, const SensorModel& model,
+                         uint64_t seed, uint32_t frame, kfusion::cuda::Depth& depth, kfusion::cuda::DeviceArray2D<unsigned char>* flags = nullptr) {
+    if (points.rows() != normals.rows() || points.cols() != normals.cols())
+        kfusion::cuda::error("depth_sensor: points and normals differ in size", __FILE__, __LINE__);
+    depth.create(points.rows(), points.cols());
+    if (flags) flags->create(points.rows(), points.cols());
+    const sobfu_hip_sensor_params p = model.params(seed, frame);
+    const int rc = sobfu_hip_depth_sensor((const float*) points.ptr(), (int) points.step(), (const float*) normals.ptr(), (int) normals.step(), points.rows(),
+                                          points.cols(), &p, depth.ptr(), (int) depth.step(), flags ? flags->ptr() : nullptr,
+                                          flags ? (int) flags->step() : 0, nullptr);
+    if (rc == SOBFU_E_BADARG) return false;
+    sobfuSafeCall(rc);
+    return true;
+}
+
 // ---- compare_meshes: float64 statistics over the finite distances, as sobfu_amd.evaluate.distance_stats ------------------------------
 struct DistanceStats {
     size_t n = 0, within = 0;

@@ -697,6 +697,61 @@ int sobfu_hip_mesh_inside(void* d_grid_workspace, size_t grid_workspace_bytes, c
                           int n_triangles, const float origin[3], float h, const int dims[3], const float* d_points, int n, uint8_t* d_inside,
                           uint8_t* d_open, int mode, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * depth sensor model  (no counterpart in the reference; sobfu_amd/csrc/depth_sensor_kernels.hip, sobfu_random.hpp)
+ * A clean render -- the float4 point and normal images of sobfu_hip_mesh_render or sobfu_hip_raycast -- into the uint16 millimetre frame
+ * a structured-light camera would report: lateral jitter, distance- and angle-dependent axial noise, disparity quantisation, dropouts
+ * at grazing angles, at depth edges and at random, and a range gate.  The random numbers are Philox4x32-10 draws that depend on
+ * (seed, frame, pixel, stream) alone: the same arguments give the same frame bit for bit on any machine and for any launch shape.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct sobfu_hip_sensor_params {
+    uint64_t seed;
+    uint32_t frame;
+    float lateral;        /* sigma of the pixel jitter, pixels; >= 0, finite                         */
+    float z_min, z_max;   /* depths kept: (z_min, z_max]; z_min finite, z_max = +Inf allowed         */
+    float cos_min;        /* pixels seen flatter than this are lost; in [0, 1]                       */
+    int edge_radius;      /* 0..3; 0: no edge test                                                   */
+    float edge_jump;      /* metres; >= 0                                                            */
+    float edge_drop;      /* probability in [0, 1] that a pixel at an edge is lost                   */
+    float drop;           /* probability in [0, 1] that any pixel is lost                            */
+    float a0, a1, z0, a2; /* sigma_z = (a0 + a1 (z - z0)^2) + a2 ((1 - c^2) / c^2) / sqrt(z); finite */
+    float disparity;      /* focal x baseline x sub-pixel levels, pixel metres; 0: no quantisation; >= 0, finite */
+} sobfu_hip_sensor_params;
+
+/* what became of a pixel (d_flags) */
+#define SOBFU_SENSOR_VALID 0   /* a depth was reported */
+#define SOBFU_SENSOR_MISS 1    /* the ray missed */
+#define SOBFU_SENSOR_RANGE 2   /* outside the depth range (also: no representable millimetre value, a NaN depth) */
+#define SOBFU_SENSOR_GRAZING 3 /* seen at too flat an angle */
+#define SOBFU_SENSOR_EDGE 4    /* lost at a depth edge */
+#define SOBFU_SENSOR_DROPOUT 5 /* lost at random */
+
+/* Known-answer entry of the generator: d_out[i] = philox4x32_10(counter d_counters[i], key), four words each (dense device arrays of
+ * n x 4 uint32).  SOBFU_E_BADARG: a NULL or misaligned array, a NULL key, n < 0.  n = 0 succeeds and launches nothing.  Asynchronous. */
+int sobfu_hip_philox4x32_10(const uint32_t* d_counters, const uint32_t key[2], int n, uint32_t* d_out, void* stream);
+/* Pitched images (step in bytes): d_points float4 (x, y, z, .) in the camera frame, d_normals float4 with w = 1 on a hit and all zero on
+ * a miss -> d_depth uint16 millimetres (0: no reading) and d_flags uint8 SOBFU_SENSOR_* (may be NULL).  Pixel (u, v) (column, row), all
+ * arithmetic fp32 in this order; g0, g1, g2 are the normal variates of streams 0, 1, 2 of the pixel, U0, U1 the uniform variates of
+ * words 0 and 1 of stream 3 (sobfu_random.hpp); the first condition that holds ends the pixel with depth 0 and that flag:
+ *   jitter    du = clamp(rint(g0 lateral), -4, 4), dv likewise from g1; the source pixel s = (clamp(u + du, 0, cols - 1),
+ *             clamp(v + dv, 0, rows - 1)) is the one everything below reads (nearest pixel: depths are never mixed)
+ *   miss      N(s).w == 0
+ *   range     z = P(s).z; not (z > z_min && z <= z_max) (a NaN too)
+ *   grazing   l = sqrt((x x + y y) + z z), c = |(N.x x + N.y y) + N.z z| / l; c < cos_min
+ *   edge      edge_radius r > 0 and some pixel q of the (2r + 1)^2 window around s inside the frame is a miss or has
+ *             |z_q - z| > edge_jump; and U0 < edge_drop
+ *   dropout   U1 < drop
+ *   noise     dz = z - z0, cc = c c, sigma = (a0 + a1 (dz dz)) + a2 (((1 - cc) / cc) / sqrt(z)), zn = z + g2 sigma
+ *   disparity when disparity > 0: q = rint(disparity / zn); not q >= 1: range; zn = disparity / q
+ *   depth     mm = rint(1000 zn); not (mm >= 1 && mm <= 65535): range; else the depth is mm, valid
+ * With lateral = a0 = a1 = a2 = drop = disparity = 0, edge_radius = 0, cos_min = 0, z_min = 0, z_max = +Inf the frame is
+ * sobfu_hip_mesh_render's own d_depth of the same render, bit for bit.  Every argument is checked before any device call
+ * (SOBFU_E_BADARG): NULL images or params, steps smaller than a row or misaligned, negative sizes, a parameter outside the range the
+ * struct states.  rows * cols = 0 succeeds and launches nothing.  Asynchronous. */
+int sobfu_hip_depth_sensor(const float* d_points, int points_step, const float* d_normals, int normals_step, int rows, int cols,
+                           const sobfu_hip_sensor_params* p, uint16_t* d_depth, int depth_step, uint8_t* d_flags, int flags_step,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,13 @@ class SolverReport(C.Structure):
                 ("last_max_update_index", C.c_float), ("last_e_data", C.c_float), ("last_e_reg", C.c_float)]
 
 
+class SensorParams(C.Structure):
+    """sobfu_hip_sensor_params (include/sobfu_hip.h, depth sensor model)."""
+    _fields_ = [("seed", C.c_uint64), ("frame", C.c_uint32), ("lateral", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("cos_min", C.c_float), ("edge_radius", C.c_int), ("edge_jump", C.c_float), ("edge_drop", C.c_float), ("drop", C.c_float),
+                ("a0", C.c_float), ("a1", C.c_float), ("z0", C.c_float), ("a2", C.c_float), ("disparity", C.c_float)]
+
+
 LOG_FN = C.CFUNCTYPE(None, C.c_char_p, C.c_void_p)
 
 

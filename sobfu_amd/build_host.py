@@ -18,6 +18,7 @@ SOBFU_HPP = os.path.join(INC, "sobfu_amd", "sobfu.hpp")
 DEPTH_IO_HPP = os.path.join(INC, "sobfu_amd", "depth_io.hpp")
 SOBFU_HIP_H = os.path.join(INC, "sobfu_hip.h")
 EVALUATE_HPP = os.path.join(INC, "sobfu_amd", "evaluate.hpp")  # part of sobfu.hpp
+TRAJECTORY_HPP = os.path.join(INC, "sobfu_amd", "trajectory.hpp")
 
 
 def _test_src(name: str) -> str:
@@ -43,7 +44,7 @@ def _build(out: str, src: str, deps, linked: bool, force: bool = False, flags=()
 
 def build_app(force: bool = False) -> str:
     """apps/sobfu_headless.cpp: the headless frame-loop app over the shells."""
-    return _build("sobfu_headless", os.path.join(ROOT, "apps", "sobfu_headless.cpp"), [SOBFU_HPP, EVALUATE_HPP, DEPTH_IO_HPP], True, force)
+    return _build("sobfu_headless", os.path.join(ROOT, "apps", "sobfu_headless.cpp"), [SOBFU_HPP, EVALUATE_HPP, DEPTH_IO_HPP, TRAJECTORY_HPP, SOBFU_HIP_H], True, force)
 
 
 def build_io_tool(force: bool = False) -> str:
@@ -117,8 +118,18 @@ def build_rigid_tool(force: bool = False) -> str:
                   ["-std=c++14", f"-I{CSRC}", "-ffp-contract=off"])
 
 
+def build_depth_sensor_tool(force: bool = False) -> str:
+    """tests/cpp/depth_sensor_tool.cpp: the depth sensor model through its C++ twin (sobfu_amd::SensorModel, sobfu_amd::depth_sensor)."""
+    return _build("depth_sensor_tool", _test_src("depth_sensor_tool.cpp"), [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H], True, force)
+
+
+def build_trajectory_tool(force: bool = False, flags=()) -> str:
+    """tests/cpp/trajectory_tool.cpp: CPU-only driver of include/sobfu_amd/trajectory.hpp (TUM files, ATE, RPE; no HIP)."""
+    return _build("trajectory_tool", _test_src("trajectory_tool.cpp"), [TRAJECTORY_HPP], False, force, ["-std=c++14", *flags])
+
+
 def build_host(force: bool = False) -> str:
-    for build in (build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
+    for build in (build_depth_sensor_tool, build_trajectory_tool, build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
                   build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_mesh_parity_tool, build_rigid_tool):
         build(force)
     return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H], True, force)

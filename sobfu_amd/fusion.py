@@ -204,6 +204,17 @@ class SobFusion:
             return self.ops.render_colour(pts, nrm, self.ops.sample_colour(col, P["vs"], R, t, pts, nrm), light)
         return self.ops.render_image(pts, nrm, light)
 
+    def render_model_depth(self, sensor=None, seed=0):
+        """The fused model phi_global seen from the current pose (render's camera), as a (rows, cols) int16 tensor holding the bits of
+        uint16 millimetres: ops.raycast, then ops.depth_sensor -- what the depth sensor `sensor` (an ops.SensorModel; None: the ideal one,
+        rint(1000 z) of every hit) would report of the reconstruction.  The frame number of the draws is the number of frames fused."""
+        if self.phi_global is None or self.image_shape is None:
+            raise RuntimeError("there is no model and no depth camera before the first depth frame")
+        P, (rows, cols) = self.P, self.image_shape
+        R, t = self.vol2cam()
+        pts, nrm = self.ops.raycast(self.phi_global, P["vs"], P["trunc"], R, t, P["intr"], rows=rows, cols=cols)
+        return self.ops.depth_sensor(pts, nrm, self.ops.SensorModel.ideal() if sensor is None else sensor, seed, self.frame)
+
     def warp_to_live(self, vertices, normals=None):
         """Carries marching-cubes vertices of the canonical model (ops.marching_cubes_indexed of phi_global at the volume pose), and their
         normals when given, to the live frame through the current psi: vertex i stays the same surface point from frame to frame.

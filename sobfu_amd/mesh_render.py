@@ -30,12 +30,19 @@ def mesh_grid(vertices, faces):
     return ops.TriangleGrid(*_mesh(vertices, faces))
 
 
-def render_mesh_depth(vertices, faces, intr, rows=480, cols=640, pose=None, grid=None):
+def render_mesh_depth(vertices, faces, intr, rows=480, cols=640, pose=None, grid=None, sensor=None, seed=0, frame=0):
     """uint16 millimetre depth image (numpy) of the mesh seen by the pinhole camera intr = (fx, fy, cx, cy): pixel (u, v) casts
     ((u - cx) / fx, (v - cy) / fy, 1); depth = z of the nearest triangle the ray meets, rounded (half to even) to millimetres; 0 where
-    the ray misses.  grid: a TriangleGrid of this mesh (mesh_grid) to reuse."""
+    the ray misses.  grid: a TriangleGrid of this mesh (mesh_grid) to reuse.  sensor: an ops.SensorModel -- the frame that depth
+    sensor would report of the rendered points and normals (ops.depth_sensor with this seed and frame number) instead of the clean one."""
     g = mesh_grid(vertices, faces) if grid is None else grid
-    d = g.render(intr, rows, cols, pose=pose, outputs=("depth",))["depth"]
+    if sensor is not None:
+        from . import ops
+
+        r = g.render(intr, rows, cols, pose=pose, outputs=("points", "normals"))
+        d = ops.depth_sensor(r["points"], r["normals"], sensor, seed, frame)
+    else:
+        d = g.render(intr, rows, cols, pose=pose, outputs=("depth",))["depth"]
     torch.cuda.synchronize()
     return d.cpu().numpy().view(np.uint16)
 

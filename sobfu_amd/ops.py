@@ -8,6 +8,7 @@ Names follow the reference's launcher names (include/sobfu/*.hpp `namespace devi
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import torch
@@ -509,6 +510,83 @@ def render_normals(normals, image=None):
     check(_lib.lib().sobfu_hip_render_normals(*_image_ptr(normals, torch.float32, 4), C.c_int(rows), C.c_int(cols),
                                               *_image_ptr(image, torch.uint8, 4), _stream()), "render_normals")
     return image
+
+
+# ---- depth sensor model (sobfu_amd/csrc/depth_sensor_kernels.hip) ----------------------------------------------------
+@dataclasses.dataclass
+class SensorModel:
+    """The fields of sobfu_hip_sensor_params but seed and frame (include/sobfu_hip.h states the rule they enter)."""
+    lateral: float = 0.0        # sigma of the pixel jitter, pixels
+    z_min: float = 0.0          # depths kept: (z_min, z_max]
+    z_max: float = float("inf")
+    cos_min: float = 0.0        # pixels seen flatter than this are lost
+    edge_radius: int = 0        # 0..3; 0: no edge test
+    edge_jump: float = 0.0      # metres
+    edge_drop: float = 0.0      # probability that a pixel at an edge is lost
+    drop: float = 0.0           # probability that any pixel is lost
+    a0: float = 0.0             # sigma_z = (a0 + a1 (z - z0)^2) + a2 ((1 - c^2) / c^2) / sqrt(z)
+    a1: float = 0.0
+    z0: float = 0.0
+    a2: float = 0.0
+    disparity: float = 0.0      # focal x baseline x sub-pixel levels, pixel metres; 0: no quantisation
+
+    @classmethod
+    def kinect(cls, **changes):
+        """a first-generation structured-light camera: Nguyen et al.'s axial noise, 0.8 pixels of jitter, 1/8-pixel disparity levels
+        (8 x 0.075 m x 580 px), dropouts beyond 78 degrees and at half of the pixels next to a 5 cm jump"""
+        return dataclasses.replace(cls(lateral=0.8, z_min=0.4, z_max=4.0, cos_min=0.2, edge_radius=1, edge_jump=0.05, edge_drop=0.5, drop=0.0,
+                                       a0=0.0012, a1=0.0019, z0=0.4, a2=0.0001, disparity=348.0), **changes)
+
+    @classmethod
+    def ideal(cls, **changes):
+        """the identity: the frame is the renderer's own depth image, rint(1000 z) of every hit"""
+        return dataclasses.replace(cls(), **changes)
+
+    def params(self, seed=0, frame=0):
+        return _lib.SensorParams(int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame) & 0xFFFFFFFF, self.lateral, self.z_min, self.z_max, self.cos_min,
+                                 int(self.edge_radius), self.edge_jump, self.edge_drop, self.drop, self.a0, self.a1, self.z0, self.a2, self.disparity)
+
+
+def _plane_ptr(t, dtypes, what):
+    if not (t.is_cuda and t.dtype in dtypes and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)):
+        raise ValueError(f"expected a (rows, cols) {dtypes[0]} {what} image on the GPU with contiguous rows, got {t.dtype} {tuple(t.shape)}")
+    return C.c_void_p(t.data_ptr()), C.c_int(t.stride(0) * t.element_size())
+
+
+def depth_sensor(points, normals, model, seed=0, frame=0, depth=None, flags=False):
+    """What a depth sensor described by `model` (a SensorModel) reports of a clean render: points, normals (rows, cols, 4) float32 as
+    ops.raycast and TriangleGrid.render give them -> depth (rows, cols) int16, the bits of uint16 millimetres (0: no reading), as the
+    depth pre-steps take them.  The random numbers depend on (seed, frame, pixel) alone: the same call gives the same frame.  depth: an
+    existing (possibly pitched) image to write into.  flags: True -> (depth, flags), flags (rows, cols) uint8 with what became of every
+    pixel (SOBFU_SENSOR_*: 0 valid, 1 miss, 2 range, 3 grazing, 4 edge, 5 dropout); an existing uint8 image may be given instead."""
+    rows, cols = int(points.shape[0]), int(points.shape[1])
+    if tuple(normals.shape[:2]) != (rows, cols):
+        raise ValueError("points and normals differ in size")
+    if depth is None:
+        depth = torch.empty((rows, cols), dtype=torch.int16, device=points.device)
+    if flags is True:
+        flags = torch.empty((rows, cols), dtype=torch.uint8, device=points.device)
+    want_flags = flags is not None and flags is not False
+    for img in (depth,) + ((flags,) if want_flags else ()):
+        if tuple(img.shape) != (rows, cols):
+            raise ValueError(f"the output images must be {rows} x {cols}")
+    p = model.params(seed, frame)
+    fl = _plane_ptr(flags, (torch.uint8,), "flag") if want_flags else (None, C.c_int(0))
+    check(_lib.lib().sobfu_hip_depth_sensor(*_image_ptr(points, torch.float32, 4), *_image_ptr(normals, torch.float32, 4), C.c_int(rows), C.c_int(cols),
+                                            C.byref(p), *_plane_ptr(depth, (torch.int16, torch.uint16), "depth"), *fl, _stream()), "depth_sensor")
+    return (depth, flags) if want_flags else depth
+
+
+def philox4x32_10(counters, key):
+    """The generator behind depth_sensor on its own: counters (n, 4) int32 (the bits of uint32), key = (k0, k1) -> (n, 4) int32 outputs"""
+    if not (counters.dim() == 2 and counters.shape[1] == 4):
+        raise ValueError("expected (n, 4) counters")
+    out = torch.empty_like(counters)
+    if counters.shape[0] == 0:
+        return out
+    k = (C.c_uint32 * 2)(int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF)
+    check(_lib.lib().sobfu_hip_philox4x32_10(_ptr(counters, torch.int32), k, C.c_int(int(counters.shape[0])), _ptr(out, torch.int32), _stream()), "philox4x32_10")
+    return out
 
 
 # ---- colour (sobfu_amd/csrc/colour_kernels.hip): a (Z, Y, X, 4) uint8 volume of (b, g, r, weight); BGRA frames ---------------------
