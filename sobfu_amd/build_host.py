@@ -128,8 +128,14 @@ def build_trajectory_tool(force: bool = False, flags=()) -> str:
     return _build("trajectory_tool", _test_src("trajectory_tool.cpp"), [TRAJECTORY_HPP], False, force, ["-std=c++14", *flags])
 
 
+def build_pass_a_plan_tool(force: bool = False) -> str:
+    """tests/cpp/pass_a_plan_tool.cpp: CPU-only driver of the warping march's launch plan (sobfu_amd/csrc/sobfu_geometry.hpp, no HIP)."""
+    deps = [os.path.join(CSRC, h) for h in ("sobfu_geometry.hpp", "sobfu_variant.hpp")] + [SOBFU_HIP_H]
+    return _build("pass_a_plan_tool", _test_src("pass_a_plan_tool.cpp"), deps, False, force, ["-std=c++17", f"-I{CSRC}"])
+
+
 def build_host(force: bool = False) -> str:
-    for build in (build_depth_sensor_tool, build_trajectory_tool, build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
+    for build in (build_pass_a_plan_tool, build_depth_sensor_tool, build_trajectory_tool, build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
                   build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_mesh_parity_tool, build_rigid_tool):
         build(force)
     return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H], True, force)

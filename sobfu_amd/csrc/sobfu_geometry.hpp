@@ -27,6 +27,12 @@ constexpr int TX = 64;  // tile width in lanes: one wave per tile row (32-wide t
 // tile of a workgroup: 64 lanes x 8 waves, one row per wave (rows-per-thread 2 / 4 and 4 / 16 waves were measured in rounds 1 - 2:
 // profiles/LABBOOK.md; the kernels keep RPT / WY as template parameters, the launchers instantiate this one shape)
 constexpr int kRPT = 1, kWY = 8;
+// ... but the WARPING march of pass A, whose halo rows and columns cost a whole trilinear sample per wave: three halo tasks per 16 rows
+// instead of three per 8 (1.19 x instead of 1.375 x wave-samples per row); 8 and 16 measured: profiles/r08_pass_a_tiles_sampler.md
+#ifndef SOBFU_WARP_WY
+#define SOBFU_WARP_WY 16
+#endif
+constexpr int kWarpWY = SOBFU_WARP_WY;
 // the chip: workgroups of 8 waves that are resident at once when a CU holds `per_cu` of them (VGPRs / LDS / waves decide how many)
 constexpr int kCUs = 256;
 constexpr int wg_slots(int per_cu) { return kCUs * per_cu * 8 / kWY; }
@@ -237,6 +243,11 @@ inline bool has_direct_box(const LaunchBox* boxes, int n) {
 inline int plan_pass_a(BoxList& L, const LaunchBox* boxes, int n) {
     // <= 64 VGPR (the warping march included), 22 KB LDS: 4 workgroups of 8 waves per CU
     return finish_boxes(L, boxes, n, kRPT * kWY, wg_slots(4), 2, "SOBFU_ZC_A");
+}
+// the warping march of pass A (fused_potential_gradient_kernel<.., WARP>): tiles of 64 x kWarpWY cells, one row per wave
+inline int plan_pass_a_warp(BoxList& L, const LaunchBox* boxes, int n) {
+    // <= 64 VGPR: 8 waves per SIMD, 32 per CU -- 2 workgroups of 16 waves (39 KB LDS each)
+    return finish_boxes(L, boxes, n, kRPT * kWarpWY, kCUs * 32 / kWarpWY, 2, "SOBFU_ZC_A");
 }
 // pass A of a launch that holds thin boxes: the tile kernel (no messages, no signalling, no gate) with a list of the call's own
 // (< 0: too many boxes)

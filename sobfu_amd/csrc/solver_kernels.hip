@@ -86,12 +86,13 @@ int launch_pass_a(const PassALaunch& L, hipStream_t stream) {
         return rc != 0 ? rc : (int) f;
     }
     PassAArgs a{{L.pnp, L.pg, L.psi, L.nU, {L.X, L.Y, L.Z}, L.w_reg, L.prev_slots, L.max_update_norm}, {}};
-    const int groups = plan_pass_a(a.boxes, L.boxes, L.n_boxes);
+    const int groups = v.warp ? plan_pass_a_warp(a.boxes, L.boxes, L.n_boxes) : plan_pass_a(a.boxes, L.boxes, L.n_boxes);
     if (groups == 0) return 0;
-    const dim3 grid((unsigned) groups), block(TX, kWY);
+    const dim3 grid((unsigned) groups);
     const bool found = launch_row(kPassATable, v, [&](auto i) {
         constexpr PassAVariant V = kPassATable[decltype(i)::value];
-        hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, kWY, V.compact, V.nt ? kNT : 0, V.warp>), grid, block, 0, stream, a);
+        constexpr int WY = V.warp ? kWarpWY : kWY;  // the warping march has a tile height of its own
+        hipLaunchKernelGGL((fused_potential_gradient_kernel<kRPT, WY, V.compact, V.nt ? kNT : 0, V.warp>), grid, dim3(TX, WY), 0, stream, a);
     });
     return found ? (int) hipGetLastError() : SOBFU_E_UNSUPPORTED;
 }

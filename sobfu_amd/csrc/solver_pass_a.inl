@@ -316,7 +316,9 @@ SOBFU_DEV void pass_a_march(const PassACore& a, const TileGeom& tg, const GateRe
 }
 
 
-// WARP: a.c.pnp is phi_n (see pass_a_march); its register budget is held at 64 VGPR, 8 waves per SIMD: 4 workgroups per CU, like the others
+// WARP: a.c.pnp is phi_n (see pass_a_march); its register budget is held at 64 VGPR, 8 waves per SIMD.  Its tiles are kWarpWY = 16 rows high
+// (the launcher's choice: sobfu_geometry.hpp), two workgroups of 16 waves per CU where the others run four of 8: the three halo tasks, each
+// a whole trilinear sample on a wave of its own, are then paid once per 16 rows instead of once per 8
 template <int RPT, int WY, bool COMPACT, int NTL, bool WARP = false>
 __global__ void __launch_bounds__(TX* WY, WARP ? 8 : 1) fused_potential_gradient_kernel(PassAArgs a) {
     const GateRegs gate = gate_load(a.c.prev_slots, 1);
