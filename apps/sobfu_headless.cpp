@@ -53,7 +53,8 @@
 // TSDF (SobFusion::integrate_mesh), without a depth camera in between; a mesh that is not closed ends the run.  It shares the mesh and the
 // scoring grid with --evaluate-live as --render-mesh does (the voxelisation builds a grid of its own over the vertices in the volume's
 // frame).  --evaluate-signed adds signed_mean, inside and open to each side of the evaluate lines: the sign of a vertex against the
-// other mesh, > 0 outside.
+// other mesh, > 0 outside.  --mesh-sign parity|winding chooses the inside / outside rule of both: parity (the default) is for
+// closed meshes; winding takes the generalised winding number, is defined for open meshes too, and refuses none for being open.
 //
 // A depth sensor and a moving camera for --render-mesh (opt-in; sobfu_amd/csrc/depth_sensor_kernels.hip): --sensor kinect|ideal
 // passes every rendered frame -- its points and normals -- through the depth sensor model before it goes the way a depth file's pixels go:
@@ -72,7 +73,7 @@
 //                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE]
 //                   [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE]
 //                   | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | frame0.pgm frame1.pgm ...)
-//                  [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-signed]
+//                  [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-signed] [--mesh-sign parity|winding]
 #include <dirent.h>
 #include <sys/stat.h>
 
@@ -237,6 +238,7 @@ int main(int argc, char** argv) {
     std::string eval_gt, eval_live, eval_pose, error_dir, eval_pose_out;
     std::string render_mesh, render_pose;  // --render-mesh: the frame source; --render-pose: applied to its meshes first
     bool voxelise = false, eval_signed = false;  // --voxelise-mesh: the meshes reach the solver as volumes, not as depth frames
+    int mesh_sign = sobfu_amd::kSignParity;      // --mesh-sign: the inside / outside rule of --voxelise-mesh and --evaluate-signed
     int render_frames = 1;
     bool sensor = false;  // --sensor: rendered frames pass through sensor_model
     sobfu_amd::SensorModel sensor_model;
@@ -295,6 +297,14 @@ int main(int argc, char** argv) {
             render_mesh = argv[++i], voxelise = true;
         }
         else if (a == "--evaluate-signed") eval_signed = true;
+        else if (a == "--mesh-sign" && i + 1 < argc) {
+            const std::string rule = argv[++i];
+            if (rule != "parity" && rule != "winding") {
+                std::printf("--mesh-sign takes parity or winding\n");
+                return 2;
+            }
+            mesh_sign = rule == "winding" ? sobfu_amd::kSignWinding : sobfu_amd::kSignParity;
+        }
         else if (a == "--render-frames" && i + 1 < argc) render_frames = std::atoi(argv[++i]);
         else if (a == "--render-pose" && i + 1 < argc) render_pose = argv[++i];
         else if (a == "--sensor" && i + 1 < argc) {
@@ -382,8 +392,8 @@ int main(int argc, char** argv) {
         sobfu_amd::AlignRequest request;
         std::copy(gt_pose, gt_pose + 16, request.pose);
         request.iters = eval_align, request.dof = eval_align_dof;
-        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why, shared ? &rendered.grid : nullptr, eval_signed)
-                   : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr, eval_signed))) {
+        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why, shared ? &rendered.grid : nullptr, eval_signed, mesh_sign)
+                   : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr, eval_signed, mesh_sign))) {
             std::printf("cannot evaluate against %s: %s\n", gt_path.c_str(), why.c_str());
             return false;
         }
@@ -564,7 +574,7 @@ int main(int argc, char** argv) {
         if (voxelise) {
             std::string why;
             kfusion::SampledScopeTime fps(time_ms);
-            if (!fusion.integrate_mesh(rendered.mesh, sobfu_amd::mesh_frame(), false, &why)) {
+            if (!fusion.integrate_mesh(rendered.mesh, sobfu_amd::mesh_frame(), false, &why, nullptr, mesh_sign)) {
                 std::printf("cannot voxelise %s: %s\n", rendered.path.c_str(), why.c_str());
                 return 2;
             }

@@ -5,7 +5,8 @@
 // (sobfu_amd/csrc/mesh_align_kernels.hip): TriangleGrid::align, align_meshes, format_alignment.  Rays and a camera over
 // the same grid (sobfu_amd/csrc/mesh_ray_kernels.hip): TriangleGrid::raycast, TriangleGrid::render.  Closed meshes as signed
 // TSDF volumes and the inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip): TriangleGrid::voxelise,
-// TriangleGrid::inside, mesh_to_tsdf, and the signed fields of compare_meshes.
+// TriangleGrid::inside, mesh_to_tsdf, and the signed fields of compare_meshes.  Open meshes through generalised winding numbers (DESIGN.md 4.14,
+// sobfu_amd/csrc/mesh_winding_kernels.hip): TriangleGrid::boundary, TriangleGrid::winding, and MeshSign on voxelise, mesh_to_tsdf and compare_meshes.
 #pragma once
 
 #include "../../sobfu_amd/csrc/sobfu_rigid.hpp"  // the rigid inverse, the same lines as the kernels'
@@ -208,12 +209,17 @@ struct Alignment {
     std::vector<float> trace;
 };
 
+// the inside / outside rule of voxelise, mesh_to_tsdf, compare_meshes and SobFusion::integrate_mesh: the parity of the row crossings (closed
+// meshes) or the generalised winding number (any oriented mesh)
+enum MeshSign { kSignParity = 0, kSignWinding = 1 };
+
 // ---- TriangleGrid: the grid of sobfu_hip_mesh_grid_build over a mesh kept on the device ---------------------------------------------
 class TriangleGrid {
 public:
     // false (+ *why): a face index out of range or a non-finite corner -- there is no grid to query then
     bool build(const std::vector<float4>& vertices, const std::vector<int>& faces, float cell = 0.f, std::string* why = nullptr) {
-        built_ = false;
+        built_ = has_boundary_ = false;
+        nb_ = 0, boundary_.release();
         nv_ = (int) vertices.size(), nt_ = (int) (faces.size() / 3);
         float bbox[6] = {0, 0, 0, 0, 0, 0};
         bool any = false;
@@ -369,9 +375,26 @@ public:
     // ops.TriangleGrid.voxelise / inside) ----
     // d_vol: dims[0] x dims[1] x dims[2] float2 {tsdf, weight} on the device, the mesh's vertices being in the volume's frame: voxel i of
     // an axis has its centre at i vs + vs / 2; tsdf = clamp(s / trunc, -1, 1), s the exact distance to the mesh, negative inside; weight =
-    // s > -eta.  -> the number of rows along x that cross the mesh an odd number of times: 0 for a closed mesh (synchronises)
-    int voxelise(float* d_vol, const int dims[3], const float vs[3], float trunc, float eta, int mode = SOBFU_MESH_DISTANCE_AUTO) {
+    // s > -eta.  -> the number of rows along x that cross the mesh an odd number of times: 0 for a closed mesh (synchronises).
+    // sign: kSignParity (a closed mesh: inside iff the row crosses it an odd number of times beyond the voxel) or kSignWinding (any oriented
+    // mesh, open ones included: inside iff the generalised winding number exceeds 1 / 2; the count returned is then only
+    // information); d_winding (kSignWinding, may be NULL): dims[0] x dims[1] x dims[2] floats on the device, w at every voxel centre
+    int voxelise(float* d_vol, const int dims[3], const float vs[3], float trunc, float eta, int mode = SOBFU_MESH_DISTANCE_AUTO, int sign = kSignParity,
+                 float* d_winding = nullptr) {
         if (!built_) kfusion::cuda::error("TriangleGrid::voxelise without a built grid", __FILE__, __LINE__);
+        if (sign == kSignWinding) {
+            const size_t wbytes = sobfu_hip_mesh_voxelise_winding_workspace_bytes(dims[0], dims[1], dims[2]);
+            if (wbytes == 0) kfusion::cuda::error("TriangleGrid::voxelise: at most 512 voxels along x", __FILE__, __LINE__);
+            boundary();
+            kfusion::cuda::DeviceArray<unsigned char> wws(wbytes);
+            kfusion::cuda::DeviceArray<int> wopen(1);
+            sobfuSafeCall(with_target(sobfu_hip_mesh_voxelise_winding, nb_ ? (const float*) boundary_.ptr() : nullptr, nb_, d_vol, dims[0], dims[1], dims[2], vs,
+                                      trunc, eta, mode, wws.ptr(), wws.size(), wopen.ptr(), d_winding, nullptr));
+            std::vector<int> wn;
+            wopen.download(wn);
+            return wn[0];
+        }
+        if (sign != kSignParity || d_winding) kfusion::cuda::error("TriangleGrid::voxelise: unknown sign, or d_winding without kSignWinding", __FILE__, __LINE__);
         const size_t bytes = sobfu_hip_mesh_voxelise_workspace_bytes(dims[0], dims[1], dims[2]);
         if (bytes == 0) kfusion::cuda::error("TriangleGrid::voxelise: at most 512 voxels along x", __FILE__, __LINE__);
         kfusion::cuda::DeviceArray<unsigned char> ws(bytes);
@@ -394,6 +417,43 @@ public:
         sobfuSafeCall(with_target(sobfu_hip_mesh_inside, (const float*) dp.ptr(), (int) n, di.ptr(), dopen.ptr(), mode, nullptr));
         di.download(inside), dopen.download(open);
     }
+    // ---- generalised winding numbers (sobfu_amd/csrc/mesh_winding_kernels.hip; ops.TriangleGrid.winding) ----
+    // the boundary chain, computed once and kept on the device: two float4 per edge, (u, k) and (v, 0) -> the number of edges (0: closed)
+    int boundary() {
+        if (!built_) kfusion::cuda::error("TriangleGrid::boundary without a built grid", __FILE__, __LINE__);
+        if (has_boundary_) return nb_;
+        std::vector<int> faces, edges;
+        std::vector<float4> vertices;
+        if (nt_) faces_.download(faces);
+        if (nv_) vertices_.download(vertices);
+        int count = 0;
+        sobfuSafeCall(sobfu_hip_mesh_boundary(nt_ ? faces.data() : nullptr, nt_, nv_, nullptr, 0, &count));
+        edges.resize(3 * (size_t) count);
+        if (count) sobfuSafeCall(sobfu_hip_mesh_boundary(faces.data(), nt_, nv_, edges.data(), count, &count));
+        std::vector<float4> pairs(2 * (size_t) count);
+        for (int e = 0; e < count; ++e) {
+            const float4 &u = vertices[edges[3 * e]], &v = vertices[edges[3 * e + 1]];
+            pairs[2 * e] = make_float4(u.x, u.y, u.z, (float) edges[3 * e + 2]), pairs[2 * e + 1] = make_float4(v.x, v.y, v.z, 0.f);
+        }
+        if (count) boundary_.upload(pairs);
+        nb_ = count, has_boundary_ = true;
+        return nb_;
+    }
+    // per point: the winding number -- 1 inside and 0 outside a closed, outward-oriented mesh, smooth across holes; inside iff > 1 / 2.
+    // mode: SOBFU_MESH_WINDING_BOUNDARY (crossings + boundary strips) or _SUM (the definition); walk: the crossing walk, never changes a bit
+    void winding(const std::vector<float4>& points, std::vector<float>& w, int mode = SOBFU_MESH_WINDING_BOUNDARY, int walk = SOBFU_MESH_DISTANCE_AUTO) {
+        if (!built_) kfusion::cuda::error("TriangleGrid::winding without a built grid", __FILE__, __LINE__);
+        const size_t n = points.size();
+        w.assign(n, 0.f);
+        if (n == 0) return;
+        boundary();
+        kfusion::cuda::DeviceArray<float4> dp;
+        kfusion::cuda::DeviceArray<float> dw(n);
+        dp.upload(points);
+        sobfuSafeCall(with_target(sobfu_hip_mesh_winding, nb_ ? (const float*) boundary_.ptr() : nullptr, nb_, (const float*) dp.ptr(), (int) n, dw.ptr(), mode,
+                                  walk, nullptr));
+        dw.download(w);
+    }
     bool built() const { return built_; }
     int references() const { return references_; }
     const int* dims() const { return dims_; }
@@ -409,9 +469,10 @@ private:
     kfusion::cuda::DeviceArray<float4> vertices_;
     kfusion::cuda::DeviceArray<int> faces_;
     kfusion::cuda::DeviceArray<unsigned char> workspace_;
+    kfusion::cuda::DeviceArray<float4> boundary_;
     float origin_[3] = {0, 0, 0}, h_ = 0.f;
-    int dims_[3] = {1, 1, 1}, nv_ = 0, nt_ = 0, references_ = 0;
-    bool built_ = false;
+    int dims_[3] = {1, 1, 1}, nv_ = 0, nt_ = 0, references_ = 0, nb_ = 0;
+    bool built_ = false, has_boundary_ = false;
 };
 
 // ---- the depth sensor model (sobfu_amd/csrc/depth_sensor_kernels.hip; ops.SensorModel / ops.depth_sensor) ---------------
@@ -503,9 +564,11 @@ inline void add_signs(DistanceStats& s, const std::vector<float>& dist, const st
     if (s.within) s.signed_mean = sum / (double) s.within;
 }
 // with_signs: each direction gains signed_mean, inside and open -- the sign of the query vertex against the OTHER mesh (TriangleGrid::inside),
-// which should be closed; the unsigned fields are the same with and without
+// which should be closed; the unsigned fields are the same with and without.  sign = kSignWinding: inside iff the other mesh's winding number
+// exceeds 1 / 2 (TriangleGrid::winding), which is defined for open meshes too; `open` is counted as before
 inline bool compare_meshes(const IndexedMesh& a, const IndexedMesh& b, float max_dist, MeshComparison& out, std::vector<float>* d_ab = nullptr,
-                           std::vector<float>* d_ba = nullptr, std::string* why = nullptr, TriangleGrid* grid_b = nullptr, bool with_signs = false) {
+                           std::vector<float>* d_ba = nullptr, std::string* why = nullptr, TriangleGrid* grid_b = nullptr, bool with_signs = false,
+                           int sign = kSignParity) {
     TriangleGrid ga, own;
     if (!grid_b && !own.build(b.vertices, b.faces, 0.f, why)) return false;
     TriangleGrid& gb = grid_b ? *grid_b : own;
@@ -517,9 +580,17 @@ inline bool compare_meshes(const IndexedMesh& a, const IndexedMesh& b, float max
     out.chamfer = 0.5 * (out.a_to_b.mean + out.b_to_a.mean), out.hausdorff = std::max(out.a_to_b.max, out.b_to_a.max);
     if (with_signs) {
         std::vector<unsigned char> in, open;
+        std::vector<float> w;
+        auto by_winding = [&](TriangleGrid& g, const std::vector<float4>& p) {
+            if (sign != kSignWinding) return;
+            g.winding(p, w);
+            for (size_t i = 0; i < w.size(); ++i) in[i] = w[i] > 0.5f;
+        };
         gb.inside(a.vertices, in, open);
+        by_winding(gb, a.vertices);
         add_signs(out.a_to_b, ab, in, open);
         ga.inside(b.vertices, in, open);
+        by_winding(ga, b.vertices);
         add_signs(out.b_to_a, ba, in, open);
     }
     if (d_ab) d_ab->swap(ab);
@@ -611,9 +682,9 @@ inline void mesh_to_volume_frame(std::vector<float4>& vertices, const cv::Affine
 }
 // Fills `vol` (its dims, voxel size, truncation distance and eta) with the mesh: the vertices are transformed once and the triangle grid is
 // built with a cell edge of `cell` (0: four voxels, half a brick -- profiles/mesh_voxelise.md).  *open_rows: the rows
-// that cross the mesh an odd number of times, 0 for a closed mesh.  false (+ *why): the mesh is refused (TriangleGrid::build)
+// that cross the mesh an odd number of times, 0 for a closed mesh.  false (+ *why): the mesh is refused (TriangleGrid::build).  sign: MeshSign
 inline bool mesh_to_tsdf(const IndexedMesh& mesh, const cv::Affine3f& mesh2cam, const cv::Affine3f& vol2cam, kfusion::cuda::TsdfVolume& vol, int* open_rows,
-                         std::string* why = nullptr, float cell = 0.f, int mode = SOBFU_MESH_DISTANCE_AUTO) {
+                         std::string* why = nullptr, float cell = 0.f, int mode = SOBFU_MESH_DISTANCE_AUTO, int sign = kSignParity) {
     std::vector<float4> v = mesh.vertices;
     mesh_to_volume_frame(v, mesh2cam, vol2cam);
     TriangleGrid grid;
@@ -622,7 +693,7 @@ inline bool mesh_to_tsdf(const IndexedMesh& mesh, const cv::Affine3f& mesh2cam, 
     if (!grid.build(v, mesh.faces, cell > 0.f ? cell : 4.f * std::max(s[0], std::max(s[1], s[2])), why)) return false;
     const int dims[3]  = {d[0], d[1], d[2]};
     const float vs[3]  = {s[0], s[1], s[2]};
-    const int open     = grid.voxelise(vol.data().ptr<float>(), dims, vs, vol.getTruncDist(), vol.getEta(), mode);
+    const int open     = grid.voxelise(vol.data().ptr<float>(), dims, vs, vol.getTruncDist(), vol.getEta(), mode, sign);
     if (open_rows) *open_rows = open;
     return true;
 }

@@ -1348,14 +1348,15 @@ public:
     // no sensor model) in place of bilateral -> truncate -> dists -> integrate; everything after that is operator()'s.  mesh: in the mesh
     // frame; mesh2cam: mesh frame -> camera frame (the default: the meshes written here, (x, -y, -z)).  Camera tracking does not apply: the
     // pose is appended unchanged.  false (+ *why), with nothing fused: the mesh is refused, or it is not closed (rows that cross it an odd
-    // number of times) and allow_open is not set.
+    // number of times) and allow_open is not set.  sign = sobfu_amd::kSignWinding: inside iff the mesh's generalised winding number exceeds
+    // 1 / 2, which is defined for open meshes too: none is refused for being open.
     bool integrate_mesh(const sobfu_amd::IndexedMesh& mesh, const cv::Affine3f& mesh2cam = sobfu_amd::mesh_frame(), bool allow_open = false,
-                        std::string* why = nullptr, int* open_rows = nullptr) {
+                        std::string* why = nullptr, int* open_rows = nullptr, int sign = sobfu_amd::kSignParity) {
         cv::Ptr<kfusion::cuda::TsdfVolume> target = frame_counter_ == 0 ? cv::Ptr<kfusion::cuda::TsdfVolume>(new kfusion::cuda::TsdfVolume(params)) : phi_n;
         int open = 0;
-        if (!sobfu_amd::mesh_to_tsdf(mesh, mesh2cam, camera_pose_.inv() * params.volume_pose, *target, &open, why)) return false;
+        if (!sobfu_amd::mesh_to_tsdf(mesh, mesh2cam, camera_pose_.inv() * params.volume_pose, *target, &open, why, 0.f, SOBFU_MESH_DISTANCE_AUTO, sign)) return false;
         if (open_rows) *open_rows = open;
-        if (open > 0 && !allow_open) {
+        if (sign != sobfu_amd::kSignWinding && open > 0 && !allow_open) {
             if (why) *why = "the mesh is not closed: " + std::to_string(open) + " rows of the volume cross it an odd number of times";
             return false;
         }
@@ -1422,7 +1423,8 @@ public:
     // align (optional, canonical only): align->pose, the caller's ground-truth-to-model guess, is first refined against the model
     // (sobfu_amd::align_meshes with max_dist) and applied to a copy of the ground truth; without it the ground truth is taken as given.
     bool evaluate_canonical(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
-                            std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::AlignRequest* align = nullptr, bool with_signs = false) {
+                            std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::AlignRequest* align = nullptr, bool with_signs = false,
+                            int sign = sobfu_amd::kSignParity) {
         sobfu_amd::IndexedMesh m = get_phi_global_indexed_mesh();
         bool ok;
         if (align) {
@@ -1430,19 +1432,21 @@ public:
             ok = sobfu_amd::align_meshes(m.vertices, gt, align->pose, align->info, align->iters, max_dist, align->dof, 0.f, 0.f, why);
             if (ok) {
                 sobfu_amd::transform_points(posed.vertices, align->pose);
-                ok = sobfu_amd::compare_meshes(m, posed, max_dist, out, d_model, nullptr, why, nullptr, with_signs);
+                ok = sobfu_amd::compare_meshes(m, posed, max_dist, out, d_model, nullptr, why, nullptr, with_signs, sign);
             }
         } else {
-            ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, nullptr, with_signs);
+            ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, nullptr, with_signs, sign);
         }
         if (model) *model = std::move(m);
         return ok;
     }
-    // gt_grid (optional): a grid already built over gt, used instead of building another.  with_signs (both): the comparison's signed fields
+    // gt_grid (optional): a grid already built over gt, used instead of building another.  with_signs (both): the comparison's signed fields,
+    // by the rule `sign` (sobfu_amd::MeshSign)
     bool evaluate_live(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
-                       std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::TriangleGrid* gt_grid = nullptr, bool with_signs = false) {
+                       std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::TriangleGrid* gt_grid = nullptr, bool with_signs = false,
+                       int sign = sobfu_amd::kSignParity) {
         sobfu_amd::IndexedMesh m = get_phi_global_warped_indexed_mesh();
-        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, gt_grid, with_signs);
+        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, gt_grid, with_signs, sign);
         if (model) *model = std::move(m);
         return ok;
     }

@@ -698,6 +698,40 @@ int sobfu_hip_mesh_inside(void* d_grid_workspace, size_t grid_workspace_bytes, c
                           uint8_t* d_open, int mode, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * generalised winding numbers  (no counterpart in the reference; sobfu_amd/csrc/mesh_winding_kernels.hip)
+ * Inside / outside for meshes that are not closed: w(p) is 1 inside and 0 outside a closed, outward-oriented mesh, varies smoothly
+ * across holes, and "inside iff w > 1 / 2" is defined for any oriented triangle soup (Jacobson et al. 2013).  Computed from the mesh's
+ * boundary: w = N + the solid angles of the strips from the boundary edges to infinity along -x, over 4 pi, with N the signed number of
+ * crossings of the row beyond p (the counting rule of sobfu_mesh_parity.hpp with signs; sobfu_amd/csrc/sobfu_mesh_winding.hpp).  fp64,
+ * accumulated in index order: the same bits from run to run and for every walk mode.  A workspace that is not marked as built, or no
+ * triangles: w = 0 everywhere.  Every argument is checked before any device call (SOBFU_E_BADARG).
+ * ---------------------------------------------------------------------------------------------------- */
+/* Host only: the boundary chain of n_triangles faces (3 ints each, host memory) -> the (u, v, k) with u < v and
+ * k = (#triangles that run u -> v) - (#that run v -> u) != 0, sorted by (u, v), 3 ints per edge into h_edges; *h_count = their number.
+ * h_edges = NULL (capacity 0) only counts.  SOBFU_E_BADARG: an index outside [0, n_vertices); SOBFU_E_UNSUPPORTED: capacity (in
+ * edges) is smaller than *h_count. */
+int sobfu_hip_mesh_boundary(const int* h_faces, int n_triangles, int n_vertices, int* h_edges, int capacity, int* h_count);
+#define SOBFU_MESH_WINDING_BOUNDARY 0 /* crossings + boundary strips; the definition where a point lies on a seam */
+#define SOBFU_MESH_WINDING_SUM 1      /* the definition: every triangle's solid angle; d_boundary is not read */
+/* n points (dense float4, w ignored) -> d_w[i], the winding number as a float.  d_boundary: n_boundary edges of the chain as two float4
+ * each, (u.x, u.y, u.z, k) and (v.x, v.y, v.z, .), device memory (NULL for none).  mode: SOBFU_MESH_WINDING_*; walk: the crossing
+ * walk, SOBFU_MESH_DISTANCE_AUTO, _GRID or _BRUTE (never changes a bit).  n = 0 succeeds and launches nothing.  Asynchronous. */
+int sobfu_hip_mesh_winding(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                           int n_triangles, const float origin[3], float h, const int dims[3], const float* d_boundary, int n_boundary,
+                           const float* d_points, int n, float* d_w, int mode, int walk, void* stream);
+/* Bytes of the caller-kept workspace (16-byte aligned) of sobfu_hip_mesh_voxelise_winding: the sign bits and the list of seam voxels.
+ * 0 for X outside [1, 512], Y or Z < 1, or more than INT_MAX voxels. */
+size_t sobfu_hip_mesh_voxelise_winding_workspace_bytes(int X, int Y, int Z);
+/* sobfu_hip_mesh_voxelise with the sign of the winding number: a voxel is inside iff w > 1 / 2 at its centre.  Distances, packing and
+ * margins are sobfu_hip_mesh_voxelise's; for a closed, outward-oriented mesh (no boundary) so is every bit of the volume.
+ * *d_open_rows stays the number of rows crossed an odd number of times, for information.  d_winding (X * Y * Z floats, may be NULL): w
+ * at every voxel centre. */
+int sobfu_hip_mesh_voxelise_winding(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,
+                                    int n_triangles, const float origin[3], float h, const int dims[3], const float* d_boundary, int n_boundary,
+                                    float* d_vol, int X, int Y, int Z, const float voxel_size[3], float trunc, float eta, int mode, void* d_workspace,
+                                    size_t workspace_bytes, int* d_open_rows, float* d_winding, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * depth sensor model  (no counterpart in the reference; sobfu_amd/csrc/depth_sensor_kernels.hip, sobfu_random.hpp)
  * A clean render -- the float4 point and normal images of sobfu_hip_mesh_render or sobfu_hip_raycast -- into the uint16 millimetre frame
  * a structured-light camera would report: lateral jitter, distance- and angle-dependent axial noise, disparity quantisation, dropouts

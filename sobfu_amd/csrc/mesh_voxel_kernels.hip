@@ -275,6 +275,24 @@ size_t bits_bytes(int X, int Y, int Z) { return ((size_t) Y * Z * words_per_row(
 
 }  // namespace
 
+namespace sobfu_hip {
+
+// The distance pass alone, over sign bits that another unit wrote into d_bits in row_parity_kernel's format (mesh_winding_kernels.hip).
+// The arguments are sobfu_hip_mesh_voxelise's and have been checked there.
+int mesh_voxel_bricks(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles,
+                      const float origin[3], float h, const int dims[3], float* d_vol, int X, int Y, int Z, const float voxel_size[3], float trunc,
+                      float eta, int mode, void* d_bits, int* d_open_rows, void* stream) {
+    MeshTarget tg;
+    SOBFU_CHECK_ARGS(mesh_target(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
+    const VoxArgs a{tg.mesh, is_brute(mode, n_triangles), {X, Y, Z}, voxel_size[0], voxel_size[1], voxel_size[2], trunc, eta, tg.box_l, (float2*) d_vol,
+                    (unsigned*) d_bits, words_per_row(X), d_open_rows};
+    const dim3 bricks((unsigned) ((X + kBrick - 1) / kBrick), (unsigned) ((Y + kBrick - 1) / kBrick), (unsigned) ((Z + kBrick - 1) / kBrick));
+    hipLaunchKernelGGL(brick_kernel, bricks, dim3(512), 0, (hipStream_t) stream, tg.grid, a);
+    return (int) hipGetLastError();
+}
+
+}  // namespace sobfu_hip
+
 extern "C" {
 
 size_t sobfu_hip_mesh_voxelise_workspace_bytes(int X, int Y, int Z) {

@@ -1,5 +1,6 @@
 // The mesh side's home: what the units that work on "an indexed triangle mesh plus its uniform grid" share -- mesh_distance_kernels.hip
-// (builds the grid, queries it with points), mesh_ray_kernels.hip (rays), mesh_voxel_kernels.hip (rows, bricks), mesh_align_kernels.hip.
+// (builds the grid, queries it with points), mesh_ray_kernels.hip (rays), mesh_voxel_kernels.hip (rows, bricks), mesh_winding_kernels.hip
+// (rows and points with winding numbers), mesh_align_kernels.hip.
 // The grid's workspace as the kernels see it, the mesh record and its corner loads, a triangle's cell range, the LDS staging loads of the
 // 256-lane brute-force loops, the margin, the mode, and the one check of the nine arguments every mesh entry point of the C ABI starts with.  The
 // plan (origin, cell edge, dims) is sobfu_mesh_grid.hpp's.  Internal linkage, no kernels: the scan is compiled where it is launched.

@@ -45,7 +45,9 @@ def compare_meshes(a_vertices, a_faces, b_vertices, b_faces, max_dist=None, retu
     return_distances: -> (dict, a_to_b distances, b_to_a distances) (float32 GPU tensors).
     signed: each direction gains the fields of signed_stats -- the sign is that of the query vertex against the OTHER mesh
     (ops.TriangleGrid.inside), which should be closed: a_to_b.signed_mean > 0 says mesh a lies outside b on average (inflated).  The
-    unsigned fields are the same with and without."""
+    unsigned fields are the same with and without.
+    signed="winding": the sign is that of the other mesh's generalised winding number (ops.TriangleGrid.winding: inside iff > 1 / 2),
+    which is defined for open meshes too; `open` still counts the vertices on rows the other mesh crosses an odd number of times."""
     import torch
 
     from . import ops
@@ -56,7 +58,10 @@ def compare_meshes(a_vertices, a_faces, b_vertices, b_faces, max_dist=None, retu
     d_ab = gb.query(av, max_dist)[0]
     d_ba = ga.query(bv, max_dist)[0]
     ab, ba = distance_stats(d_ab), distance_stats(d_ba)
-    if signed:
+    if signed == "winding":
+        ab.update(signed_stats(d_ab, gb.winding(av) > 0.5, gb.inside(av)[1]))
+        ba.update(signed_stats(d_ba, ga.winding(bv) > 0.5, ga.inside(bv)[1]))
+    elif signed:
         ab.update(signed_stats(d_ab, *gb.inside(av)))
         ba.update(signed_stats(d_ba, *ga.inside(bv)))
     out = dict(a_to_b=ab, b_to_a=ba, chamfer=0.5 * (ab["mean"] + ba["mean"]), hausdorff=max(ab["max"], ba["max"]))

@@ -117,19 +117,20 @@ class SobFusion:
 
         return self._frame(integrate, colour)
 
-    def integrate_mesh(self, vertices, faces, pose=MESH_FRAME, allow_open=False):
+    def integrate_mesh(self, vertices, faces, pose=MESH_FRAME, allow_open=False, sign="parity"):
         """A frame whose phi_n is the closed mesh itself, voxelised (sobfu_amd.mesh_voxelise.mesh_to_tsdf: exact signed distances on both
         sides of the surface, no sensor model) in place of bilateral -> truncate -> dists -> integrate_depth; everything after that is
         __call__'s.  vertices (V, 3 | 4), faces (F, 3) in the mesh frame; pose = (R, t): mesh frame -> camera frame (MESH_FRAME: the
         meshes the project writes).  Camera tracking does not apply: the pose is appended unchanged.  A mesh that is not closed (rows
-        that cross it an odd number of times) raises ValueError before anything is fused, unless allow_open."""
+        that cross it an odd number of times) raises ValueError before anything is fused, unless allow_open.  sign="winding": inside
+        iff the mesh's generalised winding number exceeds 1 / 2, which is defined for open meshes too: none is refused."""
         from .mesh_voxelise import mesh_to_tsdf
 
         ops, P = self.ops, self.P
         R, t = self.vol2cam()
         target = ops.new_volume(P["dims"]) if self.frame == 0 else self.phi_n
-        _, open_rows = mesh_to_tsdf(vertices, faces, dict(P, R=R, t=t), pose=pose, out=target)
-        if int(open_rows) > 0 and not allow_open:
+        _, open_rows = mesh_to_tsdf(vertices, faces, dict(P, R=R, t=t), pose=pose, out=target, sign=sign)
+        if sign != "winding" and int(open_rows) > 0 and not allow_open:
             raise ValueError(f"the mesh is not closed: {int(open_rows)} rows of the volume cross it an odd number of times")
         self.poses.append(self.pose.copy())
 

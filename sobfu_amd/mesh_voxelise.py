@@ -28,15 +28,16 @@ def mesh_to_volume_frame(vertices, params, pose=MESH_FRAME):
     return out
 
 
-def mesh_to_tsdf(vertices, faces, params, pose=MESH_FRAME, out=None, cell=None, mode="auto", return_grid=False):
+def mesh_to_tsdf(vertices, faces, params, pose=MESH_FRAME, out=None, cell=None, mode="auto", return_grid=False, sign="parity"):
     """vertices (V, 3 | 4) and faces (F, 3), numpy arrays or tensors, in the mesh frame -> (phi (Z, Y, X, 2) float32 GPU tensor of the
     volume of `params` (dims, vs, trunc, eta), open_rows (1,) int32 GPU tensor: 0 for a closed mesh).  The vertices are transformed once
     and the triangle grid is built with a cell edge of `cell` (None: CELL_IN_VOXELS voxels).  out: a volume to
-    write into.  return_grid: -> (phi, open_rows, grid), the ops.TriangleGrid of the transformed mesh (in the VOLUME's frame)."""
+    write into.  return_grid: -> (phi, open_rows, grid), the ops.TriangleGrid of the transformed mesh (in the VOLUME's frame).
+    sign: "parity" (closed meshes) or "winding" (any oriented mesh: inside iff its generalised winding number exceeds 1 / 2)."""
     from . import ops
 
     trunc = float(params["trunc"])
     v, f = _mesh(mesh_to_volume_frame(vertices, params, pose), faces)
     grid = ops.TriangleGrid(v, f, cell=CELL_IN_VOXELS * float(max(params["vs"])) if cell is None else float(cell))
-    phi, open_rows = grid.voxelise(params["dims"], tuple(float(x) for x in params["vs"]), trunc, float(params["eta"]), out=out, mode=mode)
+    phi, open_rows = grid.voxelise(params["dims"], tuple(float(x) for x in params["vs"]), trunc, float(params["eta"]), out=out, mode=mode, sign=sign)
     return (phi, open_rows, grid) if return_grid else (phi, open_rows)

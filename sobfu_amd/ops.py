@@ -757,6 +757,35 @@ class TriangleGrid:
             check(rc, "mesh_grid_build")
             break
         self.references = refs.value
+        self._boundary, self.boundary_edges = None, None
+
+    @property
+    def boundary(self):
+        """The mesh's boundary chain on the device, computed once: (B, 2, 4) float32, per edge u = (x, y, z, k) and v = (x, y, z, 0) with
+        k = (#triangles that run u -> v) - (#that run v -> u) != 0, sorted by the vertex indices (u < v).  Empty for a closed,
+        consistently oriented mesh.  boundary_edges: the (B, 3) int32 numpy rows (u, v, k)."""
+        if self._boundary is None:
+            faces = np.ascontiguousarray(self.faces.detach().cpu().numpy(), np.int32)
+            L, count = _lib.lib(), C.c_int(0)
+            fp = faces.ctypes.data_as(C.POINTER(C.c_int)) if self.n_triangles else None
+            check(L.sobfu_hip_mesh_boundary(fp, C.c_int(self.n_triangles), C.c_int(self.n_vertices), None, C.c_int(0), C.byref(count)), "mesh_boundary")
+            edges = np.zeros((count.value, 3), np.int32)
+            if count.value:
+                check(L.sobfu_hip_mesh_boundary(fp, C.c_int(self.n_triangles), C.c_int(self.n_vertices), edges.ctypes.data_as(C.POINTER(C.c_int)),
+                                                C.c_int(count.value), C.byref(count)), "mesh_boundary")
+            self.boundary_edges = edges
+            dev = self.vertices.device
+            b = torch.zeros((len(edges), 2, 4), dtype=torch.float32, device=dev)
+            if len(edges):
+                idx = torch.from_numpy(edges.astype(np.int64)).to(dev)
+                b[:, 0, :3], b[:, 1, :3] = self.vertices[idx[:, 0], :3], self.vertices[idx[:, 1], :3]
+                b[:, 0, 3] = idx[:, 2].to(torch.float32)
+            self._boundary = b.contiguous()
+        return self._boundary
+
+    def _boundary_args(self):
+        b = self.boundary
+        return (_ptr(b) if b.shape[0] else None, C.c_int(int(b.shape[0])))
 
     def _mesh(self):
         return (_ptr(self.vertices) if self.n_vertices else None, C.c_int(self.n_vertices),
@@ -908,17 +937,36 @@ class TriangleGrid:
         return given
 
     # ---- this mesh, closed, as a signed TSDF volume and an inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip) ----
-    def voxelise(self, dims, vs, trunc, eta, out=None, mode="auto"):
+    def voxelise(self, dims, vs, trunc, eta, out=None, mode="auto", sign="parity", winding_out=None):
         """This mesh, its vertices in the volume's frame, as a TSDF volume of dims = (X, Y, Z) voxels of size vs (3,): voxel (i, j, k) has
         its centre at i vs + vs / 2 per axis; tsdf = clamp(s / trunc, -1, 1) with s the exact distance to the mesh, negative inside;
         weight = s > -eta -> (volume (Z, Y, X, 2) float32, open_rows (1,) int32 GPU tensor: the rows along x that cross the mesh an odd
-        number of times -- 0 for a closed mesh).  out: a volume to write into.  mode never changes a bit.  X <= 512."""
+        number of times -- 0 for a closed mesh).  out: a volume to write into.  mode never changes a bit.  X <= 512.
+        sign: "parity" (a closed mesh: inside iff the row crosses it an odd number of times beyond the voxel) or "winding" (any oriented
+        mesh, open ones included: inside iff the generalised winding number exceeds 1 / 2; open_rows is then only information).
+        winding_out (sign="winding"): a (Z, Y, X) float32 tensor that receives the winding number at every voxel centre."""
+        if sign not in ("parity", "winding"):
+            raise ValueError(f"unknown sign {sign!r}")
+        if winding_out is not None and sign != "winding":
+            raise ValueError("winding_out needs sign='winding'")
         mode = self._mode(mode)
         X, Y, Z = (int(d) for d in dims)
         dev = self.vertices.device
         vol = torch.empty((Z, Y, X, 2), dtype=torch.float32, device=dev) if out is None else out
         if tuple(vol.shape) != (Z, Y, X, 2):
             raise ValueError(f"the volume must be {(Z, Y, X, 2)}, got {tuple(vol.shape)}")
+        if sign == "winding":
+            if winding_out is not None and tuple(winding_out.shape) != (Z, Y, X):
+                raise ValueError(f"winding_out must be {(Z, Y, X)}, got {tuple(winding_out.shape)}")
+            nbytes = int(_lib.lib().sobfu_hip_mesh_voxelise_winding_workspace_bytes(C.c_int(X), C.c_int(Y), C.c_int(Z)))
+            if nbytes == 0:
+                raise ValueError(f"cannot voxelise into {X} x {Y} x {Z} voxels (X <= 512)")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            open_rows = torch.empty(1, dtype=torch.int32, device=dev)
+            check(_lib.lib().sobfu_hip_mesh_voxelise_winding(*self._target(), *self._boundary_args(), _ptr(vol), C.c_int(X), C.c_int(Y), C.c_int(Z),
+                                                             _vs3(vs), _f(trunc), _f(eta), mode, *_ws(ws), _ptr(open_rows, torch.int32),
+                                                             None if winding_out is None else _ptr(winding_out), _stream()), "mesh_voxelise_winding")
+            return vol, open_rows
         nbytes = int(_lib.lib().sobfu_hip_mesh_voxelise_workspace_bytes(C.c_int(X), C.c_int(Y), C.c_int(Z)))
         if nbytes == 0:
             raise ValueError(f"cannot voxelise into {X} x {Y} x {Z} voxels (X <= 512)")
@@ -939,6 +987,21 @@ class TriangleGrid:
             check(_lib.lib().sobfu_hip_mesh_inside(*self._target(), _point_list(points, "points"), C.c_int(n), _ptr(ins, torch.uint8),
                                                    _ptr(opn, torch.uint8), mode, _stream()), "mesh_inside")
         return ins, opn
+
+    def winding(self, points, mode="boundary", walk="auto"):
+        """(n, 4) float32 points -> (n,) float32 generalised winding numbers: 1 inside and 0 outside a closed, outward-oriented mesh,
+        smooth across the holes of an open one; inside iff > 1 / 2.  mode "boundary": signed row crossings + the solid angles of the
+        strips behind the boundary edges (the definition on seam points); "sum": the definition, every triangle's solid angle.
+        walk "auto" | "grid" | "brute": the crossing walk, never changes a bit."""
+        if mode not in ("boundary", "sum"):
+            raise ValueError(f"unknown mode {mode!r}")
+        walk = self._mode(walk)
+        n = int(points.shape[0])
+        w = torch.empty(n, dtype=torch.float32, device=points.device)
+        if n:
+            check(_lib.lib().sobfu_hip_mesh_winding(*self._target(), *self._boundary_args(), _point_list(points, "points"), C.c_int(n), _ptr(w),
+                                                    C.c_int(0 if mode == "boundary" else 1), walk, _stream()), "mesh_winding")
+        return w
 
     def unresolved(self):
         """how many points of the last query hit the ring cap and were finished by brute force (synchronises)"""
