@@ -382,25 +382,20 @@ public:
     int voxelise(float* d_vol, const int dims[3], const float vs[3], float trunc, float eta, int mode = SOBFU_MESH_DISTANCE_AUTO, int sign = kSignParity,
                  float* d_winding = nullptr) {
         if (!built_) kfusion::cuda::error("TriangleGrid::voxelise without a built grid", __FILE__, __LINE__);
-        if (sign == kSignWinding) {
-            const size_t wbytes = sobfu_hip_mesh_voxelise_winding_workspace_bytes(dims[0], dims[1], dims[2]);
-            if (wbytes == 0) kfusion::cuda::error("TriangleGrid::voxelise: at most 512 voxels along x", __FILE__, __LINE__);
-            boundary();
-            kfusion::cuda::DeviceArray<unsigned char> wws(wbytes);
-            kfusion::cuda::DeviceArray<int> wopen(1);
-            sobfuSafeCall(with_target(sobfu_hip_mesh_voxelise_winding, nb_ ? (const float*) boundary_.ptr() : nullptr, nb_, d_vol, dims[0], dims[1], dims[2], vs,
-                                      trunc, eta, mode, wws.ptr(), wws.size(), wopen.ptr(), d_winding, nullptr));
-            std::vector<int> wn;
-            wopen.download(wn);
-            return wn[0];
-        }
-        if (sign != kSignParity || d_winding) kfusion::cuda::error("TriangleGrid::voxelise: unknown sign, or d_winding without kSignWinding", __FILE__, __LINE__);
-        const size_t bytes = sobfu_hip_mesh_voxelise_workspace_bytes(dims[0], dims[1], dims[2]);
+        const bool winding = sign == kSignWinding;
+        if (!winding && (sign != kSignParity || d_winding))
+            kfusion::cuda::error("TriangleGrid::voxelise: unknown sign, or d_winding without kSignWinding", __FILE__, __LINE__);
+        const size_t bytes = (winding ? sobfu_hip_mesh_voxelise_winding_workspace_bytes : sobfu_hip_mesh_voxelise_workspace_bytes)(dims[0], dims[1], dims[2]);
         if (bytes == 0) kfusion::cuda::error("TriangleGrid::voxelise: at most 512 voxels along x", __FILE__, __LINE__);
+        if (winding) boundary();
         kfusion::cuda::DeviceArray<unsigned char> ws(bytes);
         kfusion::cuda::DeviceArray<int> open_rows(1);
-        sobfuSafeCall(with_target(sobfu_hip_mesh_voxelise, d_vol, dims[0], dims[1], dims[2], vs, trunc, eta, mode, ws.ptr(), ws.size(), open_rows.ptr(),
-                                  nullptr));
+        // the winding entry point takes the boundary behind the target and d_winding ahead of the stream
+        if (winding)
+            sobfuSafeCall(with_target(sobfu_hip_mesh_voxelise_winding, nb_ ? (const float*) boundary_.ptr() : nullptr, nb_, d_vol, dims[0], dims[1], dims[2], vs, trunc,
+                                      eta, mode, ws.ptr(), ws.size(), open_rows.ptr(), d_winding, nullptr));
+        else
+            sobfuSafeCall(with_target(sobfu_hip_mesh_voxelise, d_vol, dims[0], dims[1], dims[2], vs, trunc, eta, mode, ws.ptr(), ws.size(), open_rows.ptr(), nullptr));
         std::vector<int> n;
         open_rows.download(n);
         return n[0];

@@ -2,14 +2,10 @@
 // has no such step; the rules are this project's, and tests/mesh_parity_reference.py restates them (the row-crossing rule operation by
 // operation: sobfu_mesh_parity.hpp; the distance: sobfu_mesh_distance.hpp).  The kernels only read the grid that
 // sobfu_hip_mesh_grid_build made for the distance query; the grid's view, the mesh record, the corner loads, the cell range the rows and
-// points ask for, the margin, the mode and the check of the leading arguments are shared (sobfu_mesh.hpp).  Vertices are in the volume's frame.
+// points ask for, the margin, the mode and the check of the leading arguments are shared (sobfu_mesh.hpp), and so are the rows: the walk
+// of a row's cell column, the voxel centres and the format of the sign bits (sobfu_mesh_rows.hpp).  Vertices are in the volume's frame.
 //
 //   centres  voxel i of an axis has its centre at i vs + vs / 2, in fp32
-//   sign     a row is the line through (., py, pz) along +x.  A crossing triangle's box contains (py, pz) -- the fp32 translation of the
-//            rule keeps signs -- so it is referenced from the row's one cell column (cell_of(py), cell_of(pz)), whose cells cx = 0 ..
-//            dx - 1 hold one contiguous range of references.  A triangle referenced from several cells of the column counts only in
-//            the first cell in x of its cell range (cells_of, which the build bins by).  The crossing rule is exact, so the count depends
-//            neither on the cells, nor on the order of the references, nor on grid versus brute force (every triangle once).
 //   rows     one wave per volume row (j, k), up to X = 512: lanes stride over the column's references; each crossing flips, in an LDS mask,
 //            the bit of the first voxel whose centre is not below X (bit X: beyond the last voxel).  XOR is order-independent.  Voxel i
 //            is inside iff the flips at bits above i are odd in number: a suffix parity, written as ceil(X / 32) words per row.  A
@@ -31,17 +27,14 @@
 //            not read.
 #include "sobfu_hip.h"
 #include "sobfu_device.hpp"
-#include "sobfu_mesh.hpp"
-#include "sobfu_mesh_parity.hpp"
+#include "sobfu_mesh_rows.hpp"
 
 using namespace sobfu_hip;
 
 namespace {
 
-constexpr int kMaxX      = 512;
 constexpr int kMaskWords = kMaxX / 32 + 1;  // bit X of a row: crossings beyond the last voxel
-constexpr int kBrick     = 8;
-constexpr int kStage     = 1024;  // triangles staged in LDS at a time (48 B each)
+constexpr int kStage     = 1024;            // triangles staged in LDS at a time (48 B each)
 
 struct VoxArgs {
     Mesh mesh;
@@ -55,30 +48,6 @@ struct VoxArgs {
     int* open_rows;
 };
 
-SOBFU_DEV float centre(int i, float vs) { return (float) i * vs + vs / 2.f; }
-
-// the first i in [0, n] whose centre is not below X (n: none is)
-SOBFU_DEV int first_not_below(double X, float vs, int n) {
-    const double e = ceil((X - (double) (vs / 2.f)) / (double) vs);
-    int i = (int) fmax(fmin(e, (double) n), 0.0);
-    while (i > 0 && (double) centre(i - 1, vs) >= X) --i;
-    while (i < n && (double) centre(i, vs) < X) ++i;
-    return i;
-}
-
-SOBFU_DEV Crossing cross_triangle(const Corners& t, float py, float pz) { return row_crossing(p3(t.a), p3(t.b), p3(t.c), py, pz); }
-
-// the cell c in [c0, c1] of a row of cells (start: that row's entries) whose references hold position k: the largest c with start[c] <= k
-SOBFU_DEV int cell_of_reference(const int* __restrict__ start, int c0, int c1, int k) {
-    int lo = c0, hi = c1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (start[mid] <= k) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(256) row_parity_kernel(Grid g, VoxArgs a) {
     __shared__ unsigned mask[4][kMaskWords];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -88,26 +57,10 @@ __global__ void __launch_bounds__(256) row_parity_kernel(Grid g, VoxArgs a) {
     __syncthreads();
     if (valid && g.hdr[kHdrBuilt] == 1) {
         const float py = centre((int) (row % a.d.y), a.vsy), pz = centre((int) (row / a.d.y), a.vsz);
-        if (a.brute) {
-            for (int t = lane; t < a.mesh.n_triangles; t += 64) {
-                const Crossing c = cross_triangle(corners_of(a.mesh, t), py, pz);
-                if (c.hit) {
-                    const int i = first_not_below(c.X, a.vsx, a.d.x);
-                    atomicXor(&mask[wave][i >> 5], 1u << (i & 31));
-                }
-            }
-        } else {
-            const int* start = g.start + g.dx * (cell_of(py, g.oy, g.h, g.dy) + g.dy * cell_of(pz, g.oz, g.h, g.dz));
-            const int k1 = start[g.dx];
-            for (int k = start[0] + lane; k < k1; k += 64) {
-                const Corners t  = corners_of(a.mesh, g.refs[k]);
-                const Crossing c = cross_triangle(t, py, pz);
-                if (c.hit && cells_of(g, t).x0 == cell_of_reference(start, 0, g.dx - 1, k)) {
-                    const int i = first_not_below(c.X, a.vsx, a.d.x);
-                    atomicXor(&mask[wave][i >> 5], 1u << (i & 31));
-                }
-            }
-        }
+        walk_row_wave(g, a.mesh, a.brute, py, pz, lane, [&](const SignedCrossing& c) {
+            const int i = first_not_below(c.X, a.vsx, a.d.x);
+            atomicXor(&mask[wave][i >> 5], 1u << (i & 31));
+        });
     }
     __syncthreads();
     if (!valid) return;
@@ -144,20 +97,7 @@ __global__ void __launch_bounds__(256) mesh_inside_kernel(Grid g, InsideArgs a) 
     if (g.hdr[kHdrBuilt] == 1) {
         const float4 p  = a.points[i];
         const double px = (double) p.x;
-        if (a.brute) {
-            for (int t = 0; t < a.mesh.n_triangles; ++t) {
-                const Crossing c = cross_triangle(corners_of(a.mesh, t), p.y, p.z);
-                if (c.hit) ++total, beyond += c.X > px ? 1u : 0u;
-            }
-        } else {
-            const int* start = g.start + g.dx * (cell_of(p.y, g.oy, g.h, g.dy) + g.dy * cell_of(p.z, g.oz, g.h, g.dz));
-            for (int cx = 0; cx < g.dx; ++cx)
-                for (int k = start[cx]; k < start[cx + 1]; ++k) {
-                    const Corners t  = corners_of(a.mesh, g.refs[k]);
-                    const Crossing c = cross_triangle(t, p.y, p.z);
-                    if (c.hit && cells_of(g, t).x0 == cx) ++total, beyond += c.X > px ? 1u : 0u;
-                }
-        }
+        walk_row_lane(g, a.mesh, a.brute, p.y, p.z, [&](const SignedCrossing& c) { ++total, beyond += c.X > px ? 1u : 0u; });
     }
     a.inside[i] = (unsigned char) (beyond & 1u);
     a.open[i]   = (unsigned char) (total & 1u);
@@ -270,15 +210,11 @@ __global__ void __launch_bounds__(512) brick_kernel(Grid g, VoxArgs a) {
     a.vol[vidx(a.d, x, y, z)] = pack_tsdf(s, a.trunc, s > -a.eta ? 1.f : 0.f);
 }
 
-int words_per_row(int X) { return (X + 31) / 32; }
-size_t bits_bytes(int X, int Y, int Z) { return ((size_t) Y * Z * words_per_row(X) * sizeof(unsigned) + 15) / 16 * 16; }
-
 }  // namespace
 
 namespace sobfu_hip {
 
-// The distance pass alone, over sign bits that another unit wrote into d_bits in row_parity_kernel's format (mesh_winding_kernels.hip).
-// The arguments are sobfu_hip_mesh_voxelise's and have been checked there.
+// declared, with what it takes, in sobfu_mesh_rows.hpp
 int mesh_voxel_bricks(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles,
                       const float origin[3], float h, const int dims[3], float* d_vol, int X, int Y, int Z, const float voxel_size[3], float trunc,
                       float eta, int mode, void* d_bits, int* d_open_rows, void* stream) {
@@ -296,7 +232,7 @@ int mesh_voxel_bricks(void* d_grid_workspace, size_t grid_workspace_bytes, const
 extern "C" {
 
 size_t sobfu_hip_mesh_voxelise_workspace_bytes(int X, int Y, int Z) {
-    if (X < 1 || X > kMaxX || Y < 1 || Z < 1 || (long long) Y * Z > INT_MAX) return 0;
+    if (!rows_ok(X, Y, Z) || (long long) Y * Z > INT_MAX) return 0;
     return bits_bytes(X, Y, Z);
 }
 
@@ -306,20 +242,16 @@ int sobfu_hip_mesh_voxelise(void* d_grid_workspace, size_t grid_workspace_bytes,
                             int* d_open_rows, void* stream) {
     MeshTarget tg;
     SOBFU_CHECK_ARGS(mesh_target(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
-    SOBFU_CHECK_ARGS(d_vol && aligned(d_vol, 0, 8) && volume_ok(X, Y, Z, kGridZ * kBrick) && X <= kMaxX && (long long) Y * Z <= INT_MAX);
-    SOBFU_CHECK_ARGS(voxel_size && positive_finite(voxel_size[0]) && positive_finite(voxel_size[1]) && positive_finite(voxel_size[2]) &&
-                     positive_finite(trunc) && std::isfinite(eta) && mode_ok(mode));
-    SOBFU_CHECK_ARGS(d_workspace && aligned(d_workspace, 0, 16) && workspace_bytes >= bits_bytes(X, Y, Z) && d_open_rows && aligned(d_open_rows, 0, 4));
+    SOBFU_CHECK_ARGS(rows_volume_ok(d_vol, X, Y, Z, voxel_size, trunc, eta, mode, d_workspace, workspace_bytes, bits_bytes(X, Y, Z), d_open_rows) &&
+                     (long long) Y * Z <= INT_MAX);
     hipStream_t st = (hipStream_t) stream;
-    const Grid& g  = tg.grid;
     const VoxArgs a{tg.mesh, is_brute(mode, n_triangles), {X, Y, Z}, voxel_size[0], voxel_size[1], voxel_size[2], trunc, eta, tg.box_l, (float2*) d_vol,
                     (unsigned*) d_workspace, words_per_row(X), d_open_rows};
     SOBFU_HIP_TRY(hipMemsetAsync(d_open_rows, 0, sizeof(int), st));
-    hipLaunchKernelGGL(row_parity_kernel, dim3((unsigned) (((long long) Y * Z + 3) / 4)), dim3(256), 0, st, g, a);
+    hipLaunchKernelGGL(row_parity_kernel, dim3((unsigned) (((long long) Y * Z + 3) / 4)), dim3(256), 0, st, tg.grid, a);
     SOBFU_HIP_TRY(hipGetLastError());
-    const dim3 bricks((unsigned) ((X + kBrick - 1) / kBrick), (unsigned) ((Y + kBrick - 1) / kBrick), (unsigned) ((Z + kBrick - 1) / kBrick));
-    hipLaunchKernelGGL(brick_kernel, bricks, dim3(512), 0, st, g, a);
-    return (int) hipGetLastError();
+    return mesh_voxel_bricks(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, d_vol, X, Y, Z,
+                             voxel_size, trunc, eta, mode, d_workspace, d_open_rows, stream);
 }
 
 int sobfu_hip_mesh_inside(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces,

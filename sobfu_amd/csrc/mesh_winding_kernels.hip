@@ -1,9 +1,9 @@
 // Generalised winding numbers of open, doubled or inconsistently oriented triangle meshes on gfx950, and the sign bits of their TSDF volumes
 // (DESIGN.md 4.14).  The reference has no such step; the rule is this project's (sobfu_mesh_winding.hpp, restated by
 // tests/mesh_winding_reference.py): w(p) = N(p) + the solid angles of the strips from the boundary edges to infinity along -x, over 4 pi.
-// The kernels read the grid of sobfu_hip_mesh_grid_build and walk it exactly as mesh_voxel_kernels.hip does (the row's one cell column,
-// every triangle counted in the first cell in x of its cell range); the boundary list is the caller's (sobfu_hip_mesh_boundary: two float4
-// per edge, u = (x, y, z, k) and v = (x, y, z, .)).
+// The kernels read the grid of sobfu_hip_mesh_grid_build through the walk that mesh_voxel_kernels.hip uses (sobfu_mesh_rows.hpp: the
+// row's one cell column, every triangle counted in the first cell in x of its cell range); the boundary list is the caller's
+// (sobfu_hip_mesh_boundary: two float4 per edge, u = (x, y, z, k) and v = (x, y, z, .)).
 //
 //   rows     one wave per volume row (j, k), up to X = 512: lanes stride over the column's references; each crossing adds its sign, an
 //            LDS integer atomic, to the counter of the first voxel whose centre is not below X (counter X: beyond the last voxel).  Integer
@@ -28,51 +28,19 @@
 
 #include "sobfu_hip.h"
 #include "sobfu_device.hpp"
-#include "sobfu_mesh.hpp"
 #include "sobfu_mesh_boundary.hpp"
+#include "sobfu_mesh_rows.hpp"
 #include "sobfu_mesh_winding.hpp"
 
 using namespace sobfu_hip;
 
-namespace sobfu_hip {
-// mesh_voxel_kernels.hip: the distance pass alone, over sign bits written here
-int mesh_voxel_bricks(void* d_grid_workspace, size_t grid_workspace_bytes, const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles,
-                      const float origin[3], float h, const int dims[3], float* d_vol, int X, int Y, int Z, const float voxel_size[3], float trunc,
-                      float eta, int mode, void* d_bits, int* d_open_rows, void* stream);
-}  // namespace sobfu_hip
-
 namespace {
 
-constexpr int kMaxX       = 512;
 constexpr int kPerLane    = 9;               // counters a lane sums: 64 x 9 = 576 >= kMaxX + 1
 constexpr int kCounters   = 64 * kPerLane;
 constexpr int kVoxPerLane = kMaxX / 64;      // voxels of a row a lane accumulates
 constexpr int kEdgeStage  = 64;              // boundary edges a wave stages at a time (56 B each)
 constexpr int kSumBlocks  = 1024;            // workgroups of the seam pass: they stride over the list
-
-SOBFU_DEV float centre(int i, float vs) { return (float) i * vs + vs / 2.f; }
-
-// the first i in [0, n] whose centre is not below X (n: none is): mesh_voxel_kernels.hip's
-SOBFU_DEV int first_not_below(double X, float vs, int n) {
-    const double e = ceil((X - (double) (vs / 2.f)) / (double) vs);
-    int i = (int) fmax(fmin(e, (double) n), 0.0);
-    while (i > 0 && (double) centre(i - 1, vs) >= X) --i;
-    while (i < n && (double) centre(i, vs) < X) ++i;
-    return i;
-}
-
-SOBFU_DEV SignedCrossing cross_triangle(const Corners& t, float py, float pz) { return signed_row_crossing(p3(t.a), p3(t.b), p3(t.c), py, pz); }
-
-// the cell c in [c0, c1] of a row of cells (start: that row's entries) whose references hold position k: the largest c with start[c] <= k
-SOBFU_DEV int cell_of_reference(const int* __restrict__ start, int c0, int c1, int k) {
-    int lo = c0, hi = c1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (start[mid] <= k) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 struct RowArgs {
     Mesh mesh;
@@ -103,23 +71,8 @@ __global__ void __launch_bounds__(256) row_winding_kernel(Grid g, RowArgs a) {
     __syncthreads();
     const bool built = g.hdr[kHdrBuilt] == 1 && a.mesh.n_triangles > 0;  // uniform
     const float py = centre((int) (row % a.d.y), a.vsy), pz = centre((int) (row / a.d.y), a.vsz);
-    if (valid && built) {
-        if (a.brute) {
-            for (int t = lane; t < a.mesh.n_triangles; t += 64) {
-                const SignedCrossing c = cross_triangle(corners_of(a.mesh, t), py, pz);
-                if (c.sign != 0) atomicAdd(&cnt[wave][first_not_below(c.X, a.vsx, a.d.x)], c.sign);
-            }
-        } else {
-            const int* start = g.start + g.dx * (cell_of(py, g.oy, g.h, g.dy) + g.dy * cell_of(pz, g.oz, g.h, g.dz));
-            const int k1 = start[g.dx];
-            for (int k = start[0] + lane; k < k1; k += 64) {
-                const Corners t        = corners_of(a.mesh, g.refs[k]);
-                const SignedCrossing c = cross_triangle(t, py, pz);
-                if (c.sign != 0 && cells_of(g, t).x0 == cell_of_reference(start, 0, g.dx - 1, k))
-                    atomicAdd(&cnt[wave][first_not_below(c.X, a.vsx, a.d.x)], c.sign);
-            }
-        }
-    }
+    if (valid && built)
+        walk_row_wave(g, a.mesh, a.brute, py, pz, lane, [&](const SignedCrossing& c) { atomicAdd(&cnt[wave][first_not_below(c.X, a.vsx, a.d.x)], c.sign); });
     __syncthreads();  // every addition has landed: from here on the counters are only read and rewritten by their own lane
     {
         int v[kPerLane], own = 0;
@@ -257,7 +210,8 @@ struct PointArgs {
     float* w;
 };
 
-// Every loop stays rolled: left to the unroller this kernel took 314 VGPRs and spilled two (tests/test_no_scratch.py); rolled, 84.
+// Every loop stays rolled, the walk's (sobfu_mesh_rows.hpp) included: left to the unroller this kernel took 314 VGPRs and spilled two
+// (tests/test_no_scratch.py); rolled, 84.
 __global__ void __launch_bounds__(256) mesh_winding_kernel(Grid g, PointArgs a) {
     __shared__ float4 s_u[256], s_v[256];
     const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
@@ -267,25 +221,10 @@ __global__ void __launch_bounds__(256) mesh_winding_kernel(Grid g, PointArgs a) 
     const P3 p{q.x, q.y, q.z};
     const double px = (double) p.x;
     int N = 0;
-    if (have && built) {
-        if (a.brute) {
-#pragma unroll 1
-            for (int t = 0; t < a.mesh.n_triangles; ++t) {
-                const SignedCrossing c = cross_triangle(corners_of(a.mesh, t), p.y, p.z);
-                if (c.sign != 0 && c.X > px) N += c.sign;
-            }
-        } else {
-            const int* start = g.start + g.dx * (cell_of(p.y, g.oy, g.h, g.dy) + g.dy * cell_of(p.z, g.oz, g.h, g.dz));
-#pragma unroll 1
-            for (int cx = 0; cx < g.dx; ++cx)
-#pragma unroll 1
-                for (int k = start[cx]; k < start[cx + 1]; ++k) {
-                    const Corners t        = corners_of(a.mesh, g.refs[k]);
-                    const SignedCrossing c = cross_triangle(t, p.y, p.z);
-                    if (c.sign != 0 && c.X > px && cells_of(g, t).x0 == cx) N += c.sign;
-                }
-        }
-    }
+    if (have && built)
+        walk_row_lane(g, a.mesh, a.brute, p.y, p.z, [&](const SignedCrossing& c) {
+            if (c.X > px) N += c.sign;
+        });
     double acc = 0.0;
     bool seam  = false;
     if (built)
@@ -314,9 +253,6 @@ __global__ void __launch_bounds__(256) mesh_winding_kernel(Grid g, PointArgs a) 
     a.w[i] = (float) w;
 }
 
-int words_per_row(int X) { return (X + 31) / 32; }
-size_t bits_bytes(int X, int Y, int Z) { return ((size_t) Y * Z * words_per_row(X) * sizeof(unsigned) + 15) / 16 * 16; }
-bool rows_ok(int X, int Y, int Z) { return X >= 1 && X <= kMaxX && Y >= 1 && Z >= 1 && (long long) X * Y * Z <= INT_MAX; }
 bool boundary_ok(const float* d_boundary, int n_boundary) { return n_boundary >= 0 && (n_boundary == 0 || d_boundary) && aligned(d_boundary, 0, 16); }
 
 }  // namespace
@@ -359,7 +295,7 @@ int sobfu_hip_mesh_winding(void* d_grid_workspace, size_t grid_workspace_bytes, 
 }
 
 size_t sobfu_hip_mesh_voxelise_winding_workspace_bytes(int X, int Y, int Z) {
-    if (!rows_ok(X, Y, Z)) return 0;
+    if (!rows_ok(X, Y, Z) || (long long) X * Y * Z > INT_MAX) return 0;
     return bits_bytes(X, Y, Z) + 16 + (size_t) X * Y * Z * sizeof(int);
 }
 
@@ -369,11 +305,9 @@ int sobfu_hip_mesh_voxelise_winding(void* d_grid_workspace, size_t grid_workspac
                                     size_t workspace_bytes, int* d_open_rows, float* d_winding, void* stream) {
     MeshTarget tg;
     SOBFU_CHECK_ARGS(mesh_target(d_grid_workspace, grid_workspace_bytes, d_vertices, n_vertices, d_faces, n_triangles, origin, h, dims, 0, &tg));
-    SOBFU_CHECK_ARGS(boundary_ok(d_boundary, n_boundary) && d_vol && aligned(d_vol, 0, 8) && rows_ok(X, Y, Z) && volume_ok(X, Y, Z, kGridZ * 8));
-    SOBFU_CHECK_ARGS(voxel_size && positive_finite(voxel_size[0]) && positive_finite(voxel_size[1]) && positive_finite(voxel_size[2]) &&
-                     positive_finite(trunc) && std::isfinite(eta) && mode_ok(mode) && aligned(d_winding, 0, 4));
-    SOBFU_CHECK_ARGS(d_workspace && aligned(d_workspace, 0, 16) && workspace_bytes >= sobfu_hip_mesh_voxelise_winding_workspace_bytes(X, Y, Z) && d_open_rows &&
-                     aligned(d_open_rows, 0, 4));
+    SOBFU_CHECK_ARGS(boundary_ok(d_boundary, n_boundary) && aligned(d_winding, 0, 4) && (long long) X * Y * Z <= INT_MAX &&
+                     rows_volume_ok(d_vol, X, Y, Z, voxel_size, trunc, eta, mode, d_workspace, workspace_bytes,
+                                    sobfu_hip_mesh_voxelise_winding_workspace_bytes(X, Y, Z), d_open_rows));
     hipStream_t st    = (hipStream_t) stream;
     char* ws          = (char*) d_workspace;
     int* seam_count   = (int*) (ws + bits_bytes(X, Y, Z));

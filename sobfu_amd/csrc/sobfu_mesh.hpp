@@ -3,7 +3,8 @@
 // (rows and points with winding numbers), mesh_align_kernels.hip.
 // The grid's workspace as the kernels see it, the mesh record and its corner loads, a triangle's cell range, the LDS staging loads of the
 // 256-lane brute-force loops, the margin, the mode, and the one check of the nine arguments every mesh entry point of the C ABI starts with.  The
-// plan (origin, cell edge, dims) is sobfu_mesh_grid.hpp's.  Internal linkage, no kernels: the scan is compiled where it is launched.
+// plan (origin, cell edge, dims) is sobfu_mesh_grid.hpp's.  What only the rows along +x share -- the crossing walk, the voxel centres, the
+// sign bits -- is sobfu_mesh_rows.hpp's, on top of this.  Internal linkage, no kernels: the scan is compiled where it is launched.
 #pragma once
 
 #include "sobfu_device.hpp"

@@ -13,7 +13,8 @@
 //               (+e, +e^2) in (y, z): E + e (Pz - Qz) + e^2 (Qy - Py), so the sign of Pz - Qz, else that of Qy - Py, else none (an edge
 //               without length: the triangle is no crossing).  Antisymmetric in (P, Q) and computed from the same values in both
 //               triangles of a shared edge
-//   crossing    the three signs are equal and det = (U + V) + W != 0 (a triangle seen edge-on never crosses)
+//   crossing    the three signs are equal and det = (U + V) + W != 0 (a triangle seen edge-on never crosses); sign = their common
+//               sign, 0 where the row does not cross
 //   position    X = ((U a.x + V b.x) + W c.x) / det in fp64, absolute
 //   inside      (x, py, pz) is inside iff the number of crossings with X > (double) x is odd
 //   open rows   a row whose total number of crossings is odd: the mesh is not closed there
@@ -23,8 +24,8 @@
 
 namespace sobfu_hip {
 
-struct Crossing {
-    bool hit;
+struct SignedCrossing {
+    int sign;  // +1 / -1: the common sign of the three edge functions; 0: no crossing
     double X;
 };
 
@@ -37,15 +38,16 @@ SOBFU_MD_FN int parity_sign(double e, float Py, float Pz, float Qy, float Qz) {
     return 0;
 }
 
-SOBFU_MD_FN Crossing row_crossing(const P3& a, const P3& b, const P3& c, float py, float pz) {
+// the one statement of the rule: the parity test counts the crossings (sign != 0), the winding number of sobfu_mesh_winding.hpp adds the signs
+SOBFU_MD_FN SignedCrossing signed_row_crossing(const P3& a, const P3& b, const P3& c, float py, float pz) {
     const float Ay = a.y - py, Az = a.z - pz, By = b.y - py, Bz = b.z - pz, Cy = c.y - py, Cz = c.z - pz;
     const double U = (double) By * (double) Cz - (double) Bz * (double) Cy;
     const double V = (double) Cy * (double) Az - (double) Cz * (double) Ay;
     const double W = (double) Ay * (double) Bz - (double) Az * (double) By;
     const int su = parity_sign(U, By, Bz, Cy, Cz), sv = parity_sign(V, Cy, Cz, Ay, Az), sw = parity_sign(W, Ay, Az, By, Bz);
     const double det = (U + V) + W;
-    if (su == 0 || su != sv || su != sw || !(det != 0.0)) return Crossing{false, 0.0};
-    return Crossing{true, ((U * (double) a.x + V * (double) b.x) + W * (double) c.x) / det};
+    if (su == 0 || su != sv || su != sw || !(det != 0.0)) return SignedCrossing{0, 0.0};
+    return SignedCrossing{su, ((U * (double) a.x + V * (double) b.x) + W * (double) c.x) / det};
 }
 
 }  // namespace sobfu_hip

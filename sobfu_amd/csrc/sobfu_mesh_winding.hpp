@@ -7,7 +7,7 @@
 // sign of its edge functions) and Omega_strip the solid angle of the strip.  tests/mesh_winding_reference.py restates all of it.  Plain
 // C++, no HIP types: a host compiler takes this header too (every TU is built with -ffp-contract=off).
 //
-//   crossing   signed_row_crossing: row_crossing's operations in row_crossing's order; sign = su where the row crosses, else 0
+//   crossing   signed_row_crossing of sobfu_mesh_parity.hpp, the one statement of the rule
 //   strip      a = u - p, b = v - p: y and z translated in fp32 exactly as the crossing rule translates them, x in fp64.
 //              W = a_y b_z - a_z b_y in fp64 (exact products, one rounding: the sign is exact); the strip's sign is -parity_sign(W, ...),
 //              never the sign of a rounded determinant, so the strip flips exactly where N jumps; an edge without projected length
@@ -28,22 +28,6 @@
 namespace sobfu_hip {
 
 constexpr double kFourPi = 12.566370614359172953850573533118;
-
-struct SignedCrossing {
-    int sign;  // +1 / -1: the common sign of the three edge functions; 0: no crossing
-    double X;
-};
-
-SOBFU_MD_FN SignedCrossing signed_row_crossing(const P3& a, const P3& b, const P3& c, float py, float pz) {
-    const float Ay = a.y - py, Az = a.z - pz, By = b.y - py, Bz = b.z - pz, Cy = c.y - py, Cz = c.z - pz;
-    const double U = (double) By * (double) Cz - (double) Bz * (double) Cy;
-    const double V = (double) Cy * (double) Az - (double) Cz * (double) Ay;
-    const double W = (double) Ay * (double) Bz - (double) Az * (double) By;
-    const int su = parity_sign(U, By, Bz, Cy, Cz), sv = parity_sign(V, Cy, Cz, Ay, Az), sw = parity_sign(W, Ay, Az, By, Bz);
-    const double det = (U + V) + W;
-    if (su == 0 || su != sv || su != sw || !(det != 0.0)) return SignedCrossing{0, 0.0};
-    return SignedCrossing{su, ((U * (double) a.x + V * (double) b.x) + W * (double) c.x) / det};
-}
 
 // what the boundary edge u -> v is to the row (., py, pz)
 struct StripRow {

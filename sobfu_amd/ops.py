@@ -955,25 +955,23 @@ class TriangleGrid:
         vol = torch.empty((Z, Y, X, 2), dtype=torch.float32, device=dev) if out is None else out
         if tuple(vol.shape) != (Z, Y, X, 2):
             raise ValueError(f"the volume must be {(Z, Y, X, 2)}, got {tuple(vol.shape)}")
+        if winding_out is not None and tuple(winding_out.shape) != (Z, Y, X):
+            raise ValueError(f"winding_out must be {(Z, Y, X)}, got {tuple(winding_out.shape)}")
+        L = _lib.lib()
+        # one path; the winding entry point takes the boundary behind the target and winding_out ahead of the stream
         if sign == "winding":
-            if winding_out is not None and tuple(winding_out.shape) != (Z, Y, X):
-                raise ValueError(f"winding_out must be {(Z, Y, X)}, got {tuple(winding_out.shape)}")
-            nbytes = int(_lib.lib().sobfu_hip_mesh_voxelise_winding_workspace_bytes(C.c_int(X), C.c_int(Y), C.c_int(Z)))
-            if nbytes == 0:
-                raise ValueError(f"cannot voxelise into {X} x {Y} x {Z} voxels (X <= 512)")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            open_rows = torch.empty(1, dtype=torch.int32, device=dev)
-            check(_lib.lib().sobfu_hip_mesh_voxelise_winding(*self._target(), *self._boundary_args(), _ptr(vol), C.c_int(X), C.c_int(Y), C.c_int(Z),
-                                                             _vs3(vs), _f(trunc), _f(eta), mode, *_ws(ws), _ptr(open_rows, torch.int32),
-                                                             None if winding_out is None else _ptr(winding_out), _stream()), "mesh_voxelise_winding")
-            return vol, open_rows
-        nbytes = int(_lib.lib().sobfu_hip_mesh_voxelise_workspace_bytes(C.c_int(X), C.c_int(Y), C.c_int(Z)))
+            name, size, fn = "mesh_voxelise_winding", L.sobfu_hip_mesh_voxelise_winding_workspace_bytes, L.sobfu_hip_mesh_voxelise_winding
+            boundary, extra = self._boundary_args, (None if winding_out is None else _ptr(winding_out),)
+        else:
+            name, size, fn = "mesh_voxelise", L.sobfu_hip_mesh_voxelise_workspace_bytes, L.sobfu_hip_mesh_voxelise
+            boundary, extra = tuple, ()
+        nbytes = int(size(C.c_int(X), C.c_int(Y), C.c_int(Z)))
         if nbytes == 0:
             raise ValueError(f"cannot voxelise into {X} x {Y} x {Z} voxels (X <= 512)")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         open_rows = torch.empty(1, dtype=torch.int32, device=dev)
-        check(_lib.lib().sobfu_hip_mesh_voxelise(*self._target(), _ptr(vol), C.c_int(X), C.c_int(Y), C.c_int(Z), _vs3(vs), _f(trunc), _f(eta), mode,
-                                                 *_ws(ws), _ptr(open_rows, torch.int32), _stream()), "mesh_voxelise")
+        check(fn(*self._target(), *boundary(), _ptr(vol), C.c_int(X), C.c_int(Y), C.c_int(Z), _vs3(vs), _f(trunc), _f(eta), mode, *_ws(ws),
+                 _ptr(open_rows, torch.int32), *extra, _stream()), name)
         return vol, open_rows
 
     def inside(self, points, mode="auto"):

@@ -27,9 +27,10 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < (size_t) n; ++i)
         for (size_t k = 0; k < (size_t) T; ++k) {
             const float* c = &tris[9 * k];
-            const sobfu_hip::Crossing x = sobfu_hip::row_crossing(P3{c[0], c[1], c[2]}, P3{c[3], c[4], c[5]}, P3{c[6], c[7], c[8]}, rows[2 * i], rows[2 * i + 1]);
-            hit[i * T + k] = x.hit ? 1 : 0;
-            X[i * T + k]   = x.hit ? x.X : 0.0;
+            const sobfu_hip::SignedCrossing x =
+                sobfu_hip::signed_row_crossing(P3{c[0], c[1], c[2]}, P3{c[3], c[4], c[5]}, P3{c[6], c[7], c[8]}, rows[2 * i], rows[2 * i + 1]);
+            hit[i * T + k] = x.sign != 0 ? 1 : 0;  // a crossing is sign != 0
+            X[i * T + k]   = x.sign != 0 ? x.X : 0.0;
         }
     f = std::fopen(argv[2], "wb");
     if (!f) return 2;

@@ -1,5 +1,5 @@
-"""numpy restatement of the row-crossing rule of sobfu_amd/csrc/sobfu_mesh_parity.hpp (operation by operation: the translation in float32,
-the edge functions, det and X in float64) and of what sobfu_amd/csrc/mesh_voxel_kernels.hip computes with it by brute force: the inside
+"""numpy restatement of the row-crossing rule of sobfu_amd/csrc/sobfu_mesh_parity.hpp (signed_crossings, operation by operation: the
+translation in float32, the edge functions, det and X in float64) and of what sobfu_amd/csrc/mesh_voxel_kernels.hip computes with it by brute force: the inside
 and open flags of a point list, and the signed TSDF volume of a closed mesh (voxel centres, sign bits, the exact minimum distance of
 tests/mesh_distance_reference.py, pack_tsdf)."""
 import numpy as np
@@ -23,8 +23,9 @@ def corners(vertices, faces):
     return v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
 
 
-def crossings(rows, vertices, faces):
-    """rows (n, 2) float32 (py, pz) -> hit (n, T) bool, X (n, T) float64 (0 where there is no crossing)"""
+def signed_crossings(rows, vertices, faces):
+    """rows (n, 2) float32 (py, pz) -> s (n, T) int8 (the common sign of the edge functions where the row crosses, else 0), X (n, T)
+    float64 (0 where there is no crossing): signed_row_crossing's operations in its order, the one statement of the rule in numpy"""
     a, b, c = corners(vertices, faces)
     r = np.asarray(rows, np.float32).reshape(-1, 2)
     py, pz = r[:, 0:1], r[:, 1:2]
@@ -40,7 +41,13 @@ def crossings(rows, vertices, faces):
         X = np.zeros_like(det)
         num = (U * a[None, :, 0].astype(D) + V * b[None, :, 0].astype(D)) + W * c[None, :, 0].astype(D)
         np.divide(num, det, out=X, where=hit)
-    return hit, X
+    return np.where(hit, su, 0).astype(np.int8), X
+
+
+def crossings(rows, vertices, faces):
+    """rows (n, 2) float32 (py, pz) -> hit (n, T) bool, X (n, T) float64 (0 where there is no crossing): a crossing is sign != 0"""
+    s, X = signed_crossings(rows, vertices, faces)
+    return s != 0, X
 
 
 def inside(points, vertices, faces, chunk=512):

@@ -1,5 +1,5 @@
 """numpy restatement of the generalised winding number of sobfu_amd/csrc/sobfu_mesh_winding.hpp and sobfu_mesh_boundary.hpp (DESIGN.md
-4.14): the signed row crossings (the operations of tests/mesh_parity_reference.py, with the common sign), the boundary chain of an indexed
+4.14): the signed row crossings (tests/mesh_parity_reference.py states them), the boundary chain of an indexed
 mesh, the solid angle of the strip from a boundary edge to infinity along -x, van Oosterom and Strackee's solid angle of a triangle, the
 seam predicate, and the two ways to the winding number: the definition (every triangle's solid angle) and the boundary formula
 (crossings beyond the point + strips, the definition on seams).  Everything is float64 but the translation in y and z, which is the
@@ -12,24 +12,7 @@ F, D = np.float32, np.float64
 FOUR_PI = 4.0 * np.pi
 
 
-def signed_crossings(rows, vertices, faces):
-    """rows (n, 2) float32 (py, pz) -> s (n, T) int8 (the common sign of the edge functions where the row crosses, else 0), X (n, T)
-    float64 (0 where there is no crossing): row_crossing's operations in its order"""
-    a, b, c = MP.corners(vertices, faces)
-    r = np.asarray(rows, F).reshape(-1, 2)
-    py, pz = r[:, 0:1], r[:, 1:2]
-    Ay, Az, By, Bz, Cy, Cz = (((x[None, :, k] - p).astype(F)) for x in (a, b, c) for k, p in ((1, py), (2, pz)))
-    with np.errstate(all="ignore"):
-        U = By.astype(D) * Cz.astype(D) - Bz.astype(D) * Cy.astype(D)
-        V = Cy.astype(D) * Az.astype(D) - Cz.astype(D) * Ay.astype(D)
-        W = Ay.astype(D) * Bz.astype(D) - Az.astype(D) * By.astype(D)
-        su, sv, sw = MP._sign(U, By, Bz, Cy, Cz), MP._sign(V, Cy, Cz, Ay, Az), MP._sign(W, Ay, Az, By, Bz)
-        det = (U + V) + W
-        hit = (su != 0) & (su == sv) & (su == sw) & (det != 0)
-        X = np.zeros_like(det)
-        num = (U * a[None, :, 0].astype(D) + V * b[None, :, 0].astype(D)) + W * c[None, :, 0].astype(D)
-        np.divide(num, det, out=X, where=hit)
-    return np.where(hit, su, 0).astype(np.int8), X
+signed_crossings = MP.signed_crossings  # the crossing rule is stated once, there
 
 
 def boundary_chain(faces, n_vertices):

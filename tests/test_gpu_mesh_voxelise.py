@@ -158,6 +158,29 @@ def test_two_schedules_one_rule(shape, sphere):
             assert zero.sum() > 50 and np.signbit(_cpu(vol)[..., 0][zero]).any() and not np.signbit(_cpu(vol)[..., 0][zero]).all()
 
 
+@pytest.mark.parametrize("X,inside", [(1, 4), (32, 40), (33, 44), (512, 640)])
+def test_row_lengths(X, inside):
+    """one voxel, one full bit word, two words with a ragged second, and the widest row: a closed cube off the lattice, so every row that
+    meets it has both signs.  The sign bits are in the format that the winding rows write too (sobfu_mesh_rows.hpp)."""
+    import torch
+
+    dims, vs = (X, 3, 2), (0.32 / X, 0.05, 0.05)
+    v, f = MP.cube((0.1, 0.02, 0.02), (0.2, 0.12, 0.08))
+    want, want_open, want_inside = MP.voxelise(v, f, dims, vs, 0.03, 0.01)
+    assert want_open == 0 and int(want_inside.sum()) == inside and not want_inside.all()
+    p = _gpu(MP.voxel_centres(dims, vs).reshape(-1, 4))
+    g = _grid(v, f)
+    for mode in ("grid", "brute"):
+        vol, open_rows = g.voxelise(dims, vs, 0.03, 0.01, mode=mode)
+        got = _cpu(vol)
+        assert np.array_equal(_bits(got), _bits(want)), "X = %d, %s: %d values differ" % (X, mode, int((_bits(got) != _bits(want)).sum()))
+        assert int(open_rows) == 0
+        ins, opn = g.inside(p, mode=mode)
+        assert np.array_equal(_cpu(ins).reshape(-1) == 1, np.signbit(got[..., 0]).reshape(-1)) and not _cpu(opn).any(), (X, mode)
+        wvol, _ = g.voxelise(dims, vs, 0.03, 0.01, mode=mode, sign="winding")
+        assert torch.equal(wvol.view(torch.int32), vol.view(torch.int32)), (X, mode)
+
+
 def test_open_cube_is_reported_and_refused_by_integrate_mesh():
     from sobfu_amd.fusion import SobFusion
     from sobfu_amd.params import read_ini

@@ -189,7 +189,7 @@ def _header_equals_restatement(tool, tmp_path, v, f, points, what):
     want_sign, want_X = MW.signed_crossings(points[:, 1:3], v, f)
     assert np.array_equal(sign, want_sign), "%s: the sign differs at %d pairs" % (what, int((sign != want_sign).sum()))
     assert np.array_equal(X.view(np.uint64), want_X.view(np.uint64)), "%s: X differs" % what
-    hit, Xp = MP.crossings(points[:, 1:3], v, f)  # the same operations as row_crossing
+    hit, Xp = MP.crossings(points[:, 1:3], v, f)  # signed_row_crossing with sign != 0
     assert np.array_equal(sign != 0, hit) and np.array_equal(X.view(np.uint64), Xp.view(np.uint64))
     got = _run(tool, tmp_path, "triangles", points[:, :3], tris).view(np.float64).reshape(n, T)
     q = points[:, None, :3].astype(np.float64)

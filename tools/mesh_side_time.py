@@ -10,6 +10,10 @@ The mesh: marching_cubes_indexed of init_sphere (r = 0.2 m at (0.375, 0.37, 0.38
   raycast_brute    the 160 x 120 rays of a camera 0.6 m in front of the sphere, mode brute (ray_brute_kernel)
   voxelise         back into the 256^3 volume, trunc 48 voxels, eta 3 voxels, cell 4 voxels (row_parity_kernel, brick_kernel)
   inside           the voxel centres of every fourth voxel per axis, 64^3 points (mesh_inside_kernel)
+  voxelise_winding the open mesh of profiles/mesh_winding.md -- the same mesh without the faces whose centroid lies within 4 mm of the
+                   planes x = centre and y = centre + 0.1 m -- into the 256^3 volume with sign="winding" (row_winding_kernel,
+                   winding_sum_kernel over the seam list, brick_kernel); the JSON line carries its triangle and boundary-edge counts
+  winding          the 64^3 points of `inside` against the open mesh, mode "boundary" (mesh_winding_kernel, winding_sum_kernel)
   align            10 iterations, dof 6, from the vertices turned by 1 degree and moved 2 mm (align_*_kernel and the grid query)
   icp_points / icp_depth   {10, 5, 4} iterations on 640 x 480 frames rendered from the mesh at two poses (icp_*_kernel)"""
 import json
@@ -22,7 +26,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sobfu_amd import ops  # noqa: E402
 
-CALLS = {"distance_brute": 5, "distance_grid": 30, "raycast_brute": 5, "voxelise": 3, "inside": 5, "align": 20, "icp_points": 20, "icp_depth": 20}
+CALLS = {"distance_brute": 5, "distance_grid": 30, "raycast_brute": 5, "voxelise": 3, "inside": 5, "voxelise_winding": 3, "winding": 5, "align": 20, "icp_points": 20, "icp_depth": 20}
 N, SIZE = 256, 0.75
 VS = SIZE / N
 INTR = (525.0, 525.0, 319.5, 239.5)
@@ -61,7 +65,7 @@ def main(names):
         d = torch.stack([(u - 79.5) / 131.0, (w - 59.5) / 131.0, torch.ones_like(u), torch.zeros_like(u)], -1).reshape(-1, 4).contiguous()
         o = torch.cat([centre - torch.tensor([0.0, 0.0, 0.6], device="cuda"), torch.ones(1, device="cuda")]).repeat(d.shape[0], 1).contiguous()
         out["raycast_brute"] = timed("raycast_brute", lambda: grid.raycast(o, d, mode="brute"))
-    if "voxelise" in names or "inside" in names:
+    if {"voxelise", "inside", "voxelise_winding", "winding"} & set(names):
         vv = v.clone()  # the mesh in the volume's frame: marching cubes writes (x, -y, -z)
         vv[:, 1:3] *= -1.0
         vgrid = ops.TriangleGrid(vv, f, cell=4 * VS)
@@ -69,11 +73,23 @@ def main(names):
             dst = ops.new_volume((N, N, N))
             out["voxelise"] = timed("voxelise", lambda: vgrid.voxelise((N, N, N), (VS,) * 3, 48 * VS, 3 * VS, out=dst))
             del dst
-        if "inside" in names:
+        if "inside" in names or "winding" in names:
             g = (torch.arange(0, N, 4, dtype=torch.float32, device="cuda") + 0.5) * VS
             zz, yy, xx = torch.meshgrid(g, g, g, indexing="ij")
             pts = torch.stack([xx, yy, zz, torch.ones_like(xx)], -1).reshape(-1, 4).contiguous()
+        if "inside" in names:
             out["inside"] = timed("inside", lambda: vgrid.inside(pts))
+        if "voxelise_winding" in names or "winding" in names:
+            mid = vv[f.long(), :3].mean(1)
+            keep = ((mid[:, 0] - 0.375).abs() > 0.004) & ((mid[:, 1] - 0.47).abs() > 0.004)
+            ogrid = ops.TriangleGrid(vv, f[keep].contiguous(), cell=4 * VS)
+            out.update(open_triangles=ogrid.n_triangles, boundary_edges=int(ogrid.boundary.shape[0]))
+            if "voxelise_winding" in names:
+                dst = ops.new_volume((N, N, N))
+                out["voxelise_winding"] = timed("voxelise_winding", lambda: ogrid.voxelise((N, N, N), (VS,) * 3, 48 * VS, 3 * VS, out=dst, sign="winding"))
+                del dst
+            if "winding" in names:
+                out["winding"] = timed("winding", lambda: ogrid.winding(pts, mode="boundary"))
     if "align" in names:
         a = np.deg2rad(1.0)
         R = torch.tensor([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]], dtype=torch.float32, device="cuda")
