@@ -67,6 +67,15 @@
 // frame scores the tracked poses against the file: "trajectory: ate=... rpe_trans=... rpe_rot=..." (sobfu_amd/trajectory.hpp: metres,
 // metres, radians; steps of one frame).
 //
+// Precision, recall and F-score (opt-in; sobfu_amd/csrc/mesh_sample_kernels.hip): --evaluate-fscore TAU[,TAU...] (metres,
+// up to 16, each > 0; needs --evaluate or --evaluate-live) samples both meshes of every evaluation uniformly per unit area and prints, after
+// each "evaluate canonical|live <frame>: ..." line, "fscore canonical|live <frame>: a_samples=... b_samples=... tau=... precision=... recall=...
+// f=... [tau=... ...] a_to_b.n=... ... chamfer=... hausdorff=..." from the same (aligned, posed) meshes: precision is the share of the model's
+// samples within tau of the ground truth, recall the share of the ground truth's within tau of the model, the statistics those of
+// compare_meshes over the samples, so weighted by area.  --evaluate-samples N (default 200 000: the density is N over the larger of the two
+// areas) or --evaluate-density D (samples per square metre), not both; --evaluate-seed S (default 0) picks the draws.  A sample farther
+// than --evaluate-max-dist is a miss.  The evaluate lines are the same with and without.
+//
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
 //                  [--warp-mesh] [--track-mesh K] [--fit-stats]
@@ -74,6 +83,7 @@
 //                   [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE]
 //                   | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | frame0.pgm frame1.pgm ...)
 //                  [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-signed] [--mesh-sign parity|winding]
+//                  [--evaluate-fscore TAU[,TAU...] [--evaluate-samples N | --evaluate-density D] [--evaluate-seed S]]
 #include <dirent.h>
 #include <sys/stat.h>
 
@@ -220,7 +230,7 @@ static std::string frame_path(const std::string& pattern, int n) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--evaluate-signed] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--evaluate-signed] [--evaluate-fscore TAU[,TAU...] [--evaluate-samples N | --evaluate-density D] [--evaluate-seed S]] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -246,6 +256,8 @@ int main(int argc, char** argv) {
     std::string render_trajectory;  // --render-trajectory: frame n is rendered from pose n of this file
     int eval_align = -1, eval_align_dof = 6;  // --evaluate-align: the iterations; -1: off
     float eval_max_dist = -1.f;  // < 0: 5 x the truncation distance
+    sobfu_amd::ScoreRequest score;  // --evaluate-fscore: its thresholds; empty: off
+    bool score_given = false, score_samples = false, score_density = false, score_seed = false;
     Screenshots shots;
     bool print_stats = true;  // per-frame volume statistics download four volumes: --no-stats leaves only the frame loop (timing runs)
     std::vector<std::string> files;
@@ -282,6 +294,49 @@ int main(int argc, char** argv) {
         else if (a == "--evaluate-align-dof" && i + 1 < argc) eval_align_dof = std::atoi(argv[++i]);
         else if (a == "--evaluate-pose-out" && i + 1 < argc) eval_pose_out = argv[++i];
         else if (a == "--error-mesh" && i + 1 < argc) error_dir = argv[++i];
+        else if (a == "--evaluate-fscore" && i + 1 < argc) {
+            const std::string list = argv[++i];
+            score_given = true;
+            for (size_t at = 0; at <= list.size();) {  // TAU[,TAU...]: every entry a finite number > 0
+                const size_t comma = std::min(list.find(',', at), list.size());
+                const std::string item = list.substr(at, comma - at);
+                char* end = nullptr;
+                const float tau = std::strtof(item.c_str(), &end);
+                if (item.empty() || end != item.c_str() + item.size() || !std::isfinite(tau) || !(tau > 0.f) || score.thresholds.size() == 16) {
+                    std::printf("--evaluate-fscore %s: expected 1 to 16 comma-separated distances in metres, each > 0\n", list.c_str());
+                    return 2;
+                }
+                score.thresholds.push_back(tau);
+                at = comma + 1;
+            }
+        }
+        else if (a == "--evaluate-samples" && i + 1 < argc) {
+            char* end = nullptr;
+            score.samples = std::strtoll(argv[++i], &end, 10);
+            score_samples = true;
+            if (end == argv[i] || *end != '\0' || score.samples < 1) {
+                std::printf("--evaluate-samples %s: expected a count >= 1\n", argv[i]);
+                return 2;
+            }
+        }
+        else if (a == "--evaluate-density" && i + 1 < argc) {
+            char* end = nullptr;
+            score.density = std::strtod(argv[++i], &end);
+            score_density = true;
+            if (end == argv[i] || *end != '\0' || !std::isfinite(score.density) || !(score.density > 0.0)) {
+                std::printf("--evaluate-density %s: expected samples per square metre, finite and > 0\n", argv[i]);
+                return 2;
+            }
+        }
+        else if (a == "--evaluate-seed" && i + 1 < argc) {
+            char* end = nullptr;
+            score.seed = std::strtoull(argv[++i], &end, 0);
+            score_seed = true;
+            if (end == argv[i] || *end != '\0') {
+                std::printf("--evaluate-seed %s: expected an unsigned integer\n", argv[i]);
+                return 2;
+            }
+        }
         else if (a == "--render-mesh" && i + 1 < argc) {
             if (voxelise) {
                 std::printf("--voxelise-mesh and --render-mesh exclude each other\n");
@@ -341,6 +396,18 @@ int main(int argc, char** argv) {
         std::printf("--evaluate-align takes at most 1000 iterations and needs --evaluate GT.ply; --evaluate-pose-out needs --evaluate-align\n");
         return 2;
     }
+    if (score_samples && score_density) {
+        std::printf("--evaluate-samples and --evaluate-density exclude each other\n");
+        return 2;
+    }
+    if (!score_given && (score_samples || score_density || score_seed)) {
+        std::printf("--evaluate-samples, --evaluate-density and --evaluate-seed need --evaluate-fscore\n");
+        return 2;
+    }
+    if (score_given && eval_gt.empty() && eval_live.empty()) {
+        std::printf("--evaluate-fscore needs --evaluate GT.ply or --evaluate-live PATTERN\n");
+        return 2;
+    }
     if ((warp_mesh || track_mesh >= 0) && mesh_dir.empty()) {
         std::printf("--warp-mesh and --track-mesh need --mesh DIR\n");
         return 2;
@@ -392,8 +459,10 @@ int main(int argc, char** argv) {
         sobfu_amd::AlignRequest request;
         std::copy(gt_pose, gt_pose + 16, request.pose);
         request.iters = eval_align, request.dof = eval_align_dof;
-        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why, shared ? &rendered.grid : nullptr, eval_signed, mesh_sign)
-                   : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr, eval_signed, mesh_sign))) {
+        sobfu_amd::MeshScore scored;
+        const sobfu_amd::ScoreRequest* scoring = score_given ? &score : nullptr;
+        if (!(live ? fusion.evaluate_live(gt, eval_max_dist, r, &model, &d, &why, shared ? &rendered.grid : nullptr, eval_signed, mesh_sign, scoring, &scored)
+                   : fusion.evaluate_canonical(gt, eval_max_dist, r, &model, &d, &why, align ? &request : nullptr, eval_signed, mesh_sign, scoring, &scored))) {
             std::printf("cannot evaluate against %s: %s\n", gt_path.c_str(), why.c_str());
             return false;
         }
@@ -410,6 +479,7 @@ int main(int argc, char** argv) {
             }
         }
         std::printf("evaluate %s %d: %s\n", live ? "live" : "canonical", n, sobfu_amd::format_comparison(r).c_str());
+        if (scoring) std::printf("fscore %s %d: %s\n", live ? "live" : "canonical", n, sobfu_amd::format_f_score(scored).c_str());
         if (!error_dir.empty() && !model.empty()) {
             sobfu_amd::error_colours(d, eval_max_dist, model.colours);
             const std::string path = error_dir + (live ? "/error_live_" : "/error_canonical_") + std::to_string(n) + ".ply";

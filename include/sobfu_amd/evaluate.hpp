@@ -7,6 +7,8 @@
 // TSDF volumes and the inside / outside test (sobfu_amd/csrc/mesh_voxel_kernels.hip): TriangleGrid::voxelise,
 // TriangleGrid::inside, mesh_to_tsdf, and the signed fields of compare_meshes.  Open meshes through generalised winding numbers (DESIGN.md 4.14,
 // sobfu_amd/csrc/mesh_winding_kernels.hip): TriangleGrid::boundary, TriangleGrid::winding, and MeshSign on voxelise, mesh_to_tsdf and compare_meshes.
+// Area-weighted surface samples and precision / recall / F-score over them (sobfu_amd/csrc/mesh_sample_kernels.hip): sample_mesh,
+// distance_score, f_score, format_f_score.
 #pragma once
 
 #include "../../sobfu_amd/csrc/sobfu_rigid.hpp"  // the rigid inverse, the same lines as the kernels'
@@ -650,6 +652,174 @@ struct AlignRequest {
     int iters = 30, dof = 6;
     Alignment info;
 };
+// ---- area-weighted samples, precision, recall and F-score (sobfu_amd/csrc/mesh_sample_kernels.hip; ops.mesh_sample,
+// ops.distance_score, sobfu_amd.evaluate.f_score) -----------------------------------------------------------------------------------------
+// the sum of doubles, exactly rounded and so independent of their order: Python's math.fsum (Shewchuk's non-overlapping partials, the
+// last step rounded half to even), for finite values whose sum does not overflow
+inline double exact_sum(const std::vector<double>& values) {
+    std::vector<double> partials;
+    for (double x : values) {
+        size_t i = 0;
+        for (double y : partials) {
+            if (std::fabs(x) < std::fabs(y)) std::swap(x, y);
+            const volatile double hi = x + y;  // volatile: each step is rounded to double, whatever the flags
+            const volatile double back = hi - x;
+            const double lo = y - back;
+            if (lo != 0.0) partials[i++] = lo;
+            x = hi;
+        }
+        partials.resize(i);
+        partials.push_back(x);
+    }
+    size_t n = partials.size();
+    if (n == 0) return 0.0;
+    double hi = partials[--n], lo = 0.0;
+    while (n > 0) {
+        const double x = hi, y = partials[--n];
+        const volatile double sum = x + y;
+        const volatile double back = sum - x;
+        hi = sum, lo = y - back;
+        if (lo != 0.0) break;
+    }
+    if (n > 0 && ((lo < 0.0 && partials[n - 1] < 0.0) || (lo > 0.0 && partials[n - 1] > 0.0))) {
+        const double y = lo * 2.0;
+        const volatile double x = hi + y;
+        const volatile double back = x - hi;
+        if (y == back) hi = x;
+    }
+    return hi;
+}
+struct MeshSamples {
+    std::vector<float4> points;  // (x, y, z, 1), ordered by triangle
+    std::vector<int> tri;        // each sample's triangle (on request)
+    std::vector<float2> bary;    // the weights of that triangle's second and third corner (on request)
+    std::vector<double> areas;   // per triangle (on request)
+};
+// Points drawn uniformly per unit area at `density` samples per square metre (ops.mesh_sample): triangle t receives floor(area_t density)
+// samples plus one more with probability frac(area_t density); the result depends on the mesh, the density and the seed alone, bit for bit.
+// false (+ *why): a face index out of range, a non-finite corner, a density that is not finite and >= 0, or more than INT32_MAX samples
+inline bool sample_mesh(const IndexedMesh& m, double density, uint64_t seed, MeshSamples& out, bool with_tri = false, bool with_bary = false,
+                        bool with_areas = false, std::string* why = nullptr) {
+    out = MeshSamples();
+    const int nv = (int) m.vertices.size(), nt = (int) (m.faces.size() / 3);
+    if (!(std::isfinite(density) && density >= 0.0)) {
+        if (why) *why = "the sampling density must be finite and >= 0";
+        return false;
+    }
+    kfusion::cuda::DeviceArray<float4> dv, dp;
+    kfusion::cuda::DeviceArray<int> df, dt;
+    kfusion::cuda::DeviceArray<float2> db;
+    kfusion::cuda::DeviceArray<double> da;
+    kfusion::cuda::DeviceArray<unsigned char> ws(sobfu_hip_mesh_sample_workspace_bytes(nt));
+    if (nv) dv.upload(m.vertices);
+    if (nt) df.upload(m.faces.data(), 3 * (size_t) nt);
+    if (with_areas && nt) da.create((size_t) nt);
+    long long total = 0;
+    const float* vp = nv ? (const float*) dv.ptr() : nullptr;
+    const int* fp   = nt ? df.ptr() : nullptr;
+    const int rc = sobfu_hip_mesh_sample_count(vp, nv, fp, nt, density, seed, ws.ptr(), ws.sizeBytes(), with_areas && nt ? da.ptr() : nullptr, &total, nullptr);
+    if (rc == SOBFU_E_BADARG || rc == SOBFU_E_UNSUPPORTED) {
+        if (why) *why = rc == SOBFU_E_BADARG ? "the mesh has a face index out of range or a non-finite corner" : "more than INT32_MAX samples (" + std::to_string(total) + ")";
+        return false;
+    }
+    sobfuSafeCall(rc);
+    if (with_areas && nt) da.download(out.areas);
+    const size_t n = (size_t) total;
+    if (n) {
+        dp.create(n);
+        if (with_tri) dt.create(n);
+        if (with_bary) db.create(n);
+        sobfuSafeCall(sobfu_hip_mesh_sample_generate(vp, nv, fp, nt, seed, ws.ptr(), ws.sizeBytes(), (float*) dp.ptr(), with_tri ? dt.ptr() : nullptr,
+                                                     with_bary ? (float*) db.ptr() : nullptr, (int) n, nullptr));
+        dp.download(out.points);
+        if (with_tri) dt.download(out.tri);
+        if (with_bary) db.download(out.bary);
+    }
+    return true;
+}
+// the mesh's area: exact_sum of the triangles' fp64 areas (the denominator of "n samples": density = n / area)
+inline bool mesh_area(const IndexedMesh& m, double& area, std::string* why = nullptr) {
+    MeshSamples s;
+    if (!sample_mesh(m, 0.0, 0, s, false, false, true, why)) return false;
+    area = exact_sum(s.areas);
+    return true;
+}
+// within[k] = how many distances are finite and <= thresholds[k] (1 to 16 of them, any order); finite = how many are finite at all
+inline void distance_score(const std::vector<float>& dist, const std::vector<float>& thresholds, std::vector<long long>& within, long long& finite) {
+    if (thresholds.empty() || thresholds.size() > 16) kfusion::cuda::error("distance_score: 1 to 16 thresholds", __FILE__, __LINE__);
+    kfusion::cuda::DeviceArray<float> dd;
+    kfusion::cuda::DeviceArray<long long> dc(thresholds.size() + 1);
+    if (!dist.empty()) dd.upload(dist);
+    sobfuSafeCall(sobfu_hip_distance_score(dist.empty() ? nullptr : dd.ptr(), (int) dist.size(), thresholds.data(), (int) thresholds.size(), dc.ptr(), nullptr));
+    dc.download(within);
+    finite = within.back();
+    within.pop_back();
+}
+// what f_score is to do: the thresholds (metres); density > 0: samples per square metre, else `samples` over the larger of the two areas;
+// mesh a draws with `seed`, mesh b with seed + 1
+struct ScoreRequest {
+    std::vector<float> thresholds;
+    double density    = 0.0;
+    long long samples = 200000;
+    uint64_t seed     = 0;
+};
+struct MeshScore {
+    std::vector<float> thresholds;
+    std::vector<double> precision, recall, f;  // one entry per threshold; f = 2 P R / (P + R), 0 when P + R = 0
+    size_t a_samples = 0, b_samples = 0;
+    DistanceStats a_to_b, b_to_a;  // of the sampled distances
+    double chamfer = 0, hausdorff = 0;
+};
+// sobfu_amd.evaluate.f_score: a = the model, b = the ground truth, both sampled at one density; each sample set is sent to the other mesh's
+// surface and scored.  The denominators are all the samples: one farther than max_dist (> 0) has no match and is a miss.  false (+ *why):
+// a mesh is refused.  grid_b (optional): a grid already built over b
+inline bool f_score(const IndexedMesh& a, const IndexedMesh& b, const ScoreRequest& request, float max_dist, MeshScore& out, std::string* why = nullptr,
+                    TriangleGrid* grid_b = nullptr) {
+    out = MeshScore();
+    out.thresholds = request.thresholds;
+    TriangleGrid ga, own;
+    if (!grid_b && !own.build(b.vertices, b.faces, 0.f, why)) return false;
+    TriangleGrid& gb = grid_b ? *grid_b : own;
+    if (!ga.build(a.vertices, a.faces, 0.f, why)) return false;
+    double density = request.density;
+    if (!(density > 0.0)) {
+        double area_a = 0, area_b = 0;
+        if (!mesh_area(a, area_a, why) || !mesh_area(b, area_b, why)) return false;
+        const double larger = std::max(area_a, area_b);
+        density = larger > 0.0 ? (double) request.samples / larger : 0.0;
+    }
+    MeshSamples sa, sb;
+    if (!sample_mesh(a, density, request.seed, sa, false, false, false, why) || !sample_mesh(b, density, request.seed + 1, sb, false, false, false, why)) return false;
+    std::vector<float> ab, ba;
+    gb.query(sa.points, ab, max_dist);
+    ga.query(sb.points, ba, max_dist);
+    std::vector<long long> wa, wb;
+    long long finite = 0;
+    distance_score(ab, request.thresholds, wa, finite);
+    distance_score(ba, request.thresholds, wb, finite);
+    out.a_samples = sa.points.size(), out.b_samples = sb.points.size();
+    for (size_t k = 0; k < request.thresholds.size(); ++k) {
+        const double p = out.a_samples ? (double) wa[k] / (double) out.a_samples : 0.0, r = out.b_samples ? (double) wb[k] / (double) out.b_samples : 0.0;
+        out.precision.push_back(p), out.recall.push_back(r), out.f.push_back(p + r > 0.0 ? 2.0 * p * r / (p + r) : 0.0);
+    }
+    out.a_to_b = distance_stats(ab), out.b_to_a = distance_stats(ba);
+    out.chamfer = 0.5 * (out.a_to_b.mean + out.b_to_a.mean), out.hausdorff = std::max(out.a_to_b.max, out.b_to_a.max);
+    return true;
+}
+// one line (sobfu_amd.evaluate.format_f_score): the two sample counts, tau, precision, recall and f per threshold, then format_comparison's
+// fields; every float at %.9g
+inline std::string format_f_score(const MeshScore& r) {
+    char part[256];
+    std::snprintf(part, sizeof part, "a_samples=%zu b_samples=%zu ", r.a_samples, r.b_samples);
+    std::string line = part;
+    for (size_t k = 0; k < r.thresholds.size(); ++k) {
+        std::snprintf(part, sizeof part, "tau=%.9g precision=%.9g recall=%.9g f=%.9g ", (double) r.thresholds[k], r.precision[k], r.recall[k], r.f[k]);
+        line += part;
+    }
+    MeshComparison c;
+    c.a_to_b = r.a_to_b, c.b_to_a = r.b_to_a, c.chamfer = r.chamfer, c.hausdorff = r.hausdorff;
+    return line + format_comparison(c);
+}
 // ---- mesh_to_tsdf: a closed mesh as the full 3-D signed TSDF of a volume (sobfu_amd.mesh_voxelise.mesh_to_tsdf) ---------------------------
 // the pose of the meshes the project writes and evaluates against, mesh frame -> camera frame: (x, -y, -z)
 inline cv::Affine3f mesh_frame() {

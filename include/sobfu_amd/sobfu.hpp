@@ -1422,10 +1422,13 @@ public:
     // mesh and its vertices' distances.  false (+ *why): the ground truth is refused (an index out of range, a non-finite corner)
     // align (optional, canonical only): align->pose, the caller's ground-truth-to-model guess, is first refined against the model
     // (sobfu_amd::align_meshes with max_dist) and applied to a copy of the ground truth; without it the ground truth is taken as given.
+    // score + scored (optional, both): precision, recall and F-score over area-weighted samples of the same (aligned, posed) meshes
+    // (sobfu_amd::f_score with max_dist) into *scored; without them nothing else changes.
     bool evaluate_canonical(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
                             std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::AlignRequest* align = nullptr, bool with_signs = false,
-                            int sign = sobfu_amd::kSignParity) {
+                            int sign = sobfu_amd::kSignParity, const sobfu_amd::ScoreRequest* score = nullptr, sobfu_amd::MeshScore* scored = nullptr) {
         sobfu_amd::IndexedMesh m = get_phi_global_indexed_mesh();
+        const bool scoring = score && scored;
         bool ok;
         if (align) {
             sobfu_amd::IndexedMesh posed = gt;
@@ -1434,8 +1437,10 @@ public:
                 sobfu_amd::transform_points(posed.vertices, align->pose);
                 ok = sobfu_amd::compare_meshes(m, posed, max_dist, out, d_model, nullptr, why, nullptr, with_signs, sign);
             }
+            if (ok && scoring) ok = sobfu_amd::f_score(m, posed, *score, max_dist, *scored, why);
         } else {
             ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, nullptr, with_signs, sign);
+            if (ok && scoring) ok = sobfu_amd::f_score(m, gt, *score, max_dist, *scored, why);
         }
         if (model) *model = std::move(m);
         return ok;
@@ -1444,9 +1449,10 @@ public:
     // by the rule `sign` (sobfu_amd::MeshSign)
     bool evaluate_live(const sobfu_amd::IndexedMesh& gt, float max_dist, sobfu_amd::MeshComparison& out, sobfu_amd::IndexedMesh* model = nullptr,
                        std::vector<float>* d_model = nullptr, std::string* why = nullptr, sobfu_amd::TriangleGrid* gt_grid = nullptr, bool with_signs = false,
-                       int sign = sobfu_amd::kSignParity) {
+                       int sign = sobfu_amd::kSignParity, const sobfu_amd::ScoreRequest* score = nullptr, sobfu_amd::MeshScore* scored = nullptr) {
         sobfu_amd::IndexedMesh m = get_phi_global_warped_indexed_mesh();
-        const bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, gt_grid, with_signs, sign);
+        bool ok = sobfu_amd::compare_meshes(m, gt, max_dist, out, d_model, nullptr, why, gt_grid, with_signs, sign);
+        if (ok && score && scored) ok = sobfu_amd::f_score(m, gt, *score, max_dist, *scored, why, gt_grid);
         if (model) *model = std::move(m);
         return ok;
     }

@@ -786,6 +786,40 @@ int sobfu_hip_depth_sensor(const float* d_points, int points_step, const float* 
                            const sobfu_hip_sensor_params* p, uint16_t* d_depth, int depth_step, uint8_t* d_flags, int flags_step,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mesh sampling and F-score counts  (no counterpart in the reference; sobfu_amd/csrc/mesh_sample_kernels.hip)
+ * Points drawn uniformly per unit area from an indexed triangle mesh (vertices as n_vertices dense float4, faces as n_triangles x 3
+ * int32, as for the mesh distance), at `density` samples per square unit.  Triangle t of area A (fp64) receives floor(A density) samples
+ * plus one more with probability frac(A density): its expectation is exactly A density and it is never more than one sample from it.
+ * Sample k of triangle t is p = (a + (b - a) r1) + (c - a) r2 with (r1, r2) from the Philox4x32-10 draw of counter (t, k, 0, 1) under
+ * the key (seed & 0xffffffff, seed >> 32), folded into the triangle on integers (the rule, operation by operation:
+ * sobfu_amd/csrc/sobfu_mesh_sample.hpp).  Samples are ordered by triangle, then k.  The result depends on the mesh, the density and the
+ * seed alone: the same bits on any machine, for any launch shape and from run to run.
+ * Every argument is checked before any device call (SOBFU_E_BADARG): NULL or misaligned pointers, negative sizes, a non-finite or
+ * negative density, a short workspace, n_thresholds outside 1 .. 16.
+ * ---------------------------------------------------------------------------------------------------- */
+/* Bytes of the caller-kept workspace (16-byte aligned) for a mesh of n_triangles: a header, the counts, their offsets and the scan's
+ * block sums.  0 for n_triangles < 0. */
+size_t sobfu_hip_mesh_sample_workspace_bytes(int n_triangles);
+/* Counts the samples of every triangle and scans them into the workspace.  SYNCHRONISES the stream once, after the count:
+ * *h_samples = the 64-bit total.  d_areas (may be NULL): n_triangles doubles, the triangles' areas.  SOBFU_E_BADARG (after the
+ * synchronisation) for a face index outside [0, n_vertices) or a non-finite corner (such a triangle counts 0); SOBFU_E_UNSUPPORTED when
+ * the total exceeds INT32_MAX (*h_samples still holds it; beyond 2^62 per triangle it saturates).  A workspace whose count did not
+ * return 0 is not marked and sobfu_hip_mesh_sample_generate through it is refused.  n_triangles = 0 or density = 0: 0 samples, success. */
+int sobfu_hip_mesh_sample_count(const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles, double density, uint64_t seed,
+                                void* d_workspace, size_t workspace_bytes, double* d_areas, long long* h_samples, void* stream);
+/* The samples of the last count through this workspace (the same mesh arrays, unchanged, and the same seed): d_points, dense float4
+ * (x, y, z, 1); d_tri (may be NULL), the triangle of each sample; d_bary (may be NULL), float2 (r1, r2), the weights of the triangle's
+ * second and third corner.  Reads the workspace's header back (one small copy), then only enqueues.  Never truncates: max_samples below
+ * the count's total is SOBFU_E_BADARG before any launch, and so is a workspace that is not marked or was counted for another n_triangles. */
+int sobfu_hip_mesh_sample_generate(const float* d_vertices, int n_vertices, const int* d_faces, int n_triangles, uint64_t seed,
+                                   void* d_workspace, size_t workspace_bytes, float* d_points, int* d_tri, float* d_bary, int max_samples,
+                                   void* stream);
+/* n float distances against n_thresholds (1 .. 16, host array, any order) -> d_counts, n_thresholds + 1 64-bit integers on the device
+ * (8-byte aligned): d_counts[k] = #{i : d_i finite and d_i <= thresholds[k]}, d_counts[n_thresholds] = #{i : d_i finite}.  NaN and
+ * +-Inf are never within.  Integer sums: the same from run to run.  n = 0 launches nothing and leaves zeros.  Asynchronous. */
+int sobfu_hip_distance_score(const float* d_dist, int n, const float* h_thresholds, int n_thresholds, long long* d_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,7 @@ def lib():
     L.sobfu_hip_mesh_align_workspace_bytes.restype = C.c_size_t
     L.sobfu_hip_mesh_voxelise_workspace_bytes.restype = C.c_size_t
     L.sobfu_hip_mesh_voxelise_winding_workspace_bytes.restype = C.c_size_t
+    L.sobfu_hip_mesh_sample_workspace_bytes.restype = C.c_size_t
     _lib = L
     return L
 

@@ -119,6 +119,13 @@ def build_mesh_winding_tool(force: bool = False, flags=(), out: str = "mesh_wind
     return _build(out, _test_src("mesh_winding_tool.cpp"), deps, False, force, ["-std=c++14", f"-I{CSRC}", "-ffp-contract=off", *flags])
 
 
+def build_mesh_sample_tool(force: bool = False, flags=(), out: str = "mesh_sample_tool") -> str:
+    """tests/cpp/mesh_sample_tool.cpp: CPU-only driver of the mesh sampling rule (sobfu_amd/csrc/sobfu_mesh_sample.hpp, no HIP;
+    -ffp-contract=off, as the kernels are built).  out: the program's name under build/ (a second build with other flags keeps the first)."""
+    deps = [os.path.join(CSRC, h) for h in ("sobfu_mesh_sample.hpp", "sobfu_mesh_distance.hpp", "sobfu_random.hpp")]
+    return _build(out, _test_src("mesh_sample_tool.cpp"), deps, False, force, ["-std=c++17", f"-I{CSRC}", "-ffp-contract=off", *flags])
+
+
 def build_rigid_tool(force: bool = False) -> str:
     """tests/cpp/rigid_solve_tool.cpp: CPU-only driver of the shared rigid solve (sobfu_amd/csrc/sobfu_rigid.hpp, no HIP; -ffp-contract=off,
     as the kernels are built)."""
@@ -144,7 +151,7 @@ def build_pass_a_plan_tool(force: bool = False) -> str:
 
 def build_host(force: bool = False) -> str:
     for build in (build_pass_a_plan_tool, build_depth_sensor_tool, build_trajectory_tool, build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
-                  build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_mesh_parity_tool, build_mesh_winding_tool, build_rigid_tool):
+                  build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_mesh_parity_tool, build_mesh_winding_tool, build_mesh_sample_tool, build_rigid_tool):
         build(force)
     return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H], True, force)
 

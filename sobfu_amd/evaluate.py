@@ -116,3 +116,52 @@ def format_alignment(info, pose):
     last = info["trace"][-1] if len(info["trace"]) else (0.0, 0.0)
     return "status=0x%x iterations=%d inliers=%d rms=%.9g pose=%s" % (info["status"], info["iterations"], int(last[0]), float(last[1]),
                                                                    ",".join("%.9g" % float(v) for v in np.asarray(pose, np.float32).reshape(16)))
+
+
+# ---- precision, recall and F-score over area-weighted samples (ops.mesh_sample, ops.distance_score) -----------------------
+def f_score(a_vertices, a_faces, b_vertices, b_faces, thresholds, density=None, n=None, seed=0, max_dist=None):
+    """Two indexed meshes, a = the model and b = the ground truth, each sampled uniformly per unit area at the same density (exactly one
+    of density, in samples per square metre, and n is given; n: the density is n over the larger of the two areas), a with the draws of
+    `seed` and b with those of seed + 1.  Each sample set is sent to the other mesh's surface (ops.TriangleGrid.query) and scored against
+    the thresholds (metres, up to 16, any order) -> dict(thresholds; precision, recall, f: lists, one entry per threshold -- the share of
+    a's samples within tau of b, of b's samples within tau of a, and 2 P R / (P + R), 0 when P + R = 0; a_samples, b_samples: the two
+    counts; a_to_b, b_to_a: distance_stats of the sampled distances; chamfer, hausdorff: as in compare_meshes, now weighted by area).
+    The denominators are all the samples: one farther than max_dist has no match and is a miss.  A side without samples scores 0."""
+    import math
+
+    import torch
+
+    from . import ops
+
+    if (density is None) == (n is None):
+        raise ValueError("give exactly one of density and n")
+    th = [float(np.float32(t)) for t in np.asarray(thresholds, np.float64).reshape(-1)]  # as the kernel compares them
+    av, bv = device_tensor(a_vertices, torch.float32), device_tensor(b_vertices, torch.float32)
+    af, bf = device_tensor(a_faces, torch.int32), device_tensor(b_faces, torch.int32)
+    ga, gb = ops.TriangleGrid(av, af), ops.TriangleGrid(bv, bf)
+    if n is not None:
+        areas = []
+        for v, f in ((av, af), (bv, bf)):
+            rc, _, _, a = ops.mesh_sample_count(v, f, 0.0, 0, areas=True)
+            ops.check(rc, "mesh_sample_count")
+            areas.append(math.fsum(a.cpu().numpy().tolist()))
+        density = float(n) / max(areas) if max(areas) > 0.0 else 0.0
+    pa, pb = ga.sample(density=density, seed=seed), gb.sample(density=density, seed=int(seed) + 1)
+    d_ab, d_ba = gb.query(pa, max_dist)[0], ga.query(pb, max_dist)[0]
+    (wa, _), (wb, _) = ops.distance_score(d_ab, th), ops.distance_score(d_ba, th)
+    na, nb = int(pa.shape[0]), int(pb.shape[0])
+    precision = [int(w) / na if na else 0.0 for w in wa]
+    recall = [int(w) / nb if nb else 0.0 for w in wb]
+    f = [2.0 * p * r / (p + r) if p + r > 0.0 else 0.0 for p, r in zip(precision, recall)]
+    ab, ba = distance_stats(d_ab), distance_stats(d_ba)
+    return dict(thresholds=th, precision=precision, recall=recall, f=f, a_samples=na, b_samples=nb, a_to_b=ab, b_to_a=ba,
+                chamfer=0.5 * (ab["mean"] + ba["mean"]), hausdorff=max(ab["max"], ba["max"]))
+
+
+def format_f_score(r):
+    """the app's printed form: the two sample counts, then tau, precision, recall and f per threshold, then the fields of format_result;
+    every float at %.9g"""
+    parts = [f"a_samples={r['a_samples']}", f"b_samples={r['b_samples']}"]
+    for t, p, q, f in zip(r["thresholds"], r["precision"], r["recall"], r["f"]):
+        parts.append(f"tau={t:.9g} precision={p:.9g} recall={q:.9g} f={f:.9g}")
+    return " ".join(parts) + " " + format_result(r)

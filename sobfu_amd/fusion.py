@@ -239,7 +239,7 @@ class SobFusion:
         return dict(valid=int(d.size), mean_abs=float(d.mean()), rms=float(np.sqrt((d * d).mean())), max=float(d.max()))
 
     def evaluate(self, gt_vertices, gt_faces, which="canonical", max_dist=None, pose=None, return_meshes=False, align=False, align_dof=6,
-                 align_iters=30, signed=False):
+                 align_iters=30, signed=False, f_score=None):
         """The reconstruction against a ground-truth mesh (vertices (V, 4), faces (F, 3)) in the frame of the meshes the app writes
         (marching-cubes vertices, (x, -y, -z)): exact vertex-to-surface distances both ways (sobfu_amd.evaluate.compare_meshes; a = the
         model, b = the ground truth), in metres.  which: "canonical" meshes phi_global (ops.marching_cubes_indexed at the volume pose),
@@ -249,7 +249,9 @@ class SobFusion:
         iterations, align_dof 6 (rigid) or 3 (translation only: symmetric objects) -- and the dict gains "pose" (the refined 4 x 4) and
         "align" (the alignment's info).  The live mesh is never aligned: that would hide the tracking error evaluation measures.
         signed: each direction gains signed_mean, inside and open (compare_meshes): a_to_b.signed_mean > 0 says the model lies outside
-        the (closed) ground truth on average."""
+        the (closed) ground truth on average.
+        f_score: a dict of sobfu_amd.evaluate.f_score's arguments (thresholds, and density or n, seed, max_dist); the dict then gains
+        "f_score", that function's result on the same (posed, aligned) meshes.  Without it the result is unchanged."""
         import torch
 
         from . import evaluate as E
@@ -273,6 +275,8 @@ class SobFusion:
         r = E.compare_meshes(v, f, gv, gt_faces, max_dist, signed=signed)
         if align:
             r["pose"], r["align"] = pose, info
+        if f_score is not None:
+            r["f_score"] = E.f_score(v, f, gv, gt_faces, **f_score)
         return (r, v, f, gv) if return_meshes else r
 
     def close(self):

@@ -1001,6 +1001,10 @@ class TriangleGrid:
                                                     C.c_int(0 if mode == "boundary" else 1), walk, _stream()), "mesh_winding")
         return w
 
+    def sample(self, density=None, n=None, seed=0, tri=False, bary=False, areas=False):
+        """mesh_sample on this grid's own mesh"""
+        return mesh_sample(self.vertices, self.faces, density, n, seed, tri, bary, areas)
+
     def unresolved(self):
         """how many points of the last query hit the ring cap and were finished by brute force (synchronises)"""
         n = C.c_int(0)
@@ -1011,6 +1015,87 @@ class TriangleGrid:
 def mesh_distance(points, vertices, faces, max_dist=None, closest=False, mode="auto", ring_cap=None, cell=None):
     """TriangleGrid(vertices, faces, cell).query(points, ...) in one call"""
     return TriangleGrid(vertices, faces, cell).query(points, max_dist, closest, mode, ring_cap)
+
+
+# ---- area-weighted mesh samples and F-score counts (sobfu_amd/csrc/mesh_sample_kernels.hip, DESIGN.md 4.15) -------------------------------
+def _mesh_args(vertices, faces):
+    _point_list(vertices, "vertices")
+    if not (faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError(f"expected (F, 3) int32 faces, got {tuple(faces.shape)}")
+    nv, nt = int(vertices.shape[0]), int(faces.shape[0])
+    return (_ptr(vertices) if nv else None, C.c_int(nv), _ptr(faces, torch.int32) if nt else None, C.c_int(nt))
+
+
+def mesh_sample_count(vertices, faces, density, seed=0, areas=False):
+    """The count call of mesh_sample on its own -> (rc, total, workspace, areas): sobfu_hip_mesh_sample_count's return code (0, -1 for a
+    face index out of range or a non-finite corner, -3 for more than INT32_MAX samples), the 64-bit total, the workspace (a uint8
+    tensor, for mesh_sample_generate) and the (F,) float64 areas when asked for.  Synchronises once."""
+    L = _lib.lib()
+    mesh = _mesh_args(vertices, faces)
+    nt = int(faces.shape[0])
+    ws = torch.empty(int(L.sobfu_hip_mesh_sample_workspace_bytes(C.c_int(nt))), dtype=torch.uint8, device=vertices.device)
+    a = torch.empty(nt, dtype=torch.float64, device=vertices.device) if areas else None
+    total = C.c_longlong(0)
+    rc = L.sobfu_hip_mesh_sample_count(*mesh, C.c_double(float(density)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), *_ws(ws),
+                                       _ptr(a, torch.float64) if areas and nt else None, C.byref(total), _stream())
+    return rc, int(total.value), ws, a
+
+
+def mesh_sample_generate(vertices, faces, seed, workspace, max_samples, tri=False, bary=False):
+    """The generate call of mesh_sample on its own, through the workspace of mesh_sample_count -> (rc, points (max_samples, 4) float32,
+    tri (max_samples,) int32 or None, bary (max_samples, 2) float32 or None)"""
+    dev, n = vertices.device, int(max_samples)
+    p = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    t = torch.empty(n, dtype=torch.int32, device=dev) if tri else None
+    b = torch.empty((n, 2), dtype=torch.float32, device=dev) if bary else None
+    rc = _lib.lib().sobfu_hip_mesh_sample_generate(*_mesh_args(vertices, faces), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), *_ws(workspace),
+                                                   _ptr(p) if n else None, _ptr(t, torch.int32) if tri and n else None, _ptr(b) if bary and n else None,
+                                                   C.c_int(n), _stream())
+    return rc, p, t, b
+
+
+def mesh_sample(vertices, faces, density=None, n=None, seed=0, tri=False, bary=False, areas=False):
+    """Points drawn uniformly per unit area from an indexed mesh (vertices (V, 4) float32, faces (F, 3) int32, GPU tensors) -> points
+    (N, 4) float32 (x, y, z, 1) on the GPU [, tri (N,) int32: each sample's triangle] [, bary (N, 2) float32: the weights of that
+    triangle's second and third corner] [, areas (F,) float64].  Exactly one of density (samples per unit area) and n is given.
+    Triangle t receives floor(area_t density) samples plus one more with probability frac(area_t density), so the total is within the
+    number of triangles of density x the mesh's area.  n means density = n / math.fsum(areas): the sample count then lands within that
+    spread of n, it is NOT exactly n.  Samples are ordered by triangle; the result depends on the mesh, the density and the seed alone,
+    bit for bit (sobfu_amd/csrc/sobfu_mesh_sample.hpp)."""
+    import math
+
+    if (density is None) == (n is None):
+        raise ValueError("give exactly one of density and n")
+    a = None
+    if n is not None:
+        if int(n) < 0:
+            raise ValueError("n >= 0")
+        rc, _, _, a = mesh_sample_count(vertices, faces, 0.0, seed, areas=True)
+        check(rc, "mesh_sample_count")
+        total_area = math.fsum(a.cpu().numpy().tolist())
+        density = float(n) / total_area if total_area > 0.0 and int(n) > 0 else 0.0
+    if not (math.isfinite(density) and density >= 0.0):
+        raise ValueError(f"the density must be finite and >= 0, got {density}")
+    rc, total, ws, a2 = mesh_sample_count(vertices, faces, density, seed, areas=areas and a is None)
+    check(rc, "mesh_sample_count")
+    rc, p, t, b = mesh_sample_generate(vertices, faces, seed, ws, total, tri, bary)
+    check(rc, "mesh_sample_generate")
+    extras = [x for x, asked in ((t, tri), (b, bary), (a2 if a is None else a, areas)) if asked]
+    return (p, *extras) if extras else p
+
+
+def distance_score(dist, thresholds):
+    """(n,) float32 distances on the GPU, up to 16 thresholds (any order) -> (within (K,) int64 numpy: how many distances are finite and
+    <= each threshold, finite: how many are finite at all).  NaN and +Inf are never within.  Synchronises to read the counts."""
+    th = [float(x) for x in np.asarray(thresholds, np.float64).reshape(-1)]
+    if not 1 <= len(th) <= 16:
+        raise ValueError("1 to 16 thresholds")
+    n = int(dist.numel())
+    counts = torch.empty(len(th) + 1, dtype=torch.int64, device=dist.device)
+    check(_lib.lib().sobfu_hip_distance_score(_ptr(dist) if n else None, C.c_int(n), (C.c_float * len(th))(*th), C.c_int(len(th)),
+                                              _ptr(counts, torch.int64), _stream()), "distance_score")
+    c = counts.cpu().numpy()
+    return c[:-1].copy(), int(c[-1])
 
 
 # ---- camera tracking (sobfu_amd/csrc/icp_kernels.hip): projective ICP and its image pyramids -------------------------------------

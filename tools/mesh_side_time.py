@@ -15,6 +15,11 @@ The mesh: marching_cubes_indexed of init_sphere (r = 0.2 m at (0.375, 0.37, 0.38
                    winding_sum_kernel over the seam list, brick_kernel); the JSON line carries its triangle and boundary-edge counts
   winding          the 64^3 points of `inside` against the open mesh, mode "boundary" (mesh_winding_kernel, winding_sum_kernel)
   align            10 iterations, dof 6, from the vertices turned by 1 degree and moved 2 mm (align_*_kernel and the grid query)
+  sample_sphere / sample_box   about 1 M area-weighted samples (profiles/mesh_sample.md) of the mesh and of a 1 x 0.5 x 0.25 m box of 12
+                   triangles: ops.mesh_sample at a given density -- count, scan, the read-back, generate (sample_count_kernel, the scan,
+                   sample_generate_kernel); sample_sphere_generate / sample_box_generate: the generate call alone through a counted workspace
+  sample_score     ops.distance_score of the sphere samples' distances against four thresholds (distance_score_kernel)
+  sample_query     TriangleGrid.query of the sphere's samples against the mesh moved by 2 mm: what f_score spends per direction
   icp_points / icp_depth   {10, 5, 4} iterations on 640 x 480 frames rendered from the mesh at two poses (icp_*_kernel)"""
 import json
 import os
@@ -26,7 +31,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sobfu_amd import ops  # noqa: E402
 
-CALLS = {"distance_brute": 5, "distance_grid": 30, "raycast_brute": 5, "voxelise": 3, "inside": 5, "voxelise_winding": 3, "winding": 5, "align": 20, "icp_points": 20, "icp_depth": 20}
+CALLS = {"distance_brute": 5, "distance_grid": 30, "raycast_brute": 5, "voxelise": 3, "inside": 5, "voxelise_winding": 3, "winding": 5, "align": 20, "icp_points": 20, "icp_depth": 20,
+         "sample_sphere": 20, "sample_box": 20, "sample_sphere_generate": 30, "sample_box_generate": 30, "sample_score": 30, "sample_query": 10}
 N, SIZE = 256, 0.75
 VS = SIZE / N
 INTR = (525.0, 525.0, 319.5, 239.5)
@@ -96,6 +102,30 @@ def main(names):
         src = v.clone()
         src[:, :3] = (v[:, :3] - centre) @ R.T + centre + torch.tensor([0.002, 0.0, 0.0], device="cuda")
         out["align"] = timed("align", lambda: grid.align(src, iters=10, dof=6))
+    if any(n.startswith("sample") for n in names):
+        import math
+
+        bv = torch.tensor([(x, y, z, 1.0) for z in (0.0, 0.25) for y in (0.0, 0.5) for x in (0.0, 1.0)], dtype=torch.float32, device="cuda")
+        bf = torch.tensor([(0, 2, 1), (1, 2, 3), (4, 5, 6), (5, 7, 6), (0, 1, 4), (1, 5, 4), (2, 6, 3), (3, 6, 7), (0, 4, 2), (2, 4, 6), (1, 3, 5), (3, 7, 5)],
+                          dtype=torch.int32, device="cuda")
+        for name, (mv, mf) in (("sample_sphere", (v, f)), ("sample_box", (bv, bf))):
+            area = math.fsum(ops.mesh_sample_count(mv, mf, 0.0, areas=True)[3].cpu().numpy().tolist())
+            density = 1.0e6 / area
+            rc, total, ws, _ = ops.mesh_sample_count(mv, mf, density)
+            assert rc == 0
+            out[name + "_samples"] = total
+            if name in names:
+                out[name] = timed(name, lambda: ops.mesh_sample(mv, mf, density=density))
+            if name + "_generate" in names:
+                out[name + "_generate"] = timed(name + "_generate", lambda: ops.mesh_sample_generate(mv, mf, 0, ws, total))
+        if "sample_score" in names or "sample_query" in names:
+            pts = grid.sample(density=1.0e6 / math.fsum(ops.mesh_sample_count(v, f, 0.0, areas=True)[3].cpu().numpy().tolist()))
+            mgrid = ops.TriangleGrid(moved, f)
+            dist = mgrid.query(pts)[0]
+            if "sample_score" in names:
+                out["sample_score"] = timed("sample_score", lambda: ops.distance_score(dist, (0.001, 0.002, 0.005, 0.01)))
+            if "sample_query" in names:
+                out["sample_query"] = timed("sample_query", lambda: mgrid.query(pts))
     if "icp_points" in names or "icp_depth" in names:
         t0 = (-centre + torch.tensor([0.0, 0.0, 0.6], device="cuda")).cpu().numpy()
         frames = [grid.render(INTR, 480, 640, pose=(np.eye(3), t0 + dt), outputs=("depth",))["depth"] for dt in ((0, 0, 0), (0.003, -0.002, 0.001))]
