@@ -76,9 +76,17 @@
 // areas) or --evaluate-density D (samples per square metre), not both; --evaluate-seed S (default 0) picks the draws.  A sample farther
 // than --evaluate-max-dist is a miss.  The evaluate lines are the same with and without.
 //
+// Diagnostics of the deformation (opt-in; sobfu_amd/csrc/warp_stats_kernels.hip): --warp-stats [BAND] prints, after each solved
+// frame, "warp <frame>: voxels=... det min=... @x,y,z max=... mean=... folds=... (...%) disp max=... mean=... inv res max=... @x,y,z mean=...
+// above=... outside=...": det J of psi (1 = volume preserving, <= 0 = folded) and the displacement |psi - id| in metres over the voxels of
+// phi_global within BAND (default 1, units of the truncation distance) of the surface, and the residual |psi(psi_inv(x)) - x| in metres over
+// those of phi_global o psi_inv: its maximum, its mean, how many exceed a tenth of the smallest voxel side and how many psi_inv(x) leave the
+// volume.  Floats are printed as %.9g: they round-trip.  --warp-stats-dump DIR (implies --warp-stats) also writes the per-voxel volumes
+// detJ_<frame>.npy and invres_<frame>.npy (Z, Y, X float32; every voxel, masked or not; NaN where psi_inv(x) is outside or non-finite).
+//
 //   sobfu_headless <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats]
 //                  [--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE]
-//                  [--warp-mesh] [--track-mesh K] [--fit-stats]
+//                  [--warp-mesh] [--track-mesh K] [--fit-stats] [--warp-stats [BAND]] [--warp-stats-dump DIR]
 //                  (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE]
 //                   [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE]
 //                   | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | frame0.pgm frame1.pgm ...)
@@ -230,7 +238,7 @@ static std::string frame_path(const std::string& pattern, int n) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::printf("usage: %s <params.ini> [--max-iter N] [--verbose|--vverbose] [--dims N] [--dump DIR] [--mesh DIR [--mesh-format vtk|ply]] [--no-stats] "
-                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--evaluate-signed] [--evaluate-fscore TAU[,TAU...] [--evaluate-samples N | --evaluate-density D] [--evaluate-seed S]] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | depth files...)\n",
+                    "[--screenshots DIR [--screenshots-detailed]] [--track] [--poses FILE] [--warp-mesh] [--track-mesh K] [--fit-stats] [--warp-stats [BAND]] [--warp-stats-dump DIR] [--evaluate GT.ply] [--evaluate-live PATTERN] [--evaluate-max-dist METRES] [--evaluate-pose FILE] [--evaluate-align [ITERS]] [--evaluate-align-dof 3|6] [--evaluate-pose-out FILE] [--evaluate-signed] [--evaluate-fscore TAU[,TAU...] [--evaluate-samples N | --evaluate-density D] [--evaluate-seed S]] [--error-mesh DIR] (--synthetic FRAMES [--shift DX] [--textured] | --data DIR | --render-mesh PATTERN [--render-frames N] [--render-pose FILE] [--textured] [--sensor kinect|ideal [--sensor-seed N] [--sensor-set name=value]...] [--render-trajectory FILE] | --voxelise-mesh PATTERN [--render-frames N] [--render-pose FILE] | depth files...)\n",
                     argv[0]);
         return 2;
     }
@@ -244,6 +252,9 @@ int main(int argc, char** argv) {
     double shift = 0.005;
     bool textured = false, warp_mesh = false, fit_stats = false;
     int track_mesh = -1;  // the frame after which the tracked mesh is cut; -1: off
+    bool warp_stats = false;  // --warp-stats: a "warp" line after each solved frame
+    float warp_stats_band = 1.f;
+    std::string warp_stats_dump;  // --warp-stats-dump: detJ_<n>.npy and invres_<n>.npy as well
     std::string dump, mesh_dir, data_dir, mesh_format = "vtk", poses_path;
     std::string eval_gt, eval_live, eval_pose, error_dir, eval_pose_out;
     std::string render_mesh, render_pose;  // --render-mesh: the frame source; --render-pose: applied to its meshes first
@@ -282,6 +293,19 @@ int main(int argc, char** argv) {
         else if (a == "--warp-mesh") warp_mesh = true;
         else if (a == "--track-mesh" && i + 1 < argc) track_mesh = std::atoi(argv[++i]);
         else if (a == "--fit-stats") fit_stats = true;
+        else if (a == "--warp-stats") {
+            warp_stats = true;
+            char* end = nullptr;  // an optional BAND: the next argument when all of it is a number
+            const float band = i + 1 < argc ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 < argc && end != argv[i + 1] && *end == '\0') {
+                if (!std::isfinite(band) || !(band > 0.f)) {
+                    std::printf("--warp-stats %s: expected a band > 0 (units of the truncation distance)\n", argv[i + 1]);
+                    return 2;
+                }
+                warp_stats_band = band, ++i;
+            }
+        }
+        else if (a == "--warp-stats-dump" && i + 1 < argc) warp_stats = true, warp_stats_dump = argv[++i];
         else if (a == "--evaluate" && i + 1 < argc) eval_gt = argv[++i];
         else if (a == "--evaluate-live" && i + 1 < argc) eval_live = argv[++i];
         else if (a == "--evaluate-max-dist" && i + 1 < argc) eval_max_dist = std::strtof(argv[++i], nullptr);
@@ -695,6 +719,17 @@ int main(int argc, char** argv) {
                 if (warp_mesh) save_ply("phi_global_warped", m);
                 std::printf("fit %d: %zu vertices, %zu valid, mean |d| %.4f mm, rms %.4f mm, max %.4f mm (unwarped rms %.4f mm)\n", n, f.vertices, f.valid,
                             1e3 * f.mean_abs, 1e3 * f.rms, 1e3 * f.max, 1e3 * before.rms);
+            }
+        }
+        if (solved_frame && warp_stats) {
+            sobfu_amd::WarpStats ws;
+            std::vector<float> det, res;
+            const bool vols = !warp_stats_dump.empty();
+            if (fusion.warp_stats(warp_stats_band, ws, vols ? &det : nullptr, vols ? &res : nullptr)) {
+                std::printf("%s\n", sobfu_amd::format_warp_stats(ws, n).c_str());
+                const size_t X = (size_t) ws.dims[0], Y = (size_t) ws.dims[1], Z = (size_t) ws.dims[2];
+                if (vols && !sobfu_amd::write_npy(warp_stats_dump + "/detJ_" + std::to_string(n) + ".npy", det.data(), {Z, Y, X})) std::printf("cannot write detJ_%d.npy\n", n);
+                if (vols && !sobfu_amd::write_npy(warp_stats_dump + "/invres_" + std::to_string(n) + ".npy", res.data(), {Z, Y, X})) std::printf("cannot write invres_%d.npy\n", n);
             }
         }
         if (solved_frame && !eval_live.empty() && !evaluate(fusion, frame_path(eval_live, n), true, n)) return 2;

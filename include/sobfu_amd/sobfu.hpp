@@ -1306,6 +1306,8 @@ inline MeshFit mesh_fit(const IndexedMesh& m, const kfusion::cuda::TsdfVolume& v
 
 // ---- reconstruction error against a ground-truth mesh: read_ply, TriangleGrid, compare_meshes (rules: DESIGN.md 4.9) ----------------------
 #include "evaluate.hpp"
+// ---- diagnostics of the deformation: det J, folds, displacement, inverse residual (rules: DESIGN.md 4.16) ---------------------------------
+#include "warp_stats.hpp"
 
 // SobFusion (include/sobfu/sob_fusion.hpp, src/sobfu/sob_fusion.cpp:71-145) -- per-frame driver: bilateral filter ->
 // depth truncation -> dists; frame 0 builds phi_global and allocates everything; frame n builds phi_n, fuses it
@@ -1456,6 +1458,21 @@ public:
         if (model) *model = std::move(m);
         return ok;
     }
+    // Diagnostics of the last solved deformation (sobfu_amd::warp_stats): det J, folds and displacement over the voxels of phi_global within
+    // `band` (units of the truncation distance) of the surface, the residual of psi o psi_inv over those of phi_global o psi_inv; lengths in
+    // metres.  det / res (optional): the per-voxel volumes.  false before the first solve (out is untouched).  Reads the volumes only.
+    bool warp_stats(float band, sobfu_amd::WarpStats& out, std::vector<float>* det = nullptr, std::vector<float>* res = nullptr,
+                    const std::vector<float>& edges = {0.f, 0.25f, 0.5f, 1.f, 2.f, 4.f}, float res_tol = -1.f) {
+        if (!solved_) return false;
+        const cv::Vec3i d = psi->get_dims();
+        const cv::Vec3f vs = params.voxel_sizes();
+        const int dims[3] = {d[0], d[1], d[2]};
+        const float v[3] = {vs[0], vs[1], vs[2]};
+        const float tol = res_tol >= 0.f ? res_tol : (float) (0.1 * (double) std::min(v[0], std::min(v[1], v[2])));  // ops.warp_stats' default
+        out = sobfu_amd::warp_stats(psi->get_data().ptr<float>(), psi_inv->get_data().ptr<float>(), phi_global->data().ptr<float>(),
+                                    phi_global_psi_inv->data().ptr<float>(), dims, v, band, edges, tol, det, res);
+        return true;
+    }
     static sobfu_amd::TriangleMesh convert_to_mesh(const kfusion::cuda::DeviceArray<kfusion::cuda::Point>& triangles) {
         sobfu_amd::TriangleMesh m;
         if (!triangles.empty()) triangles.download(m.vertices);
@@ -1493,6 +1510,7 @@ private:
             return ++frame_counter_, true;
         }
         solver->estimate_psi(phi_global, phi_global_psi_inv, phi_n, phi_n_psi, psi, psi_inv);          // :141
+        solved_ = true;
         if (coloured) integrate_colour(image, *phi_n_psi, psi->get_data().ptr<float>());
         phi_global->integrate(*phi_n_psi);                                                             // :142
         return ++frame_counter_, true;
@@ -1528,6 +1546,7 @@ private:
         std::swap(curr_, prev_);
     }
     int frame_counter_;
+    bool solved_ = false;  // estimate_psi has run: psi and psi_inv are a solve's (warp_stats)
     Params params;
     cv::Affine3f camera_pose_;  // the current frame's pose: identity (sob_fusion.cpp:33) unless params.track_camera
     std::vector<cv::Affine3f> poses_;

@@ -820,6 +820,62 @@ int sobfu_hip_mesh_sample_generate(const float* d_vertices, int n_vertices, cons
  * +-Inf are never within.  Integer sums: the same from run to run.  n = 0 launches nothing and leaves zeros.  Asynchronous. */
 int sobfu_hip_distance_score(const float* d_dist, int n, const float* h_thresholds, int n_thresholds, long long* d_counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * warp-field diagnostics  (no counterpart in the reference; sobfu_amd/csrc/warp_stats_kernels.hip)
+ * One pass over psi (float4 per voxel: the absolute position in voxel units; dense, x fastest, 16-byte aligned), optionally psi^-1 (the
+ * same format) and up to two masks in the {tsdf, weight} float2 format: a voxel is in a mask iff the pointer is NULL or
+ * weight > 0 && fabsf(tsdf) < band.  The rules, operation by operation: sobfu_amd/csrc/sobfu_warp_stats.hpp.
+ *   u           psi - id.  Its derivative along an axis of extent n at index i: 0 when n == 1; u(1) - u(0) at i == 0 and
+ *               u(n - 1) - u(n - 2) at i == n - 1 (one-sided, not halved); (u(i + 1) - u(i - 1)) / 2 elsewhere
+ *   det         of J_rc = (r == c) + d_c u_r, the expression of sobfu_hip_warp_points; unit-free; identity: exactly 1 at every voxel
+ *   det group   (voxels in d_mask_det) a non-finite det counts in N_DET_NONFINITE only; else N_DET, N_FOLD (det <= 0),
+ *               DET_BELOW + k (det < edges[k]), the exact sum, the minimum and the maximum
+ *   disp group  (the same mask) |u| in metres, sqrtf(((u.x vs.x)^2 + (u.y vs.y)^2) + (u.z vs.z)^2): non-finite counts in
+ *               N_DISP_NONFINITE; else N_DISP, the exact sum and the maximum
+ *   res group   (only with d_psi_inv; voxels x in d_mask_res) p = psi^-1[x]: a non-finite component counts in N_RES_NONFINITE; else p
+ *               outside [0, dim - 1] on any axis in N_RES_OUTSIDE; else e = (p + u(p)) - x with u(p) by the trilinear sampler of
+ *               sobfu_hip_estimate_inverse, and |e| in metres: non-finite counts in N_RES_NONFINITE; else N_RES, N_RES_ABOVE
+ *               (|e| > res_tol), the exact sum and the maximum.  Swapping the two fields measures psi^-1 o psi
+ *   exact sums  of q = llrint(clamp((double) v, -1024, 1024) 2^44) in two signed words: HI = sum(q >> 24), LO = sum(q & 0xffffff);
+ *               the sum is (HI 2^24 + LO) 2^-44.  Independent of the order
+ *   keys        a minimum is the least (ord(v) << 32) | linear index over the group, ord the order-preserving map of the float's bits
+ *               (b ^ 0x80000000 for b >= 0, ~b for b < 0, after v + 0.f); a maximum the least (~ord(v) << 32) | index: ties go to the
+ *               lowest linear index.  An empty group leaves ~0, which decodes to NaN and index -1
+ * d_result: SOBFU_WS_WORDS 64-bit words on the device (8-byte aligned), prepared by the call (a buffer may be reused uncleared); the
+ * words beyond RES_MAX_KEY are 0.  d_det (may be NULL): det of every voxel, masked or not.  d_res (may be NULL; needs d_psi_inv): |e| of
+ * every voxel, NaN where p is outside or non-finite.  In both a NaN is the quiet NaN 0x7fc00000.
+ * The result is the same bits from run to run and for any launch shape.  Every argument is checked before any device call
+ * (SOBFU_E_BADARG): NULL or misaligned pointers, d_res or d_mask_res without d_psi_inv, an extent < 1 or more than 2^31 voxels, a voxel
+ * size or band that is not positive and finite, res_tol negative or NaN, n_edges outside 0 .. 16 or edges NULL with n_edges > 0, edges
+ * (a host array) not finite and strictly ascending.  Asynchronous.
+ * ---------------------------------------------------------------------------------------------------- */
+enum {
+    SOBFU_WS_N_DET = 0,
+    SOBFU_WS_N_FOLD = 1,
+    SOBFU_WS_N_DET_NONFINITE = 2,
+    SOBFU_WS_N_DISP = 3,
+    SOBFU_WS_N_DISP_NONFINITE = 4,
+    SOBFU_WS_N_RES = 5,
+    SOBFU_WS_N_RES_ABOVE = 6,
+    SOBFU_WS_N_RES_OUTSIDE = 7,
+    SOBFU_WS_N_RES_NONFINITE = 8,
+    SOBFU_WS_DET_BELOW = 9, /* 16 words */
+    SOBFU_WS_DET_SUM_HI = 25,
+    SOBFU_WS_DET_SUM_LO = 26,
+    SOBFU_WS_DISP_SUM_HI = 27,
+    SOBFU_WS_DISP_SUM_LO = 28,
+    SOBFU_WS_RES_SUM_HI = 29,
+    SOBFU_WS_RES_SUM_LO = 30,
+    SOBFU_WS_DET_MIN_KEY = 31,
+    SOBFU_WS_DET_MAX_KEY = 32,
+    SOBFU_WS_DISP_MAX_KEY = 33,
+    SOBFU_WS_RES_MAX_KEY = 34,
+    SOBFU_WS_WORDS = 64
+};
+int sobfu_hip_warp_stats(const float* d_psi, const float* d_psi_inv, const float* d_mask_det, const float* d_mask_res, int X, int Y, int Z,
+                         const float voxel_size[3], float band, const float* edges, int n_edges, float res_tol, unsigned long long* d_result,
+                         float* d_det, float* d_res, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

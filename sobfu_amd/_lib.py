@@ -72,6 +72,9 @@ def lib():
     L.sobfu_hip_mesh_voxelise_workspace_bytes.restype = C.c_size_t
     L.sobfu_hip_mesh_voxelise_winding_workspace_bytes.restype = C.c_size_t
     L.sobfu_hip_mesh_sample_workspace_bytes.restype = C.c_size_t
+    # psi, psi_inv, mask_det, mask_res, X, Y, Z, voxel_size[3], band, edges, n_edges, res_tol, result, det, res, stream
+    L.sobfu_hip_warp_stats.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 4
+    L.sobfu_hip_warp_stats.restype = C.c_int
     _lib = L
     return L
 

@@ -18,6 +18,7 @@ SOBFU_HPP = os.path.join(INC, "sobfu_amd", "sobfu.hpp")
 DEPTH_IO_HPP = os.path.join(INC, "sobfu_amd", "depth_io.hpp")
 SOBFU_HIP_H = os.path.join(INC, "sobfu_hip.h")
 EVALUATE_HPP = os.path.join(INC, "sobfu_amd", "evaluate.hpp")  # part of sobfu.hpp
+WARP_STATS_HPP = os.path.join(INC, "sobfu_amd", "warp_stats.hpp")  # part of sobfu.hpp
 TRAJECTORY_HPP = os.path.join(INC, "sobfu_amd", "trajectory.hpp")
 
 
@@ -44,7 +45,7 @@ def _build(out: str, src: str, deps, linked: bool, force: bool = False, flags=()
 
 def build_app(force: bool = False) -> str:
     """apps/sobfu_headless.cpp: the headless frame-loop app over the shells."""
-    return _build("sobfu_headless", os.path.join(ROOT, "apps", "sobfu_headless.cpp"), [SOBFU_HPP, EVALUATE_HPP, DEPTH_IO_HPP, TRAJECTORY_HPP, SOBFU_HIP_H], True, force)
+    return _build("sobfu_headless", os.path.join(ROOT, "apps", "sobfu_headless.cpp"), [SOBFU_HPP, EVALUATE_HPP, WARP_STATS_HPP, DEPTH_IO_HPP, TRAJECTORY_HPP, SOBFU_HIP_H], True, force)
 
 
 def build_io_tool(force: bool = False) -> str:
@@ -126,6 +127,13 @@ def build_mesh_sample_tool(force: bool = False, flags=(), out: str = "mesh_sampl
     return _build(out, _test_src("mesh_sample_tool.cpp"), deps, False, force, ["-std=c++17", f"-I{CSRC}", "-ffp-contract=off", *flags])
 
 
+def build_warp_stats_tool(force: bool = False, flags=(), out: str = "warp_stats_tool") -> str:
+    """tests/cpp/warp_stats_tool.cpp: CPU-only driver of the warp-field diagnostics' rules (sobfu_amd/csrc/sobfu_warp_stats.hpp, no HIP;
+    -ffp-contract=off, as the kernels are built).  out: the program's name under build/ (a second build with other flags keeps the first)."""
+    return _build(out, _test_src("warp_stats_tool.cpp"), [os.path.join(CSRC, "sobfu_warp_stats.hpp"), SOBFU_HIP_H], False, force,
+                  ["-std=c++17", f"-I{CSRC}", "-ffp-contract=off", *flags])
+
+
 def build_rigid_tool(force: bool = False) -> str:
     """tests/cpp/rigid_solve_tool.cpp: CPU-only driver of the shared rigid solve (sobfu_amd/csrc/sobfu_rigid.hpp, no HIP; -ffp-contract=off,
     as the kernels are built)."""
@@ -151,7 +159,7 @@ def build_pass_a_plan_tool(force: bool = False) -> str:
 
 def build_host(force: bool = False) -> str:
     for build in (build_pass_a_plan_tool, build_depth_sensor_tool, build_trajectory_tool, build_app, build_io_tool, build_png_tool, build_colour_tool, build_ply_tool, build_variant_tool, build_geometry_tool,
-                  build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_mesh_parity_tool, build_mesh_winding_tool, build_mesh_sample_tool, build_rigid_tool):
+                  build_icp_tool, build_mesh_warp_tool, build_mesh_eval_tool, build_mesh_ray_tool, build_mesh_parity_tool, build_mesh_winding_tool, build_mesh_sample_tool, build_warp_stats_tool, build_rigid_tool):
         build(force)
     return _build("host_shell_tests", _test_src("host_shell_tests.cpp"), [SOBFU_HPP, EVALUATE_HPP, SOBFU_HIP_H], True, force)
 

@@ -179,6 +179,15 @@ class SobFusion:
         self.ops.integrate_colour(colour, tsdf, psi, self.colour_global, P["vs"], R, t, P["intr"],
                                   self.ops.colour_weight_cap(P["max_weight"]))
 
+    def warp_stats(self, band=1.0, **kw):
+        """Diagnostics of the last solved deformation (ops.warp_stats): det J, folds and displacement over the voxels of
+        phi_global within `band` (units of the truncation distance) of the surface, and the residual of psi o psi_inv over those of
+        phi_global o psi_inv; lengths in metres.  kw: edges, res_tol, volumes.  None before the first solve."""
+        if self.last_report is None:
+            return None
+        return self.ops.warp_stats(self.psi, self.psi_inv, mask=self.phi_global, mask_inv=self.phi_global_psi_inv,
+                                   voxel_size=tuple(float(v) for v in self.P["vs"]), band=band, **kw)
+
     def colour_global_psi_inv(self):
         """the canonical colour warped to live, colour_global o psi_inv (computed on request); None without colour"""
         import torch

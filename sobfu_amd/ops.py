@@ -1098,6 +1098,134 @@ def distance_score(dist, thresholds):
     return c[:-1].copy(), int(c[-1])
 
 
+# ---- warp-field diagnostics (sobfu_amd/csrc/warp_stats_kernels.hip) -----------------------------------------------------
+# the result block's words (include/sobfu_hip.h, SOBFU_WS_*)
+(WS_N_DET, WS_N_FOLD, WS_N_DET_NONFINITE, WS_N_DISP, WS_N_DISP_NONFINITE, WS_N_RES, WS_N_RES_ABOVE, WS_N_RES_OUTSIDE, WS_N_RES_NONFINITE,
+ WS_DET_BELOW) = range(10)
+(WS_DET_SUM, WS_DISP_SUM, WS_RES_SUM, WS_DET_MIN_KEY, WS_DET_MAX_KEY, WS_DISP_MAX_KEY, WS_RES_MAX_KEY, WS_WORDS) = (25, 27, 29, 31, 32, 33, 34, 64)
+
+
+def _ws_signed(word):
+    word = int(word)
+    return word - (1 << 64) if word >> 63 else word
+
+
+def _ws_mean(words, at, n):
+    """(HI 2^24 + LO) 2^-44 / n, in doubles operation by operation (sobfu_amd::WarpStats does the same); NaN for an empty group"""
+    if n == 0:
+        return float("nan")
+    return (float(_ws_signed(words[at])) * 16777216.0 + float(_ws_signed(words[at + 1]))) / 17592186044416.0 / float(n)
+
+
+def _ws_key(key, maximum, dims):
+    """a key of the result block -> (value, (x, y, z)); an empty group: (NaN, (-1, -1, -1))"""
+    key = int(key)
+    if key == (1 << 64) - 1:
+        return float("nan"), (-1, -1, -1)
+    o, index = key >> 32, key & 0xFFFFFFFF
+    if maximum:
+        o = ~o & 0xFFFFFFFF
+    b = o ^ 0x80000000 if o & 0x80000000 else ~o & 0xFFFFFFFF
+    X, Y, _ = dims
+    return float(np.array([b], np.uint32).view(np.float32)[0]), (index % X, (index // X) % Y, index // (X * Y))
+
+
+@dataclasses.dataclass
+class WarpStats:
+    """What warp_stats measured, decoded from the 64 words of the result block (`words`, (64,) uint64).  det_* and disp_* cover the voxels
+    of `mask`, res_* those of `mask_inv`; lengths are in the units of voxel_size.  An empty group has NaN values and (-1, -1, -1) voxels."""
+    dims: tuple
+    words: np.ndarray
+    edges: tuple
+    has_inverse: bool
+    n_det: int
+    n_fold: int
+    n_det_nonfinite: int
+    fold_fraction: float
+    det_below: tuple  # per edge: the voxels with det < edge
+    det_min: float
+    det_min_at: tuple
+    det_max: float
+    det_max_at: tuple
+    det_mean: float
+    n_disp: int
+    n_disp_nonfinite: int
+    disp_max: float
+    disp_max_at: tuple
+    disp_mean: float
+    n_res: int
+    n_res_above: int
+    n_res_outside: int
+    n_res_nonfinite: int
+    res_max: float
+    res_max_at: tuple
+    res_mean: float
+    det: object = None  # (Z, Y, X) float32 on the GPU with volumes=True
+    res: object = None
+
+    @classmethod
+    def from_words(cls, words, dims, edges=(), has_inverse=True, det=None, res=None):
+        w = np.asarray(words, np.uint64).reshape(WS_WORDS)
+        dims = tuple(int(v) for v in dims)
+        c = [int(v) for v in w[:WS_DET_BELOW]]
+        (det_min, det_min_at), (det_max, det_max_at) = _ws_key(w[WS_DET_MIN_KEY], False, dims), _ws_key(w[WS_DET_MAX_KEY], True, dims)
+        (disp_max, disp_max_at), (res_max, res_max_at) = _ws_key(w[WS_DISP_MAX_KEY], True, dims), _ws_key(w[WS_RES_MAX_KEY], True, dims)
+        return cls(dims=dims, words=w.copy(), edges=tuple(float(e) for e in edges), has_inverse=bool(has_inverse), n_det=c[WS_N_DET], n_fold=c[WS_N_FOLD],
+                   n_det_nonfinite=c[WS_N_DET_NONFINITE], fold_fraction=c[WS_N_FOLD] / c[WS_N_DET] if c[WS_N_DET] else float("nan"),
+                   det_below=tuple(int(v) for v in w[WS_DET_BELOW:WS_DET_BELOW + len(edges)]), det_min=det_min, det_min_at=det_min_at, det_max=det_max,
+                   det_max_at=det_max_at, det_mean=_ws_mean(w, WS_DET_SUM, c[WS_N_DET]), n_disp=c[WS_N_DISP], n_disp_nonfinite=c[WS_N_DISP_NONFINITE],
+                   disp_max=disp_max, disp_max_at=disp_max_at, disp_mean=_ws_mean(w, WS_DISP_SUM, c[WS_N_DISP]), n_res=c[WS_N_RES],
+                   n_res_above=c[WS_N_RES_ABOVE], n_res_outside=c[WS_N_RES_OUTSIDE], n_res_nonfinite=c[WS_N_RES_NONFINITE], res_max=res_max,
+                   res_max_at=res_max_at, res_mean=_ws_mean(w, WS_RES_SUM, c[WS_N_RES]), det=det, res=res)
+
+    def line(self, frame):
+        """the line apps/sobfu_headless prints with --warp-stats (floats as %.9g: they round-trip)"""
+        def g(v):
+            return "nan" if v != v else "%.9g" % v
+
+        s = "warp %d: voxels=%d det min=%s @%d,%d,%d max=%s mean=%s folds=%d (%s%%) disp max=%s mean=%s" % (
+            frame, self.n_det, g(self.det_min), *self.det_min_at, g(self.det_max), g(self.det_mean), self.n_fold, g(100.0 * self.fold_fraction),
+            g(self.disp_max), g(self.disp_mean))
+        if self.has_inverse:
+            s += " inv res max=%s @%d,%d,%d mean=%s above=%d outside=%d" % (g(self.res_max), *self.res_max_at, g(self.res_mean), self.n_res_above,
+                                                                          self.n_res_outside)
+        return s
+
+
+def warp_stats(psi, psi_inv=None, mask=None, mask_inv=None, voxel_size=(1.0, 1.0, 1.0), band=1.0, edges=(0, .25, .5, 1, 2, 4), res_tol=None, volumes=False,
+               result=None):
+    """Diagnostics of the deformation psi in one pass -> WarpStats: det J (min / max with their voxels, mean, folds det <= 0, the counts
+    below each of up to 16 ascending `edges`), the displacement |psi - id| (max, mean) and, with psi_inv, the residual |psi(psi_inv(x)) - x|
+    (max with its voxel, mean, the counts above res_tol, outside the volume and non-finite); lengths in the units of voxel_size.
+    mask / mask_inv: TSDF volumes; only voxels with weight > 0 and |tsdf| < band count in the det and displacement / the residual group
+    (meant: phi_global / phi_global o psi_inv).  res_tol: default a tenth of the smallest voxel side.  volumes: also the per-voxel det
+    and residual, (Z, Y, X) float32 on the GPU (every voxel, masked or not).  result: a (64,) int64 GPU tensor to reuse, cleared or not.
+    Every figure is an exact integer sum or minimum: the same bits from run to run (the rules: sobfu_amd/csrc/sobfu_warp_stats.hpp).
+    Swapping psi and psi_inv measures psi_inv o psi.  Synchronises to read the result."""
+    vs = [float(np.float32(v)) for v in voxel_size]  # as the kernel takes them: the default res_tol is the C++ twin's, bit for bit
+    ed = [float(e) for e in edges]
+    if len(ed) > 16:
+        raise ValueError("at most 16 edges")
+    if psi_inv is None and mask_inv is not None:
+        raise ValueError("mask_inv needs psi_inv")
+    for t, last in ((psi_inv, 4), (mask, 2), (mask_inv, 2)):
+        if t is not None and tuple(t.shape) != tuple(psi.shape[:3]) + (last,):
+            raise ValueError(f"expected a {tuple(psi.shape[:3]) + (last,)} tensor, got {tuple(t.shape)}")
+    Z, Y, X = psi.shape[:3]
+    tol = 0.1 * min(vs) if res_tol is None else float(res_tol)
+    words = torch.empty(WS_WORDS, dtype=torch.int64, device=psi.device) if result is None else result
+    det = torch.empty((Z, Y, X), dtype=torch.float32, device=psi.device) if volumes else None
+    res = torch.empty((Z, Y, X), dtype=torch.float32, device=psi.device) if volumes and psi_inv is not None else None
+
+    def opt(t):
+        return None if t is None else _ptr(t)
+
+    check(_lib.lib().sobfu_hip_warp_stats(_ptr(psi), opt(psi_inv), opt(mask), opt(mask_inv), *_xyz(psi), _F3(*vs), _f(band),
+                                          (C.c_float * len(ed))(*ed) if ed else None, C.c_int(len(ed)), _f(tol), _ptr(words, torch.int64), opt(det), opt(res),
+                                          _stream()), "warp_stats")
+    return WarpStats.from_words(words.cpu().numpy().view(np.uint64), (X, Y, Z), ed, psi_inv is not None, det, res)
+
+
 # ---- camera tracking (sobfu_amd/csrc/icp_kernels.hip): projective ICP and its image pyramids -------------------------------------
 class IcpLevel(C.Structure):
     """sobfu_hip_icp_level"""
